@@ -5,7 +5,7 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 
 ``--gpus N`` WITHOUT a launcher (no WORLD_SIZE in the environment) starts the N ranks itself: the parent makes no GPU call,
 spawns ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a child, relays rank 0's line and exits with
 the children's code; fewer than N visible devices (or a WORLD_SIZE that contradicts ``--gpus``) is a non-zero exit, never
-an ``n_gpus: 1`` line.  At N > 1 every rank also runs BASELINE config 4 -- the pretrain_3g-shaped step, B = 64 per rank, with
+an ``n_gpus: 1`` line.  With ``--full``, at N > 1 every rank also runs BASELINE config 4 -- the pretrain_3g-shaped step, B = 64 per rank, with
 the bucketed RCCL gradient all-reduce (``engine.GradientReducer``; ranks draw their graphs with seed + rank,
 /root/reference/script/run_full.py:102-107) -- timed as max over ranks, next to the same steps without the collectives.
 
@@ -18,6 +18,14 @@ epilogues + score MLP = 18 rspmm calls; here the tail and head queries share ONE
 bit-identical: tests/test_model_gpu.py), replayed as one hipGraph.  All inputs are resident in HBM before the timed
 region.  Multi-GPU: every rank holds the graph and evaluates its own query batch (query sharding, no data-path
 collective) => weak scaling; ``value`` = units of all ranks / max-over-ranks time.
+
+A plain run does only what the headline needs: set-up, ``--warmup`` steps, the ``--steps`` timed steps, the result line
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = milliseconds of one timed step, and the
+spread of the blocks inside the timed region).  Everything else below -- the per-kernel and composition timings after the
+timed region, the per-config timings (``config.configs``), S-stress (``roofline``), MRR with the CPU-oracle check, the
+fine-tuning run, ``cpu_baseline`` -- runs with ``--full`` only.  ``--dump-outputs DIR`` writes what the timed path returned in
+its last step (rank 0): ``DIR/scores.npy``, the float32 (B, 2, N) scores of ``predict``; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 What ``value`` counts (round 3).  Unit of work = one edge message = one ENTITY-graph edge x one
 query x 64 fp32 lanes that a kernel actually VISITS.  Per step: layers 2-6 walk all E edges for 2B queries
@@ -1023,6 +1031,19 @@ def distinct_devices(dev, world, share):
     return len({int(t.item()) for t in parts})
 
 
+def dump_outputs(out_dir, arrays, cap_bytes=64_000_000):
+    """``--dump-outputs DIR``: each array as ``DIR/<name>.npy`` in float32.  Arrays larger together than ``cap_bytes`` are
+    cut to the same seeded sample of their flattened elements (sorted positions) in every run, so dumps stay comparable."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * a.numel() for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.detach().float()
+        if total > cap_bytes:
+            pos = np.unique(np.random.default_rng(0).integers(0, a.numel(), max(1, a.numel() * cap_bytes // total)))
+            a = a.reshape(-1)[torch.from_numpy(pos).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1043,7 +1064,15 @@ def main():
     ap.add_argument("--data", default=None, help="directory with train.txt / valid.txt / test.txt (h<TAB>r<TAB>t lines): also "
                                                  "evaluate the test split of this REAL dataset (result key `real_data`)")
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (td_ultra_3g.pth / td_ultra_4g.pth layout) for --data")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement: per-kernel and composition timings, per-config timings, "
+                         "S-stress roofline, MRR with the CPU-oracle check, fine-tuning, cpu_baseline (shaped by --no-stress, "
+                         "--no-configs, --no-cpu-baseline, --stress-shape, --mrr-queries, --finetune-steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores the last timed step returned (rank 0) as DIR/scores.npy, float32 (B, 2, N)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1 (the headline is the HIP path; config 1's CPU run is inside the N=1 line)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1096,11 +1125,12 @@ def main():
     test_idx = np.arange(n_fact, n_fact + n_test)
     und = task.model._undirected(task.fact_graph)
     _ = und.relcsr.fwd                  # coalesce + sort + chunk schedule: once per graph (torchdrug: every rspmm call)
-    torch.cuda.synchronize()
-    t_plan = time.perf_counter()        # steady-state cost of that build (the first one above also warms rocPRIM up)
-    _ = U.RelCSR.from_edge_list(und.edge_list, und.edge_weight, und.num_node, und.num_relation).fwd
-    torch.cuda.synchronize()
-    plan_build_ms = 1e3 * (time.perf_counter() - t_plan)
+    if args.full:
+        torch.cuda.synchronize()
+        t_plan = time.perf_counter()        # steady-state cost of that build (the first one above also warms rocPRIM up)
+        _ = U.RelCSR.from_edge_list(und.edge_list, und.edge_weight, und.num_node, und.num_relation).fwd
+        torch.cuda.synchronize()
+        plan_build_ms = 1e3 * (time.perf_counter() - t_plan)
     prepare_plans(task)
     E, R2 = und.relcsr.n_edges, und.num_relation
     E_rel = task.rel_graphs[0].relcsr.n_edges
@@ -1140,7 +1170,8 @@ def main():
             lib.ultra_rspmm_profile_next(a, b)
         return real_forward(csr, relation, input, sum, mul, add_rows, boundary)
 
-    UF.rspmm_forward = timed_forward
+    if args.full:
+        UF.rspmm_forward = timed_forward
 
     # the evaluation batch is replayed as one hipGraph (engine.GraphedPredict); --eager times the un-captured path
     from ultra_torchdrug_amd.engine import GraphedPredict
@@ -1193,7 +1224,7 @@ def main():
         marks[0].record()
         nxt = 1
         for i in range(args.steps):
-            step(args.warmup + i)
+            last = step(args.warmup + i)
             if i + 1 == edges_at[nxt]:
                 marks[nxt].record()
                 nxt += 1
@@ -1206,65 +1237,69 @@ def main():
         state["on"] = False
         frontier_visited = sum(frontier_per_batch[(args.warmup + i) % n_batches] for i in range(args.steps))
 
-        # ---- after the timed region: the dominant kernel alone, and the other per-step numbers
-        phases.enter("per-kernel timings after the timed region")
-        gen = torch.Generator(device=dev).manual_seed(DEFAULT_SEED)
-        xk = torch.randn(n_node, Fk, device=dev, generator=gen)
-        rk = torch.randn(R2, Fk, device=dev, generator=gen)
-        # the layer's sparse boundary: the heads and tails of a REAL batch (Zipf hubs: a uniformly drawn boundary would
-        # flatter the first-layer frontier kernel by an order of magnitude)
-        bk = (torch.cat([shard[:B, 0], shard[:B, 1]])[:Fk // 64].to(torch.int32).contiguous(),
-              torch.randn(Fk // 64, 64, device=dev, generator=gen))
-        if graphed is not None:
-            for _ in range(4):
-                real_forward(und.relcsr, rk, xk, "add", "mul", None, bk)
-            state["on"] = True
-            for _ in range(48):
-                timed_forward(und.relcsr, rk, xk, "add", "mul", None, bk)
-            state["on"] = False
+        if args.dump_outputs and rank == 0:        # what a caller of the timed path received from its last step
+            dump_outputs(args.dump_outputs, {"scores": last})
+
+        if args.full:
+            # ---- after the timed region: the dominant kernel alone, and the other per-step numbers
+            phases.enter("per-kernel timings after the timed region")
+            gen = torch.Generator(device=dev).manual_seed(DEFAULT_SEED)
+            xk = torch.randn(n_node, Fk, device=dev, generator=gen)
+            rk = torch.randn(R2, Fk, device=dev, generator=gen)
+            # the layer's sparse boundary: the heads and tails of a REAL batch (Zipf hubs: a uniformly drawn boundary would
+            # flatter the first-layer frontier kernel by an order of magnitude)
+            bk = (torch.cat([shard[:B, 0], shard[:B, 1]])[:Fk // 64].to(torch.int32).contiguous(),
+                  torch.randn(Fk // 64, 64, device=dev, generator=gen))
+            if graphed is not None:
+                for _ in range(4):
+                    real_forward(und.relcsr, rk, xk, "add", "mul", None, bk)
+                state["on"] = True
+                for _ in range(48):
+                    timed_forward(und.relcsr, rk, xk, "add", "mul", None, bk)
+                state["on"] = False
+                torch.cuda.synchronize()
+            kernel_ms = events.elapsed_ms()
+            n_side = min(args.steps, 50)
+            eager_ms = wall_ms(lambda i: task.predict(shard[:B]), 5) if graphed is not None else 1e3 * elapsed / args.steps
+            # predict + filtered ranking (what engine.evaluate does per batch): the ranks come from the sorted completion keys
+            # on the device, nothing but (B, 2) int64 leaves it
+            rank_ms = wall_ms(lambda i: task.rank_batch(shard[:B], pred=step(i)), n_side)
+            # the same step without the first-layer frontier shortcut (every layer walks all E edges)
+            UL.FRONTIER_FIRST_LAYER = False
+            try:
+                plain = None if args.eager else capture()
+                no_frontier_ms = wall_ms(lambda i: step(i, plain), n_side, warm=5)
+            finally:
+                UL.FRONTIER_FIRST_LAYER = True
+            frontier_ms, _ = timed_kernel(lib, events, lambda: UF.rspmm_frontier(und.relcsr, rk, bk), 10)
+            # the same step with the first layer's epilogue over ALL rows (round 3's form; round 4 runs it on the rows the frontier
+            # reaches and broadcasts one constant row everywhere else: ultra_first_layer_sparse_f32)
+            UF.SPARSE_FIRST_LAYER = False
+            try:
+                dense_first = None if args.eager else capture()
+                dense_first_ms = wall_ms(lambda i: step(i, dense_first), n_side, warm=5)
+            finally:
+                UF.SPARSE_FIRST_LAYER = True
+            # the same step with the relation representations of all R relations computed once per evaluation run
+            # (task.cache_relation_representations, what engine.evaluate does): identical scores, the relation stack leaves
+            # the per-batch path.
             torch.cuda.synchronize()
-        kernel_ms = events.elapsed_ms()
-        n_side = min(args.steps, 50)
-        eager_ms = wall_ms(lambda i: task.predict(shard[:B]), 5) if graphed is not None else 1e3 * elapsed / args.steps
-        # predict + filtered ranking (what engine.evaluate does per batch): the ranks come from the sorted completion keys
-        # on the device, nothing but (B, 2) int64 leaves it
-        rank_ms = wall_ms(lambda i: task.rank_batch(shard[:B], pred=step(i)), n_side)
-        # the same step without the first-layer frontier shortcut (every layer walks all E edges)
-        UL.FRONTIER_FIRST_LAYER = False
-        try:
-            plain = None if args.eager else capture()
-            no_frontier_ms = wall_ms(lambda i: step(i, plain), n_side, warm=5)
-        finally:
-            UL.FRONTIER_FIRST_LAYER = True
-        frontier_ms, _ = timed_kernel(lib, events, lambda: UF.rspmm_frontier(und.relcsr, rk, bk), 10)
-        # the same step with the first layer's epilogue over ALL rows (round 3's form; round 4 runs it on the rows the frontier
-        # reaches and broadcasts one constant row everywhere else: ultra_first_layer_sparse_f32)
-        UF.SPARSE_FIRST_LAYER = False
-        try:
-            dense_first = None if args.eager else capture()
-            dense_first_ms = wall_ms(lambda i: step(i, dense_first), n_side, warm=5)
-        finally:
-            UF.SPARSE_FIRST_LAYER = True
-        # the same step with the relation representations of all R relations computed once per evaluation run
-        # (task.cache_relation_representations, what engine.evaluate does): identical scores, the relation stack leaves
-        # the per-batch path.
-        torch.cuda.synchronize()
-        t_c = time.perf_counter()
-        task.cache_relation_representations(B)
-        torch.cuda.synchronize()
-        cache_build_ms = 1e3 * (time.perf_counter() - t_c)
-        try:
-            cached = None if args.eager else capture()
-            cached_ms = wall_ms(lambda i: step(i, cached), n_side, warm=5)
-            replay_same_cached = replays_equal_eager(cached)
-        finally:
-            task.clear_relation_cache()
-        replay_same = replays_equal_eager(graphed)
-        # the same replays once the process has kept the GPU busy for seconds: the clocks settle ~2 % below the first second's
-        # (tools/debug/capture_order_probe.py: the FIRST 300 replays of a process 2.00 ms, every later 300 -- same graph -- 2.04)
-        sustained_ms = wall_ms(lambda i: step(i), 300, warm=20) if graphed is not None else None
-        # the relation-graph stack alone (what the step spends outside the entity graph and the score head)
-        rel_ms = wall_ms(lambda i: task.relation_representations(shard[:B, 2]), 20, warm=3)
+            t_c = time.perf_counter()
+            task.cache_relation_representations(B)
+            torch.cuda.synchronize()
+            cache_build_ms = 1e3 * (time.perf_counter() - t_c)
+            try:
+                cached = None if args.eager else capture()
+                cached_ms = wall_ms(lambda i: step(i, cached), n_side, warm=5)
+                replay_same_cached = replays_equal_eager(cached)
+            finally:
+                task.clear_relation_cache()
+            replay_same = replays_equal_eager(graphed)
+            # the same replays once the process has kept the GPU busy for seconds: the clocks settle ~2 % below the first second's
+            # (tools/debug/capture_order_probe.py: the FIRST 300 replays of a process 2.00 ms, every later 300 -- same graph -- 2.04)
+            sustained_ms = wall_ms(lambda i: step(i), 300, warm=20) if graphed is not None else None
+            # the relation-graph stack alone (what the step spends outside the entity graph and the score head)
+            rel_ms = wall_ms(lambda i: task.relation_representations(shard[:B, 2]), 20, warm=3)
     UF.rspmm_forward = real_forward
 
     # per-rank times (the driver computes scaling efficiency from `value`; this shows which rank set the max)
@@ -1295,7 +1330,7 @@ def main():
     ranks = RankReduce(world, dev, share)
     devices = distinct_devices(dev, world, share)          # a collective: every rank
     pretrain_n = None
-    if world > 1 and args.configs:                   # config 4 with the RCCL gradient all-reduce: every rank takes part
+    if world > 1 and args.full and args.configs:     # config 4 with the RCCL gradient all-reduce: every rank takes part
         del xk, rk
         torch.cuda.empty_cache()
         phases.enter("config 4: capture of three graphs + steps with the gradient all-reduce", 900)
@@ -1314,18 +1349,11 @@ def main():
         xk = rk = None
     stress_shape = tuple(int(v) for v in args.stress_shape.split(",")) if args.stress_shape else (10_000_000, 50_000_000, 500)
     stress_n = None
-    if world > 1 and args.stress:                    # config 5 at N GPUs: every rank takes part
+    if world > 1 and args.full and args.stress:      # config 5 at N GPUs: every rank takes part
         torch.cuda.empty_cache()
         phases.enter("config 5 on every rank: S-stress replicas, each rank its own triples", 900)
         stress_n = stress_inference_ranks(dev, rank, world, ranks, stress_shape)
-    phases.enter("MRR, evaluation runs, configs (rank 0), final barrier", 1800)
-
-    k_avg_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
-    algo = bytes_algo(E, n_node, R2, Fk)
-    compulsory = bytes_min(E, n_node, R2, Fk)
-    achieved = algo / (k_avg_ms * 1e-3) / 1e9
-    tj, traffic_source = latest_profile("traffic_fwd_fb15k237.json")
-    traffic = tj.get("hbm_bytes_per_launch") if (tj and tj.get("F") == Fk and args.workload == "S-fb15k237") else None
+    phases.enter("MRR, evaluation runs, configs (rank 0), final barrier" if args.full else "result line, final barrier", 1800)
 
     # ---------------- MRR (after the timed region): HIP path, and HIP vs CPU-oracle path on the same weights --------
     def mrr_of(t, queries):
@@ -1363,7 +1391,7 @@ def main():
 
     # ---------------- whole evaluation runs over the seeded test triples (engine.evaluate), three ways, same ranks ----
     eval_runs = None
-    if rank == 0 and world == 1 and args.mrr_queries > 0:
+    if args.full and rank == 0 and world == 1 and args.mrr_queries > 0:
         from ultra_torchdrug_amd import engine
         eval_runs = {"triples": int(len(test))}
         checks = []
@@ -1383,7 +1411,7 @@ def main():
     metrics = metrics_tuned = None
     mrr_check = []
     train = None
-    if args.mrr_queries > 0:
+    if args.full and args.mrr_queries > 0:
         # the seeded test triples are strided over the ranks; one all_gather of (n, 2) int64 ranks
         nq = min(-(-args.mrr_queries // world), len(test) // world)       # the same count on every rank
 
@@ -1414,75 +1442,86 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         visited = full_layers_edges * args.steps * world + frontier_all        # entity-graph messages visited, all ranks
-        l2_line = {"bound": "l2-gather", "kernel": "quad_kernel<FWD,add,mul,unit_w,8>", "workload": args.workload,
-                   "achieved": achieved, "peak": L2_PEAK_GBS, "unit": "GB/s", "frac": achieved / L2_PEAK_GBS,
-                   "algorithmic_bytes": algo, "kernel_ms": k_avg_ms, "launches_timed": len(kernel_ms),
-                   "l2_gather_ceiling": list(L2_GATHER_CEILING_GBS),
-                   "frac_of_l2_gather_ceiling": achieved / L2_GATHER_CEILING_GBS[1],
-                   "hbm_compulsory_bytes": compulsory,
-                   "hbm_frac_on_compulsory_bytes": compulsory / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                   "traffic": traffic, "traffic_source": traffic_source if traffic else None,
-                   "note": "the gathered matrix (%.0f MB) is L2 / Infinity-Cache resident: its algorithmic rate exceeds the "
-                           "HBM peak (%.1f TB/s), so it is priced against the XCD-L2 peak (MI355X_MICROARCH.md: 34.5 TB/s; "
-                           "measured ceiling for rows gathered from L2: 16.8-18.8 TB/s); not an HBM-roofline workload "
-                           "(SURVEY 8d)" % (n_node * Fk * 4 / 1e6, achieved / 1e3)}
-        configs = []
-        roofline = dict(l2_line)
-        xk = rk = None
-        torch.cuda.empty_cache()
-        if world == 1 and args.configs:
-            configs = config_timings(dev, lib, DEFAULT_SEED, B, quick=args.steps < 100)
-        if pretrain_n is not None:
-            configs.append(pretrain_n)
-        if args.stress:                             # rank 0 of any world: the other ranks wait at the final barrier
-            roofline = stress_roofline(dev, lib, n_node=stress_shape[0], n_triple=stress_shape[1], n_base_rel=stress_shape[2],
-                                       cpu_leg=(world == 1 and not args.no_cpu_baseline))
-            roofline["l2"] = l2_line
-            inf = roofline["inference"]
-            configs.append({"config": 5, "name": "Synthetic KG 10M nodes / 100M edges / 1k relations, 64d inference (HBM-roofline stress)",
-                            "shape": roofline["workload"], "operator_fwd_ms": roofline["kernel_ms"],
-                            "edges_per_s": roofline["edges_per_s"], "frac_of_hbm_peak": roofline["frac"],
-                            "plan_build_s": roofline["plan_build_s"],
-                            "predict_ms": inf["b1"]["predict_ms"], "predict_ms_b4": inf["b4"]["predict_ms"],
-                            "filtered_rank_ms": inf["b1"]["filtered_rank_ms"],
-                            "end_to_end_edges_per_s": inf["b1"]["entity_edge_messages_per_s"],
-                            "end_to_end_edges_per_s_b4": inf["b4"]["entity_edge_messages_per_s"],
-                            "layer_breakdown_b1": inf["layer_b1"],
-                            "frac_of_hbm_peak_whole_layer": inf["layer_b1"]["frac_of_hbm_peak_whole_layer"],
-                            "operator_b4_ms": roofline["b4"]["kernel_ms"], "operator_b4_frac": roofline["b4"]["frac"],
-                            "all_ranks": stress_n})
+        if args.full:
+            k_avg_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
+            algo = bytes_algo(E, n_node, R2, Fk)
+            compulsory = bytes_min(E, n_node, R2, Fk)
+            achieved = algo / (k_avg_ms * 1e-3) / 1e9
+            tj, traffic_source = latest_profile("traffic_fwd_fb15k237.json")
+            traffic = tj.get("hbm_bytes_per_launch") if (tj and tj.get("F") == Fk and args.workload == "S-fb15k237") else None
+            l2_line = {"bound": "l2-gather", "kernel": "quad_kernel<FWD,add,mul,unit_w,8>", "workload": args.workload,
+                       "achieved": achieved, "peak": L2_PEAK_GBS, "unit": "GB/s", "frac": achieved / L2_PEAK_GBS,
+                       "algorithmic_bytes": algo, "kernel_ms": k_avg_ms, "launches_timed": len(kernel_ms),
+                       "l2_gather_ceiling": list(L2_GATHER_CEILING_GBS),
+                       "frac_of_l2_gather_ceiling": achieved / L2_GATHER_CEILING_GBS[1],
+                       "hbm_compulsory_bytes": compulsory,
+                       "hbm_frac_on_compulsory_bytes": compulsory / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                       "traffic": traffic, "traffic_source": traffic_source if traffic else None,
+                       "note": "the gathered matrix (%.0f MB) is L2 / Infinity-Cache resident: its algorithmic rate exceeds the "
+                               "HBM peak (%.1f TB/s), so it is priced against the XCD-L2 peak (MI355X_MICROARCH.md: 34.5 TB/s; "
+                               "measured ceiling for rows gathered from L2: 16.8-18.8 TB/s); not an HBM-roofline workload "
+                               "(SURVEY 8d)" % (n_node * Fk * 4 / 1e6, achieved / 1e3)}
+            configs = []
+            roofline = dict(l2_line)
+            xk = rk = None
+            torch.cuda.empty_cache()
+            if world == 1 and args.configs:
+                configs = config_timings(dev, lib, DEFAULT_SEED, B, quick=args.steps < 100)
+            if pretrain_n is not None:
+                configs.append(pretrain_n)
+            if args.stress:                             # rank 0 of any world: the other ranks wait at the final barrier
+                roofline = stress_roofline(dev, lib, n_node=stress_shape[0], n_triple=stress_shape[1], n_base_rel=stress_shape[2],
+                                           cpu_leg=(world == 1 and not args.no_cpu_baseline))
+                roofline["l2"] = l2_line
+                inf = roofline["inference"]
+                configs.append({"config": 5, "name": "Synthetic KG 10M nodes / 100M edges / 1k relations, 64d inference (HBM-roofline stress)",
+                                "shape": roofline["workload"], "operator_fwd_ms": roofline["kernel_ms"],
+                                "edges_per_s": roofline["edges_per_s"], "frac_of_hbm_peak": roofline["frac"],
+                                "plan_build_s": roofline["plan_build_s"],
+                                "predict_ms": inf["b1"]["predict_ms"], "predict_ms_b4": inf["b4"]["predict_ms"],
+                                "filtered_rank_ms": inf["b1"]["filtered_rank_ms"],
+                                "end_to_end_edges_per_s": inf["b1"]["entity_edge_messages_per_s"],
+                                "end_to_end_edges_per_s_b4": inf["b4"]["entity_edge_messages_per_s"],
+                                "layer_breakdown_b1": inf["layer_b1"],
+                                "frac_of_hbm_peak_whole_layer": inf["layer_b1"]["frac_of_hbm_peak_whole_layer"],
+                                "operator_b4_ms": roofline["b4"]["kernel_ms"], "operator_b4_frac": roofline["b4"]["frac"],
+                                "all_ranks": stress_n})
+            flat = flat_config_keys(configs)
+            first = mrr_check[0] if mrr_check else {}
         # ---- `config`: the driver's record keeps about twenty scalars of it, in order, strings cut at ~128 characters (VERDICT r4
         # weak 8: the MRR half of the metric and configs 3-5 fell off the end) -- so the ones a reader needs come first
-        flat = flat_config_keys(configs)
-        first = mrr_check[0] if mrr_check else {}
         config = {
             "workload": "%s N=%d E=%d R=%d B=%d F=%d, 6+6 layers x 64d, predict() tail+head over all entities"
                         % (args.workload, n_node, E, R2, B, F),
             "launch": "eager" if graphed is None else "hipGraph replay per step (engine.GraphedPredict)",
-            "ms_per_step_sustained": sustained_ms,
-            "mrr_hip": mrr,                                             # filtered MRR, HIP path, `mrr_queries` seeded test triples
-            "mrr_hip_first_batch": first.get("mrr_hip"),                # the same B triples on both paths:
-            "mrr_cpu_oracle_first_batch": first.get("mrr_cpu_oracle"),
-            "ranks_identical": "%d/%d" % (first["ranks_identical"], first["ranks_total"]) if first else None,
-            "max_abs_score_diff": first.get("max_abs_score_diff"),
-            "cfg1_cpu_ms_per_batch": flat.get("cfg1_cpu_ms_per_batch"),
-            "cfg2_predict_ms": flat.get("cfg2_predict_ms"),
-            "cfg3_step_median_ms": flat.get("cfg3_step_median_ms"),
-            "cfg3_fwd_us": flat.get("cfg3_fwd_us"),
-            "cfg3_bwd_us": flat.get("cfg3_bwd_us"),
-            "cfg4_step_median_ms": flat.get("cfg4_step_median_ms"),
-            "cfg4_step_ms_max_over_ranks": flat.get("cfg4_step_ms_max_over_ranks"),
-            "cfg4_allreduce_exposed_ms_per_step": flat.get("cfg4_allreduce_exposed_ms_per_step"),
-            "cfg5_frac": flat.get("cfg5_frac"),
-            "cfg5_fwd_ms": flat.get("cfg5_fwd_ms"),
-            "cfg5_predict_ms": flat.get("cfg5_predict_ms"),
-            "cfg5_whole_layer_frac": flat.get("cfg5_whole_layer_frac"),
+        }
+        if args.full:
+            config.update({
+                "ms_per_step_sustained": sustained_ms,
+                "mrr_hip": mrr,                                             # filtered MRR, HIP path, `mrr_queries` seeded test triples
+                "mrr_hip_first_batch": first.get("mrr_hip"),                # the same B triples on both paths:
+                "mrr_cpu_oracle_first_batch": first.get("mrr_cpu_oracle"),
+                "ranks_identical": "%d/%d" % (first["ranks_identical"], first["ranks_total"]) if first else None,
+                "max_abs_score_diff": first.get("max_abs_score_diff"),
+                "cfg1_cpu_ms_per_batch": flat.get("cfg1_cpu_ms_per_batch"),
+                "cfg2_predict_ms": flat.get("cfg2_predict_ms"),
+                "cfg3_step_median_ms": flat.get("cfg3_step_median_ms"),
+                "cfg3_fwd_us": flat.get("cfg3_fwd_us"),
+                "cfg3_bwd_us": flat.get("cfg3_bwd_us"),
+                "cfg4_step_median_ms": flat.get("cfg4_step_median_ms"),
+                "cfg4_step_ms_max_over_ranks": flat.get("cfg4_step_ms_max_over_ranks"),
+                "cfg4_allreduce_exposed_ms_per_step": flat.get("cfg4_allreduce_exposed_ms_per_step"),
+                "cfg5_frac": flat.get("cfg5_frac"),
+                "cfg5_fwd_ms": flat.get("cfg5_fwd_ms"),
+                "cfg5_predict_ms": flat.get("cfg5_predict_ms"),
+                "cfg5_whole_layer_frac": flat.get("cfg5_whole_layer_frac"),
+            })
+        config.update({
             "collective_backend": (dist.get_backend() if world > 1 else "none (one rank)"),
             "ranks_distinct_devices": devices,
             "ms_per_step_block_median": headline_blocks["median_ms"],
             "ms_per_step_block_min": headline_blocks["min_ms"], "ms_per_step_block_max": headline_blocks["max_ms"],
             "global_batch": B * world, "parallelism": "query-sharded replicas x%d" % world,
-            "relation_stack_ms_per_step": rel_ms,
             "entity_edges_visited_per_step": visited / (args.steps * world),
             "frontier_edges_per_step": frontier_all / (args.steps * world),
             "device": "%s, %d CUs" % (torch.cuda.get_device_name(dev), torch.cuda.get_device_properties(dev).multi_processor_count),
@@ -1490,15 +1529,10 @@ def main():
             "value_counts": "ENTITY-graph edge messages the kernels visit: 10*E*B per step (layers 2-6, 2B queries) "
                             "+ the boundary nodes' out-edges in layer 1 (frontier kernel), over the WHOLE step time "
                             "(relation stack and score head included in the time, not in the count)",
-            "relation_graph_edges_per_step": rel_edges_per_step,
-            "relation_graph_edges_per_s": rel_edges_per_step / (rel_ms * 1e-3),
-            "value_r2_definition": (12 * E * B + rel_edges_per_step) * args.steps * world / elapsed,
             "value_block_median": (visited / (args.steps * world)) * world / (headline_blocks["median_ms"] * 1e-3),
             "per_rank_ms_per_step": per_rank_ms,
             "per_rank_value": [(full_layers_edges + frontier_all / (args.steps * world)) / (m * 1e-3) for m in per_rank_ms],
-        }
-        config.update({k: v for k, v in flat.items() if k not in config})
-        config["configs"] = configs
+        })
         result = {
             "metric": "edges aggregated/sec, FB15k237-shaped 6L x 64d rspmm Bellman-Ford (predict: the reference's 18 rspmm layers per batch as 6 relation-graph + 6 entity-graph launches, tails and heads in one pass)",
             "value": visited / elapsed,
@@ -1508,47 +1542,58 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": config,
-            "roofline": roofline,
-            "composition": {
-                "ms_per_step_without_first_layer_frontier": no_frontier_ms,
-                "value_all_layers_full_kernel": 12 * E * B * world / (no_frontier_ms * 1e-3),
-                "first_layer_frontier_kernel_ms": frontier_ms,
-                "ms_per_step_with_dense_first_layer_epilogue": dense_first_ms,
-                "ms_per_step_with_cached_relation_representations": cached_ms,
-                "value_with_cached_relation_representations":
-                    (visited / (args.steps * world)) / (cached_ms * 1e-3) if cached_ms else None,
-                "relation_cache_build_ms": cache_build_ms,
-                "evaluate_test_set": eval_runs,
-                "graph_replays_identical_to_eager": {"per_batch_relations": replay_same, "cached_relations": replay_same_cached},
-                "relation_graph_note": "E_rel = %d over %d relation nodes and 4 edge types: with independently drawn Zipf "
-                                       "heads / tails / relations (SURVEY 8d generator) every pair of relations co-occurs, "
-                                       "so the relation graph is complete -- LDS-resident, not a sparse-gather workload"
-                                       % (E_rel, R2),
-                "predict_plus_filtered_rank_ms_per_step": rank_ms,
-                "finetune_step": train,
-                "finetune_note": "config 3's step on this graph (B = %d, 128 strict negatives, AdamW): negatives, edge removal, "
-                                 "forward and backward replayed as one hipGraph (engine.GraphedTrainStep); per-step wall "
-                                 "times, device-synchronised" % B,
-            },
-            "plan_build_ms": plan_build_ms,
-            "eager_ms_per_step": eager_ms,
-            "rspmm_kernel_only": {"kernel": "quad_kernel<FWD,add,mul,unit_w> (entity graph, F = %d: tail and head queries of the batch in one launch)" % Fk,
-                                  "launches_timed": len(kernel_ms), "avg_ms": k_avg_ms,
-                                  "timed": "every launch of the timed region" if graphed is None else
-                                           "%d eager launches of the same kernel/shapes right after the timed region "
-                                           "(event records cannot be captured into the hipGraph with this HIP runtime)" % len(kernel_ms),
-                                  "edges_per_s": E * (Fk // 64) / (k_avg_ms * 1e-3) if kernel_ms else None},
-            "mrr_hip": mrr,
-            "mrr_hip_after_finetune": mrr_tuned,
-            "metrics_hip": metrics,
-            "metrics_hip_after_finetune": metrics_tuned,
-            "mrr_check": mrr_check,
         }
+        if args.full:
+            config.update({
+                "relation_stack_ms_per_step": rel_ms,
+                "relation_graph_edges_per_step": rel_edges_per_step,
+                "relation_graph_edges_per_s": rel_edges_per_step / (rel_ms * 1e-3),
+                "value_r2_definition": (12 * E * B + rel_edges_per_step) * args.steps * world / elapsed,
+            })
+            config.update({k: v for k, v in flat.items() if k not in config})
+            config["configs"] = configs
+            result.update({
+                "roofline": roofline,
+                "composition": {
+                    "ms_per_step_without_first_layer_frontier": no_frontier_ms,
+                    "value_all_layers_full_kernel": 12 * E * B * world / (no_frontier_ms * 1e-3),
+                    "first_layer_frontier_kernel_ms": frontier_ms,
+                    "ms_per_step_with_dense_first_layer_epilogue": dense_first_ms,
+                    "ms_per_step_with_cached_relation_representations": cached_ms,
+                    "value_with_cached_relation_representations":
+                        (visited / (args.steps * world)) / (cached_ms * 1e-3) if cached_ms else None,
+                    "relation_cache_build_ms": cache_build_ms,
+                    "evaluate_test_set": eval_runs,
+                    "graph_replays_identical_to_eager": {"per_batch_relations": replay_same, "cached_relations": replay_same_cached},
+                    "relation_graph_note": "E_rel = %d over %d relation nodes and 4 edge types: with independently drawn Zipf "
+                                           "heads / tails / relations (SURVEY 8d generator) every pair of relations co-occurs, "
+                                           "so the relation graph is complete -- LDS-resident, not a sparse-gather workload"
+                                           % (E_rel, R2),
+                    "predict_plus_filtered_rank_ms_per_step": rank_ms,
+                    "finetune_step": train,
+                    "finetune_note": "config 3's step on this graph (B = %d, 128 strict negatives, AdamW): negatives, edge removal, "
+                                     "forward and backward replayed as one hipGraph (engine.GraphedTrainStep); per-step wall "
+                                     "times, device-synchronised" % B,
+                },
+                "plan_build_ms": plan_build_ms,
+                "eager_ms_per_step": eager_ms,
+                "rspmm_kernel_only": {"kernel": "quad_kernel<FWD,add,mul,unit_w> (entity graph, F = %d: tail and head queries of the batch in one launch)" % Fk,
+                                      "launches_timed": len(kernel_ms), "avg_ms": k_avg_ms,
+                                      "timed": "every launch of the timed region" if graphed is None else
+                                               "%d eager launches of the same kernel/shapes right after the timed region "
+                                               "(event records cannot be captured into the hipGraph with this HIP runtime)" % len(kernel_ms),
+                                      "edges_per_s": E * (Fk // 64) / (k_avg_ms * 1e-3) if kernel_ms else None},
+                "mrr_hip": mrr,
+                "mrr_hip_after_finetune": mrr_tuned,
+                "metrics_hip": metrics,
+                "metrics_hip_after_finetune": metrics_tuned,
+                "mrr_check": mrr_check,
+            })
         result["headline_blocks"] = headline_blocks
         if args.data and world == 1:
             result["real_data"] = real_data_metrics(args.data, args.ckpt, dev, B)
             result["config"]["real_data_mrr"] = result["real_data"]["metrics"].get("mrr")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             und_np = {"dst": und.edge_list[:, 1].cpu().numpy(), "src": und.edge_list[:, 0].cpu().numpy(),
                       "rel": und.edge_list[:, 2].cpu().numpy()}
             result["cpu_baseline"] = cpu_baseline(und_np, n_node, R2, Fk)

@@ -3,7 +3,8 @@
 CPU part: without devices every form exits non-zero and prints no JSON line.  GPU part: a WORLD_SIZE that contradicts
 ``--gpus`` is refused before any GPU work; ``--gpus 2`` without a launcher starts its two ranks itself (they time-share the
 box's GPU over gloo under the development switch ULTRA_BENCH_SHARE_GPU=1) and the line carries ``n_gpus: 2`` and config 4's
-N-rank numbers -- the pretrain_3g-shaped step with the bucketed gradient all-reduce."""
+N-rank numbers (``--full``) -- the pretrain_3g-shaped step with the bucketed gradient all-reduce; a plain one-GPU run times
+its steps, prints the headline only and dumps the same scores in every run."""
 import json
 import os
 import subprocess
@@ -49,8 +50,8 @@ def test_world_size_that_contradicts_gpus_is_refused():
 def test_gpus_2_launches_its_own_ranks_and_times_the_pretraining_step_with_the_reducer():
     share = {} if torch.cuda.device_count() >= 2 else {"ULTRA_BENCH_SHARE_GPU": "1"}
     # (config 5 runs on a graph of 1 / 30 the size here: two ranks share one GPU on this box)
-    run, lines = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--stress-shape", "300000,1500000,40", "--no-cpu-baseline",
-                       "--mrr-queries", "0"], env=dict(share, WORLD_SIZE="", RANK="", LOCAL_RANK=""))
+    run, lines = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--stress-shape", "300000,1500000,40",
+                       "--no-cpu-baseline", "--mrr-queries", "0"], env=dict(share, WORLD_SIZE="", RANK="", LOCAL_RANK=""))
     assert run.returncode == 0 and len(lines) == 1, (run.returncode, run.stdout[-1000:], run.stderr[-3000:])
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["steps"] == 6 and line["scaling"] == "weak" and line["value"] > 0
@@ -72,6 +73,28 @@ def test_gpus_2_launches_its_own_ranks_and_times_the_pretraining_step_with_the_r
     five = [c for c in cfg["configs"] if c["config"] == 5][0]
     assert five["all_ranks"]["n_gpus"] == 2 == cfg["cfg5_n_gpus"] and len(five["all_ranks"]["per_rank_ms_per_triple"]) == 2
     assert cfg["cfg5_triples_per_s_all_ranks"] > 0 and five["predict_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_of_its_steps_and_dumps_the_same_scores_every_run(tmp_path):
+    """A plain run (no ``--full``) prints the headline of exactly ``--steps`` timed steps and nothing of the ``--full`` legs;
+    ``--dump-outputs`` writes the float32 (B, 2, N) scores of the last timed step, identical in a second run."""
+    import numpy as np
+    from ultra_torchdrug_amd.data import SHAPES
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        run, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                          env={"WORLD_SIZE": "", "RANK": "", "LOCAL_RANK": ""}, timeout=600)
+        assert run.returncode == 0 and len(lines) == 1, (run.returncode, run.stdout[-1000:], run.stderr[-3000:])
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["unit"] == "edges aggregated/s"
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert not {"roofline", "cpu_baseline", "composition", "mrr_check"} & set(line) and "configs" not in line["config"]
+        assert os.listdir(out) == ["scores.npy"]
+        dumps.append(np.load(out / "scores.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (16, 2, SHAPES["S-fb15k237"][0]) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_a_phase_that_overruns_still_leaves_the_headline_line_of_rank_0():

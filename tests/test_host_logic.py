@@ -556,6 +556,24 @@ def test_bench_byte_model_is_the_surveys():
     assert abs(bench.bytes_algo(100_000_000, 10_000_000, 1000, 64) / 1e9 - 29.4) < 0.05
 
 
+def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way(tmp_path):
+    """``bench.py --dump-outputs``: float32 .npy files, whole under the byte cap; above it the same seeded sample of sorted,
+    distinct positions of the flattened array in every run, within the cap."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.arange(1000, dtype=torch.float64).reshape(10, 2, 50)
+    bench.dump_outputs(str(tmp_path / "whole"), {"scores": x})
+    whole = np.load(tmp_path / "whole" / "scores.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, x.float().numpy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"scores": x}, cap_bytes=400)
+    a, b = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "b" / "scores.npy")
+    assert a.dtype == np.float32 and 0 < 4 * a.size <= 400 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)                    # the values are the positions here
+
+
 def test_relation_cache_is_per_context_exact_and_dropped_by_training():
     """task.cache_relation_representations on the CPU (the oracle plays every operator): predictions with the cached
     tables equal per-batch recomputation exactly, in each of two graph contexts with different relation vocabularies;
