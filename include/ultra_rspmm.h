@@ -345,6 +345,23 @@ int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd_host, const float 
                                     const float *output, const float *output_grad, float *d_weight,
                                     int64_t n_rel, int64_t F, int sum_op, int mul_op, void *stream);
 
+/*
+ * One layer of the path beam search behind TransferNBFNet.visualize (csrc/beam_search.hip; DESIGN.md "Explaining a
+ * prediction").  Over the coalesced dst-CSR of the graph with inverse edges:
+ *   row_ptr int32 [n_node + 1], src int32 [n_edges]   (rows = destination nodes, edges in coalesced order)
+ *   edge_grad fp32 [n_edges]   this layer's gradient of the score with respect to each coalesced edge weight
+ *   input fp32 [n_node][K]     the previous layer's beam values (-inf: empty beam)
+ * For every row v: the K best kept candidates m = input[u][k] + edge_grad[e] of its in-edges e = (u -> v), u != tail, m
+ * finite, after the per-edge de-duplication of near-equal beams; descending, ties by edge position, then k.  Outputs
+ * (written completely): distance fp32 [n_node][K], back_edge int32 [n_node][K] (position of the chosen edge, -1 for an
+ * empty slot), back_rank int32 [n_node][K] (prev(k): the beam of the source the path continues from, -1 for an empty
+ * slot); empty slots hold -inf.  1 <= K <= 32 (else ULTRA_ERR_BAD_SHAPE).  Row bounds are clamped to [0, n_edges] and
+ * out-of-range sources are skipped.
+ */
+int ultra_beam_search_step_f32(const int32_t *row_ptr, const int32_t *src, const float *edge_grad, const float *input,
+                               int64_t n_node, int64_t n_edges, int64_t tail, int64_t K, float *distance,
+                               int32_t *back_edge, int32_t *back_rank, void *stream);
+
 
 /*
  * Dense epilogue of one Bellman-Ford layer, fused (dim must be 64, the shipped architecture):

@@ -1,0 +1,159 @@
+"""Explaining one prediction (``TransferNBFNet.visualize``) at B = 1 on S-fb15k237 and S-stress (GPU only).
+
+    python tools/explain_bench.py [--workloads S-fb15k237,S-stress] [--reps 3] [--beams 10] [--json PATH]
+
+Per workload: the shipped 6 x 64d entity stack (DistMult, sum, LayerNorm, shortcut, projected relations; seeded random init and
+random relation representations -- the relation stack is not part of an explanation), the graph with inverse edges and its plans
+built first.  Reported:
+  * ``gradient_ms``: the per-layer edge gradients (``edge_gradients``: forward with leaf weights + ``autograd.grad``);
+  * ``search_ms``: the beam search over all layers plus the path assembly (``visualize`` minus the gradient part);
+  * ``peak_extra_bytes``: ``max_memory_allocated`` during one ``visualize`` above the allocation before it, and ``E * 64 * 4``, the
+    size of ONE materialised (E, D) message tensor, beside it;
+  * ``beam_kernel``: the ``ultra_beam_search_step_f32`` launch alone (device events around the C ABI call, median of ``--reps``
+    per layer, on that layer's real inputs) against its byte floor ``E (8 + 4 + 4K) + 4 (N + 1) + 12 N K``.
+Prints one JSON object; a workload that fails records the error instead of a result.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+HBM_PEAK = 8.0e12      # bytes / s (MI355X_MICROARCH.md)
+
+
+def build(workload, dev, seed=1024):
+    from ultra_torchdrug_amd.data import SHAPES, synthetic_kg
+    from ultra_torchdrug_amd.graph import Graph
+    from ultra_torchdrug_amd.model import TransferNBFNet
+    if workload == "S-stress":
+        n_node, n_triple, n_rel = SHAPES["S-stress"]
+        gen = torch.Generator(device=dev).manual_seed(seed)
+        triples = torch.stack([torch.randint(0, n, (n_triple,), device=dev, generator=gen) for n in (n_node, n_node, n_rel)], 1)
+        graph = Graph(triples, None, n_node, n_rel)
+    else:
+        graph = synthetic_kg(workload, device=dev)
+    torch.manual_seed(seed)
+    model = TransferNBFNet(input_dim=64, hidden_dims=[64] * 6, num_relation=graph.num_relation, message_func="distmult",
+                           aggregate_func="sum", short_cut=True, layer_norm=True, project=True, mod=True).to(dev)
+    rel = torch.randn(1, 2 * graph.num_relation, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(seed))
+    return graph, model, rel
+
+
+def kernel_ms(row_ptr, src, grad, beams, tail, reps):
+    from ultra_torchdrug_amd import _lib
+    lib = _lib.load()
+    n, K = beams.shape
+    out = torch.empty_like(beams)
+    be = torch.empty(n, K, dtype=torch.int32, device=beams.device)
+    br = torch.empty_like(be)
+    stream = torch.cuda.current_stream()
+    times = []
+    for _ in range(reps + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        _lib.check(lib.ultra_beam_search_step_f32(row_ptr.data_ptr(), src.data_ptr(), grad.data_ptr(), beams.data_ptr(), n,
+                                                  src.numel(), tail, K, out.data_ptr(), be.data_ptr(), br.data_ptr(),
+                                                  ctypes.c_void_p(stream.cuda_stream)))
+        b.record(stream)
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    times = sorted(times[1:])
+    return times[len(times) // 2], out
+
+
+def run(workload, dev, reps, beams_k):
+    from ultra_torchdrug_amd import functional
+    rec = {"workload": workload, "B": 1, "num_beam": beams_k}
+    t0 = time.perf_counter()
+    graph, model, rel = build(workload, dev)
+    model.num_beam, model.path_topk = beams_k, 10
+    und = model._undirected(graph)
+    csr = und.relcsr
+    _ = csr.csr_arrays, csr.fwd, csr.by_src, csr.by_rel
+    torch.cuda.synchronize()
+    rec["build_s"] = time.perf_counter() - t0
+    n, E = und.num_node, csr.n_edges
+    rec["N"], rec["E"] = n, E
+    h, t, r = (int(x) for x in graph.edge_list[0])
+    rec["triple"] = [h, t, r]
+    model.visualize(graph, [rel], [h], [t], [r])            # warm-up: lazily built indices, code objects
+    torch.cuda.synchronize()
+    grad_ms, total_ms = [], []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        grads = model.edge_gradients(graph, [rel], [h], [t], [r])
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        del grads
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        paths, weights = model.visualize(graph, [rel], [h], [t], [r])
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        peak = torch.cuda.max_memory_allocated() - base
+        grad_ms.append(1e3 * (t1 - t0))
+        total_ms.append(1e3 * (t3 - t2))
+    rec["gradient_ms"] = sorted(grad_ms)[len(grad_ms) // 2]
+    rec["visualize_ms"] = sorted(total_ms)[len(total_ms) // 2]
+    rec["search_ms"] = rec["visualize_ms"] - rec["gradient_ms"]
+    rec["peak_extra_bytes"] = int(peak)
+    rec["one_message_tensor_bytes"] = E * 64 * 4
+    rec["n_paths"] = len(paths)
+    rec["top_path"] = [list(e) for e in paths[0]] if paths else None
+    rec["top_weight"] = weights[0] if weights else None
+    # the beam kernel alone, per layer, on that layer's real inputs
+    grads = model.edge_gradients(graph, [rel], [h], [t], [r])
+    row_ptr, src, _, _ = csr.csr_arrays
+    beams = torch.full((n, beams_k), float("-inf"), device=dev)
+    beams[h, 0] = 0
+    floor = E * (8 + 4 + 4 * beams_k) + 4 * (n + 1) + 12 * n * beams_k
+    layers = []
+    for g in grads:
+        g = g.contiguous()
+        ms, out = kernel_ms(row_ptr, src, g, beams, t, reps)
+        want = functional.beam_search_step(row_ptr, src, g, beams, t)[0]
+        assert torch.equal(out, want)
+        layers.append({"ms": ms, "GB_per_s_of_floor": floor / ms / 1e6, "fraction_of_hbm_peak": floor / (ms * 1e-3) / HBM_PEAK})
+        beams = want
+    rec["beam_kernel"] = {"byte_floor_per_layer": floor, "layers": layers}
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="S-fb15k237,S-stress")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--beams", type=int, default=10)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    import ultra_torchdrug_amd as U
+    U.require_library()
+    if not torch.cuda.is_available():
+        raise SystemExit("explain_bench.py measures on an MI355X; no GPU is visible")
+    dev = torch.device("cuda:0")
+    out = {"device": torch.cuda.get_device_name(0), "results": []}
+    for workload in args.workloads.split(","):
+        try:
+            out["results"].append(run(workload, dev, args.reps, args.beams))
+        except Exception as err:            # (out of memory on a smaller device, ...): recorded, not hidden
+            out["results"].append({"workload": workload, "error": "%s: %s" % (type(err).__name__, err)})
+        torch.cuda.empty_cache()
+        print(json.dumps(out["results"][-1]), file=sys.stderr, flush=True)
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

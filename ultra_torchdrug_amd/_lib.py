@@ -78,6 +78,7 @@ EXPORTS = (
     "ultra_rspmm_backward_f32",
     "ultra_rspmm_backward_accumulate_f32",
     "ultra_rspmm_backward_weight_f32",
+    "ultra_beam_search_step_f32",
     "ultra_rspmm_backward_active_f32",
     "ultra_node_bitmap",
     "ultra_rspmm_drelation_boundary_f32",
@@ -225,6 +226,8 @@ def load():
     lib.ultra_rspmm_drelation_boundary_f32.argtypes = [seg, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, vp]
     lib.ultra_rspmm_backward_weight_f32.restype = i32
     lib.ultra_rspmm_backward_weight_f32.argtypes = [seg, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+    lib.ultra_beam_search_step_f32.restype = i32
+    lib.ultra_beam_search_step_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]
     lib.ultra_combine_forward_f32.restype = i32
     lib.ultra_combine_forward_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, i64, i64, vp]
     lib.ultra_combine_forward_boundary_f32.restype = i32

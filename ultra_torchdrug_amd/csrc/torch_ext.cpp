@@ -21,6 +21,8 @@
 //   ultra_mi::rspmm_fwd(row_ptr, src, rel, w?, relation, input, sum_op, mul_op) -> Tensor          (differentiable)
 //   ultra_mi::rspmm_bwd(row_ptr, src, rel, w?, relation, input, output, output_grad, sum_op, mul_op)
 //       -> (d_relation, d_input)
+//   ultra_mi::beam_search_step(row_ptr, src, edge_grad, input, tail) -> (distance, back_edge, back_rank)
+//       one layer of the path beam search of TransferNBFNet.visualize (CUDA and CPU keys)
 //   plan-based forms used by ultra_torchdrug_amd.functional (the plan = the bytes of one `ultra_segments` struct in a
 //   CPU uint8 tensor; the device arrays it points to are owned by the Python RelCSR object):
 //   ultra_mi::rspmm_plan_fwd(plan, relation, input, add_rows?, boundary_node?, boundary_value?, n_src, sum_op, mul_op) -> Tensor
@@ -33,7 +35,10 @@
 #include <torch/autograd.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cfloat>
+#include <cmath>
+#include <limits>
 #include <cstring>
 #include <tuple>
 #include <vector>
@@ -669,6 +674,132 @@ std::tuple<Tensor, Tensor> rspmm_bwd_cpu(const Tensor &row_ptr, const Tensor &sr
     return {d_relation, d_input};
 }
 
+// ------------------------------------------------------------------------------------------------ beam_search_step
+// One layer of the path beam search of TransferNBFNet.visualize (include/ultra_rspmm.h, ultra_beam_search_step_f32; DESIGN.md
+// "Explaining a prediction").  The CPU kernel below is the same definition as csrc/beam_search.hip, bit for bit: the same f32
+// add per candidate, the same near-equality test (no fused multiply-add: -ffp-contract=off), the same total order.
+struct BeamArgs {
+    int64_t n_node, n_edges, K;
+};
+
+BeamArgs check_beam(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad, const Tensor &input, int64_t tail) {
+    TORCH_CHECK(input.dim() == 2, "ultra_mi::beam_search_step: input must be (N, K), got ", input.sizes());
+    const int64_t K = input.size(1);
+    TORCH_CHECK_VALUE(K >= 1 && K <= 32, "ultra_mi::beam_search_step: the number of beams must lie in [1, 32], got ", K);
+    TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.numel() == input.size(0) + 1 && src.dim() == 1 && edge_grad.dim() == 1 &&
+                    edge_grad.numel() == src.numel(),
+                "ultra_mi::beam_search_step: row_ptr (N + 1,), src (E,), edge_grad (E,), input (N, K) expected");
+    TORCH_CHECK(row_ptr.scalar_type() == at::kInt && src.scalar_type() == at::kInt, "ultra_mi::beam_search_step: int32 row_ptr / src");
+    TORCH_CHECK(edge_grad.scalar_type() == at::kFloat && input.scalar_type() == at::kFloat,
+                "ultra_mi::beam_search_step: fp32 edge_grad / input");
+    for (const Tensor *t : {&row_ptr, &src, &edge_grad})
+        TORCH_CHECK(t->device() == input.device(), "ultra_mi::beam_search_step: all tensors must share a device");
+    const int64_t n_node = input.size(0), n_edges = src.numel();
+    TORCH_CHECK(n_node < INT32_MAX && n_edges < INT32_MAX, "ultra_mi::beam_search_step: graph too large for int32 indices");
+    TORCH_CHECK(tail >= 0 && tail < n_node, "ultra_mi::beam_search_step: tail ", tail, " outside [0, ", n_node, ")");
+    // the CSR is checked here (one reduction, one host read on the device), so that a malformed one raises on both keys
+    if (n_node > 0) {
+        const Tensor rp = row_ptr.to(at::kLong);
+        bool bad = rp[0].item<int64_t>() != 0 || rp[n_node].item<int64_t>() != n_edges;
+        if (!bad) {
+            Tensor flags = (rp.narrow(0, 1, n_node) < rp.narrow(0, 0, n_node)).any();
+            if (n_edges > 0) flags = flags | (src < 0).any() | (src >= n_node).any();
+            bad = flags.item<bool>();
+        }
+        TORCH_CHECK(!bad, "ultra_mi::beam_search_step: malformed CSR (row_ptr must run from 0 to E without decreasing, src must "
+                    "lie in [0, N))");
+    }
+    return {n_node, n_edges, K};
+}
+
+inline bool beam_near_equal(float a, float b) {
+    if (a == b) return true;
+    const float d = std::fabs(a - b);
+    const float tol = 1e-8f + 1e-5f * std::fabs(b);
+    return d <= tol;
+}
+
+std::tuple<Tensor, Tensor, Tensor> beam_search_step_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
+                                                        const Tensor &input, int64_t tail) {
+    for (const Tensor *t : {&row_ptr, &src, &edge_grad, &input})
+        TORCH_CHECK(t->device().is_cpu(), "ultra_mi (CPU): beam_search_step: all tensors must share a device");
+    const BeamArgs a = check_beam(row_ptr, src, edge_grad, input, tail);
+    const int64_t N = a.n_node, K = a.K;
+    Tensor distance = at::empty({N, K}, input.options());
+    Tensor back_edge = at::empty({N, K}, row_ptr.options()), back_rank = at::empty({N, K}, row_ptr.options());
+    if (N == 0) return {distance, back_edge, back_rank};
+    const Tensor rp_t = row_ptr.contiguous(), s_t = src.contiguous(), g_t = edge_grad.contiguous(), x_t = input.contiguous();
+    const int *rp = rp_t.data_ptr<int>(), *sp = s_t.data_ptr<int>();
+    const float *gp = g_t.data_ptr<float>(), *xp = x_t.data_ptr<float>();
+    float *dp = distance.data_ptr<float>();
+    int *bep = back_edge.data_ptr<int>(), *brp = back_rank.data_ptr<int>();
+    at::parallel_for(0, N, 64, [&](int64_t v0, int64_t v1) {
+        struct Cand { float v; int64_t e; int k, prev; };
+        std::vector<Cand> kept;
+        float m[32];
+        bool cand[32];
+        for (int64_t v = v0; v < v1; ++v) {
+            kept.clear();
+            for (int64_t e = rp[v]; e < rp[v + 1]; ++e) {
+                const int u = sp[e];
+                if (u == tail) continue;
+                const float ge = gp[e];
+                for (int64_t k = 0; k < K; ++k) {
+                    m[k] = xp[(int64_t)u * K + k] + ge;
+                    cand[k] = std::isfinite(m[k]);
+                }
+                bool last_cand = false;
+                int last_prev = -1;
+                for (int k = 0; k < (int)K; ++k) {
+                    if (!cand[k]) { last_cand = false; continue; }
+                    int p = k;
+                    for (int j = 0; j < k; ++j)
+                        if (cand[j] && beam_near_equal(m[k], m[j])) { p = j; break; }
+                    if (!(last_cand && p == last_prev)) kept.push_back({m[k], e, k, p});
+                    last_cand = true;
+                    last_prev = p;
+                }
+            }
+            // value descending, then edge position, then k (a total order: (e, k) pairs are distinct)
+            const size_t take = std::min<size_t>((size_t)K, kept.size());
+            std::partial_sort(kept.begin(), kept.begin() + take, kept.end(), [](const Cand &x, const Cand &y) {
+                return x.v > y.v || (x.v == y.v && (x.e < y.e || (x.e == y.e && x.k < y.k)));
+            });
+            for (int64_t r = 0; r < K; ++r) {
+                const int64_t o = v * K + r;
+                if ((size_t)r < take) {
+                    dp[o] = kept[r].v;
+                    bep[o] = (int)kept[r].e;
+                    brp[o] = kept[r].prev;
+                } else {
+                    dp[o] = -std::numeric_limits<float>::infinity();
+                    bep[o] = -1;
+                    brp[o] = -1;
+                }
+            }
+        }
+    });
+    return {distance, back_edge, back_rank};
+}
+
+std::tuple<Tensor, Tensor, Tensor> beam_search_step_hip(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
+                                                        const Tensor &input, int64_t tail) {
+    check_dense(input, "input", at::kFloat, input);
+    const BeamArgs a = check_beam(row_ptr, src, edge_grad, input, tail);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    const int64_t N = a.n_node, K = a.K;
+    Tensor distance = at::empty({N, K}, input.options());
+    Tensor back_edge = at::empty({N, K}, row_ptr.options()), back_rank = at::empty({N, K}, row_ptr.options());
+    if (N == 0) return {distance, back_edge, back_rank};
+    const Tensor rp = row_ptr.contiguous(), s = src.contiguous(), g = edge_grad.contiguous(), x = input.contiguous();
+    check_status(ultra_beam_search_step_f32(rp.data_ptr<int>(), a.n_edges ? s.data_ptr<int>() : nullptr,
+                                            a.n_edges ? g.data_ptr<float>() : nullptr, x.data_ptr<float>(), N, a.n_edges, tail,
+                                            K, distance.data_ptr<float>(), back_edge.data_ptr<int>(),
+                                            back_rank.data_ptr<int>(), current_stream(input)),
+                 "ultra_beam_search_step_f32");
+    return {distance, back_edge, back_rank};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
@@ -680,6 +811,7 @@ TORCH_LIBRARY(ultra_mi, m) {
           "Tensor? boundary_value, int n_src, int sum_op, int mul_op) -> Tensor");
     m.def("rspmm_plan_bwd(Tensor? by_src, Tensor? by_rel, Tensor relation, Tensor input, Tensor? output, Tensor output_grad, "
           "Tensor(a!)? d_input, bool accumulate, int n_src, int n_dst, int sum_op, int mul_op) -> Tensor");
+    m.def("beam_search_step(Tensor row_ptr, Tensor src, Tensor edge_grad, Tensor input, int tail) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int", []() -> int64_t { return ultra_rspmm_abi_version(); });
 }
 
@@ -688,6 +820,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("build_relcsr", build_relcsr);
     m.impl("rspmm_fwd", rspmm_fwd_hip);
     m.impl("rspmm_bwd", rspmm_bwd_hip);
+    m.impl("beam_search_step", beam_search_step_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)
@@ -695,6 +828,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CPU, m) {
     m.impl("build_relcsr", build_relcsr_cpu);
     m.impl("rspmm_fwd", rspmm_fwd_cpu);
     m.impl("rspmm_bwd", rspmm_bwd_cpu);
+    m.impl("beam_search_step", beam_search_step_cpu);
 }
 
 // the plan tensor lives on the CPU while the dense operands live on the device: no single backend key fits

@@ -1262,10 +1262,14 @@ class _RSPMMFunction(torch.autograd.Function):
     """Counterpart of torchdrug's ``RSPMM{Add,Min,Max}{Mul,Add}Function`` autograd classes."""
 
     @staticmethod
-    def forward(ctx, sparse, relation, input, csr, sum, mul, add_rows=None, b_node=None, b_value=None):
+    def forward(ctx, sparse, relation, input, csr, sum, mul, add_rows=None, b_node=None, b_value=None, edge_weight=None):
         # add_rows (sum only): `update + boundary` of layer.py:156,358 inside the kernel; its gradient is grad_out.
         # (b_node, b_value): the same boundary in sparse form -- the gradient of b_value[b] is row b_node[b] of
         # query block b of grad_out (what scatter_add_'s backward would gather from the dense gradient)
+        # edge_weight: fp32 (csr.n_edges,) weights of the COALESCED edges (forward-plan order) that replace csr's own; its
+        # gradient is rspmm_backward_weight's d_w (TransferNBFNet.visualize: per-layer edge gradients without an (E, F) tensor)
+        if edge_weight is not None:
+            csr = csr.with_coalesced_weights(edge_weight.detach())
         boundary = None if b_node is None else (b_node, b_value.detach())
         out = rspmm_forward(csr, relation, input, sum, mul, add_rows=add_rows, boundary=boundary)
         ctx.has_add_rows = add_rows is not None
@@ -1295,7 +1299,10 @@ class _RSPMMFunction(torch.autograd.Function):
             n_query = ctx.b_node.shape[0]
             blocks = output_grad.view(output_grad.shape[0], n_query, -1)
             d_value = blocks[ctx.b_node.long(), torch.arange(n_query, device=output_grad.device)]
-        return d_sparse, d_relation, d_input, None, None, None, d_add, None, d_value
+        d_edge = None
+        if len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]:
+            d_edge = rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul)
+        return d_sparse, d_relation, d_input, None, None, None, d_add, None, d_value, d_edge
 
 
 # Training, first layer (the caller's `input_is_boundary` promise): the edge gradient of `input` only at the boundary rows
@@ -1504,17 +1511,30 @@ def sum_layer(csr, relation, input, boundary_dense, boundary_sparse, mul, weight
                                    ln_eps, relu, shortcut, input_is_boundary, grad_tiles, grad_rows)
 
 
-def rspmm_sum_plus(sparse, relation, input, add_rows, mul="mul", boundary=None):
+def _check_edge_weight(csr, sparse_leaf, edge_weight, input):
+    if edge_weight is None:
+        return
+    if sparse_leaf is not None:
+        raise RuntimeError("give the edge weights either as the values of a sparse tensor that requires grad or as "
+                           "edge_weight, not both")
+    if (edge_weight.dtype != torch.float32 or tuple(edge_weight.shape) != (csr.n_edges,)
+            or edge_weight.device != input.device):
+        raise RuntimeError("edge_weight must be fp32 (%d,) -- one weight per coalesced edge -- on %s, got %s %s on %s"
+                           % (csr.n_edges, input.device, edge_weight.dtype, tuple(edge_weight.shape), edge_weight.device))
+
+
+def rspmm_sum_plus(sparse, relation, input, add_rows, mul="mul", boundary=None, edge_weight=None):
     """``generalized_rspmm(..., sum="add") + add_rows`` with the addition inside the kernel (differentiable).
     ``boundary = (node, value)`` instead of ``add_rows``: the boundary in sparse form (see :func:`rspmm_forward`),
-    differentiable in ``value``."""
+    differentiable in ``value``.  ``edge_weight``: see :func:`generalized_rspmm`."""
     csr, sparse_leaf = _as_relcsr(sparse)
     _check_dense(csr, relation, input)
+    _check_edge_weight(csr, sparse_leaf, edge_weight, input)
     if boundary is not None:
         if add_rows is not None:
             raise RuntimeError("give the boundary either dense (add_rows) or sparse (boundary), not both")
-        return _RSPMMFunction.apply(sparse_leaf, relation, input, csr, "add", mul, None, boundary[0], boundary[1])
-    return _RSPMMFunction.apply(sparse_leaf, relation, input, csr, "add", mul, add_rows)
+        return _RSPMMFunction.apply(sparse_leaf, relation, input, csr, "add", mul, None, boundary[0], boundary[1], edge_weight)
+    return _RSPMMFunction.apply(sparse_leaf, relation, input, csr, "add", mul, add_rows, None, None, edge_weight)
 
 
 def _rspmm_host(csr, relation, input, sum_op, mul_op):
@@ -1524,7 +1544,7 @@ def _rspmm_host(csr, relation, input, sum_op, mul_op):
     return _torch_ext.load().rspmm_fwd(row_ptr, src, rel, w, relation, input, sum_op, mul_op)
 
 
-def generalized_rspmm(sparse, relation, input, sum="add", mul="mul"):
+def generalized_rspmm(sparse, relation, input, sum="add", mul="mul", edge_weight=None):
     r"""Generalized relational sparse-dense product (drop-in for torchdrug's function of the same name).
 
     .. math::  out_{v,:} = \bigoplus_{(v, u, r) \in sparse} w_{vur} \cdot (relation_{r,:} \otimes input_{u,:})
@@ -1534,6 +1554,9 @@ def generalized_rspmm(sparse, relation, input, sum="add", mul="mul"):
     Parameters: ``sparse`` -- 3-D sparse COO tensor ``(N_dst, N_src, R)`` (any order, duplicates are merged by
     summing their values, as ``coalesce()`` does) or a :class:`RelCSR`; ``relation`` -- ``(R, F)`` fp32;
     ``input`` -- ``(N_src, F)`` fp32 (a 1-D ``input`` is treated as ``(N_src, 1)``).  Returns ``(N_dst, F)``.
+    ``edge_weight`` (MI355X only; an extension): fp32 ``(n_edges,)`` weights of the COALESCED edges in forward-plan order
+    (``RelCSR.dst / src / rel_id``) used instead of the adjacency's own; differentiable -- its gradient is
+    :func:`rspmm_backward_weight` (duplicate triples of a COO input share one coalesced edge, ``RelCSR.edge_of_input``).
     """
     _ops(sum, mul)
     csr, sparse_leaf = _as_relcsr(sparse)
@@ -1543,11 +1566,30 @@ def generalized_rspmm(sparse, relation, input, sum="add", mul="mul"):
         if relation.dim() == 1:
             relation = relation.unsqueeze(-1)
     _check_dense(csr, relation, input, require_hip=False)
+    _check_edge_weight(csr, sparse_leaf, edge_weight, input)
     if not input.is_cuda:
+        if edge_weight is not None:
+            raise RuntimeError("generalized_rspmm: edge_weight runs on an MI355X (HIP) device only")
         if sparse_leaf is not None:
             raise RuntimeError("generalized_rspmm on CPU tensors has no gradient for the sparse values "
                                "(the reference takes its scatter path then, ultra/layer.py:299)")
         out = _rspmm_host(csr, relation, input, *_ops(sum, mul))
     else:
-        out = _RSPMMFunction.apply(sparse_leaf, relation, input, csr, sum, mul)
+        out = _RSPMMFunction.apply(sparse_leaf, relation, input, csr, sum, mul, None, None, None, edge_weight)
     return out.squeeze(-1) if squeeze else out
+
+
+BEAM_MAX = 32        # beams per node the beam-search step takes (csrc/beam_search.hip: register top-K of at most 32)
+
+
+def beam_search_step(row_ptr, src, edge_grad, input, tail):
+    """One layer of the path beam search of :meth:`TransferNBFNet.visualize` (``torch.ops.ultra_mi.beam_search_step``: the
+    HIP kernel of ``csrc/beam_search.hip`` for device tensors, its CPU twin for host tensors -- same bits).
+
+    ``row_ptr`` int32 ``(N + 1,)`` / ``src`` int32 ``(E,)``: the coalesced dst-CSR (:attr:`RelCSR.csr_arrays`); ``edge_grad``
+    fp32 ``(E,)``: this layer's edge gradients in the same order; ``input`` fp32 ``(N, K)``: the previous layer's beams
+    (``-inf`` = empty); ``tail``: the explained triple's tail, whose out-edges are masked.  Returns ``(distance fp32 (N, K),
+    back_edge int32 (N, K), back_rank int32 (N, K))`` -- semantics in DESIGN.md ("Explaining a prediction")."""
+    if input.dim() != 2 or not 1 <= input.shape[1] <= BEAM_MAX:
+        raise ValueError("beam_search_step: input must be (N, K) with 1 <= K <= %d, got %s" % (BEAM_MAX, tuple(input.shape)))
+    return _torch_ext.load().beam_search_step(row_ptr, src, edge_grad, input, int(tail))

@@ -166,6 +166,8 @@ class _RelationalConvBase(nn.Module):
         produced by one kernel sequence without an add pass.  ``None``: not applicable, take the general path."""
         if graph.requires_grad or self.message_func not in self.message2mul or self.aggregate_func != "sum":
             return None
+        if getattr(graph, "native_edge_weight", None) is not None:     # the fused layer has no edge-weight gradient
+            return None
         if not self._fusable(input, input) or not torch.is_grad_enabled():
             return None
         ops = backend.get()
@@ -183,6 +185,13 @@ class _RelationalConvBase(nn.Module):
                              ln.weight if ln else None, ln.bias if ln else None, ln.eps if ln else 1e-5,
                              relu=self.activation is F.relu, shortcut=shortcut, input_is_boundary=input_is_boundary,
                              grad_tiles=grad_tiles, grad_rows=grad_rows)
+
+    def native_edge_grad(self):
+        """Whether ``bellmanford(separate_grad="native")`` gives this layer a leaf weight per COALESCED edge on the rspmm route
+        (``functional.generalized_rspmm(edge_weight=...)``): summed or max-aggregated DistMult / TransE messages.  ``mean`` and
+        ``pna`` (their degree scaling reads the edge list) and ``rotate`` keep the materialised message route."""
+        kind = self.aggregate_func[:-len("_nobound")] if self.aggregate_func.endswith("_nobound") else self.aggregate_func
+        return kind in ("sum", "max") and self.message_func in self.message2mul
 
     def _no_grad(self, *tensors):
         return not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors if t is not None)
@@ -274,6 +283,9 @@ class _RelationalConvBase(nn.Module):
         kind = func[:-len("_nobound")] if not bound else func
         ops = backend.get()
         rspmm = ops.generalized_rspmm
+        # bellmanford(separate_grad="native"): this layer's own leaf weight per coalesced edge (no fused / sparse shortcut)
+        edge_weight = getattr(graph, "native_edge_weight", None)
+        ew = {} if edge_weight is None else dict(edge_weight=edge_weight)
 
         if kind not in ("sum", "mean", "max", "pna"):
             raise ValueError("Unknown aggregation function `%s`" % self.aggregate_func)
@@ -281,7 +293,7 @@ class _RelationalConvBase(nn.Module):
         if kind in ("mean", "pna"):
             degree_out = graph.degree_out.unsqueeze(-1) + 1
         # inference: `update + boundary` / `max(update, boundary)` ride along in the rspmm kernel (bit-identical)
-        fuse_bound = bound and ops.accepts(input) and self._no_grad(input, relation_input, boundary)
+        fuse_bound = bound and ops.accepts(input) and edge_weight is None and self._no_grad(input, relation_input, boundary)
         # the boundary in its sparse form (node per query, value per query), when the caller attached it
         sparse_bound = getattr(graph, "boundary_sparse", None) if fuse_bound else None
         bound_args = dict(add_rows=boundary) if sparse_bound is None else dict(boundary=sparse_bound)
@@ -296,11 +308,11 @@ class _RelationalConvBase(nn.Module):
             elif bound and ops.accepts(input):      # training
                 sparse_train = getattr(graph, "boundary_sparse", None)
                 if sparse_train is not None:
-                    update = ops.rspmm_sum_plus(adjacency, relation_input, input, None, mul=mul, boundary=sparse_train)
+                    update = ops.rspmm_sum_plus(adjacency, relation_input, input, None, mul=mul, boundary=sparse_train, **ew)
                 else:
-                    update = ops.rspmm_sum_plus(adjacency, relation_input, input, boundary, mul=mul)
+                    update = ops.rspmm_sum_plus(adjacency, relation_input, input, boundary, mul=mul, **ew)
             else:
-                update = rspmm(adjacency, relation_input, input, sum="add", mul=mul)
+                update = rspmm(adjacency, relation_input, input, sum="add", mul=mul, **ew)
                 if bound:
                     update = update + boundary
             if kind == "mean":
@@ -309,7 +321,7 @@ class _RelationalConvBase(nn.Module):
             if fuse_bound:
                 update = ops.rspmm_forward(adjacency, relation_input, input, "max", mul, **bound_args)
             else:
-                update = rspmm(adjacency, relation_input, input, sum="max", mul=mul)
+                update = rspmm(adjacency, relation_input, input, sum="max", mul=mul, **ew)
                 if bound:
                     update = torch.max(update, boundary)
         else:

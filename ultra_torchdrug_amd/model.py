@@ -116,7 +116,10 @@ class TransferNBFNet(nn.Module):
     def bellmanford(self, graph, h_index, r_index, separate_grad=False, want_feature=True, grad_candidates=None):
         """model.py:101-143.  Returns ``node_feature`` of shape ``(num_node, batch, feature_dim)``; with
         ``want_feature=False`` only its two parts (``hidden``: last layer output, ``query``) -- the fused score
-        kernel reads them directly and the ``cat`` of model.py:134-138 is never materialised."""
+        kernel reads them directly and the ``cat`` of model.py:134-138 is never materialised.
+        ``separate_grad=True``: every layer on its own clone of the graph with the materialised message route (model.py:120).
+        ``separate_grad="native"``: every layer gets its own leaf edge-weight tensor, ``step_graph.edge_grad_leaf``
+        (:meth:`_edge_grad_graph`), for :meth:`visualize`."""
         bs = h_index.shape[0]
         if self.query.dim() == 2:
             query = self.query[r_index]
@@ -167,7 +170,9 @@ class TransferNBFNet(nn.Module):
             if cut is not None and position == cut and self.record_cuts:
                 self.last_cuts = ([layer_input] + [late_graph.relation_tables[id(c)] for c in list(self.layers)[cut:]]
                                   + [query_late])
-            if separate_grad:
+            if separate_grad == "native":
+                step_graph = self._edge_grad_graph(graph, conv, query, boundary)
+            elif separate_grad:
                 step_graph = graph.clone()
                 step_graph.query, step_graph.boundary = query, boundary
                 step_graph.requires_grad = True
@@ -189,6 +194,160 @@ class TransferNBFNet(nn.Module):
         else:
             output = torch.cat([hiddens[-1], node_query], dim=-1)
         return {"node_feature": output, "step_graphs": step_graphs}
+
+    @staticmethod
+    def _edge_grad_graph(graph, conv, query, boundary):
+        """The step graph of one layer under ``bellmanford(separate_grad="native")``.  On the device, for the layers that
+        have it (``conv.native_edge_grad()``: sum / max of DistMult / TransE messages), a shallow copy of ``graph`` whose
+        ``native_edge_weight`` -- a leaf copy of the COALESCED weights of ``graph.relcsr`` -- the layer hands to the rspmm
+        (``functional.generalized_rspmm(edge_weight=...)``): the non-fused epilogue, no fused layer, no sparse first-layer or
+        dense shortcut, no ``(E, D)`` message tensor.  Otherwise (``mean``, ``pna``, ``rotate``; CPU tensors) a clone on the
+        materialised message route (layer.py ``message`` / ``aggregate``) whose ``edge_weight`` is a leaf, one entry per
+        ORIGINAL edge.  ``edge_grad_leaf`` names the leaf, ``edge_grad_coalesced`` its order."""
+        if conv.native_edge_grad() and backend.get().accepts(boundary):
+            import copy
+            step = copy.copy(graph)
+            step.native_edge_weight = graph.relcsr.weight.detach().clone().requires_grad_()
+            step.edge_grad_leaf, step.edge_grad_coalesced = step.native_edge_weight, True
+            return step
+        step = graph.clone()
+        step.query, step.boundary = query, boundary
+        step.edge_weight = graph.edge_weight.detach().to(boundary.dtype).clone().requires_grad_()
+        step.requires_grad = True
+        step.edge_grad_leaf, step.edge_grad_coalesced = step.edge_weight, False
+        return step
+
+    def visualize(self, graph, rel_query_list, h_index, t_index, r_index):
+        """Why does the model score ``t`` for the query ``(h, r, ?)``?  ``/root/reference/ultra/model.py:394-492``: the score of
+        ONE triple is differentiated with respect to every layer's edge weights (:meth:`edge_gradients`), a beam search of
+        ``num_beam`` beams per node (``functional.beam_search_step``, one HIP launch per layer) finds the paths
+        ``h -> ... -> t`` with the largest sums of per-hop edge gradients, and the ``path_topk`` best by sum / length are
+        returned.
+
+        ``graph``: the fact graph (the inverse edges are added, memoised as in :meth:`forward`); ``rel_query_list``: the
+        relation representations as :meth:`forward` takes them; ``h_index`` / ``t_index`` / ``r_index``: one triple, ``r`` in
+        ``[0, 2R)`` of the graph with inverse edges (a head-side explanation passes ``(t, r + R, h)``).  Returns ``(paths,
+        weights)``: tuples, sorted as the reference sorts them (by weight, then by path, descending); a path is a list of
+        ``(h, t, r)`` edges of the graph with inverse edges from ``h`` to ``t``; both empty when no path reaches ``t``.
+        Gradients are taken with respect to the edge weights alone: no parameter's ``.grad`` changes, nor the module's mode.
+        DESIGN.md "Explaining a prediction" has the search's exact semantics."""
+        from . import functional
+        num_beam = int(self.num_beam)
+        if not 1 <= num_beam <= functional.BEAM_MAX:
+            raise ValueError("visualize: num_beam must lie in [1, %d], got %d" % (functional.BEAM_MAX, num_beam))
+        edge_grads, (h, t, _) = self.edge_gradients(graph, rel_query_list, h_index, t_index, r_index, with_ids=True)
+        graph = self._undirected(graph)
+        csr = graph.relcsr
+        row_ptr, src, _, _ = csr.csr_arrays
+        with torch.no_grad():
+            beams = torch.full((graph.num_node, num_beam), float("-inf"), device=self.device)
+            beams[h, 0] = 0
+            steps = []
+            for g in edge_grads:
+                beams, back_edge, back_rank = functional.beam_search_step(row_ptr, src, g.to(torch.float32).contiguous(), beams, t)
+                steps.append((beams[t], back_edge, back_rank))
+            return self._assemble_paths(csr, steps, t, int(self.path_topk))
+
+    def edge_gradients(self, graph, rel_query_list, h_index, t_index, r_index, with_ids=False):
+        """The gradient of the score of ONE triple with respect to every layer's edge weights (model.py:394-409), one tensor
+        per layer, one entry per COALESCED edge of ``graph``'s graph with inverse edges (``relcsr`` order: ``dst`` / ``src`` /
+        ``rel_id``).  ``bellmanford(separate_grad="native")``: on the device the sum / max layers of DistMult / TransE messages
+        take the rspmm route with a leaf weight vector per layer (no ``(E, D)`` message tensor); the other layers, and CPU
+        tensors, the materialised message route.  Only the edge-weight leaves are differentiated (``torch.autograd.grad``):
+        parameters' ``.grad`` stay as they are.  ``with_ids``: also return the host ids ``(h, t, r)``."""
+        dev = self.device
+        h_index, t_index, r_index = (torch.as_tensor(x, device=dev).reshape(-1).long() for x in (h_index, t_index, r_index))
+        if h_index.numel() != 1 or t_index.numel() != 1 or r_index.numel() != 1:
+            raise ValueError("visualize explains one triple: got %d heads, %d tails, %d relations"
+                             % (h_index.numel(), t_index.numel(), r_index.numel()))
+        if not graph.num_relation:
+            raise ValueError("visualize needs a relational graph")
+        h, t, r = torch.cat([h_index, t_index, r_index]).tolist()      # (the reference reads them on the host too)
+        if not (0 <= h < graph.num_node and 0 <= t < graph.num_node and 0 <= r < 2 * graph.num_relation):
+            raise IndexError("visualize: h, t must lie in [0, %d) and r in [0, %d): got (%d, %d, %d)"
+                             % (graph.num_node, 2 * graph.num_relation, h, t, r))
+        self.query = rel_query_list[0]
+        if len(rel_query_list) > 1:
+            assert len(rel_query_list) == len(self.layers) + 1
+            for i, conv in enumerate(self.layers):
+                conv.relation = rel_query_list[i + 1]
+        else:
+            for conv in self.layers:
+                conv.relation = rel_query_list[0]
+        graph = self._undirected(graph)
+
+        with torch.enable_grad():
+            output = self.bellmanford(graph, h_index, r_index, separate_grad="native", want_feature=self.concat_hidden)
+            if self.concat_hidden:
+                feature = output["node_feature"][t, 0]
+            else:
+                feature = torch.cat([output["hidden"][t, 0], output["query"][0]], dim=-1)
+            score = self.mlp(feature).squeeze(-1)
+            step_graphs = output["step_graphs"]
+            leaves = [g.edge_grad_leaf for g in step_graphs]
+            grads = torch.autograd.grad(score, leaves, allow_unused=True)
+        del output, feature, score
+        csr = graph.relcsr
+        edge_grads = []
+        for g, step, leaf in zip(grads, step_graphs, leaves):
+            g = torch.zeros_like(leaf) if g is None else g.detach()
+            edge_grads.append(g if step.edge_grad_coalesced else self._coalesced_edge_grad(csr, g))
+        return (edge_grads, (h, t, r)) if with_ids else edge_grads
+
+    @staticmethod
+    def _coalesced_edge_grad(csr, grad):
+        """Per-ORIGINAL-edge gradients (materialised route) -> one per coalesced edge: that of the edge's first original copy
+        (the copies of a duplicated triple carry the same gradient for summed messages; the native route's coalesced weight is
+        their sum, whose gradient is that same value)."""
+        n_in = grad.shape[0]
+        first = torch.full((csr.n_edges,), n_in, dtype=torch.long, device=grad.device)
+        first.scatter_reduce_(0, csr.edge_of_input, torch.arange(n_in, device=grad.device), reduce="amin")
+        return grad[first].contiguous()
+
+    @staticmethod
+    def _assemble_paths(csr, steps, t, topk):
+        """``topk_average_length`` (model.py:472-492) on the device: for every layer ``i`` the (at most ``topk``) best beams of
+        row ``t`` are followed back through the layers' ``back_edge`` / ``back_rank`` -- ``K`` chains per layer, ``i`` gathers
+        each -- and their ``(h, t, r)`` edges, values and lengths leave in one small copy; only the final sort of at most
+        ``L * topk`` paths runs on the host."""
+        src, dst, rel = csr.src, csr.dst, csr.rel_id
+        n_layer = len(steps)
+        if n_layer == 0 or topk <= 0:
+            return (), ()
+        K = steps[0][0].shape[0]
+        take = min(topk, K)
+        dev = src.device
+        hops = torch.full((n_layer, take, n_layer), -1, dtype=torch.long, device=dev)     # edge positions, hop order
+        values = torch.stack([s[0][:take] for s in steps])                                  # (L, take), descending
+        for i, (_, back_edge, back_rank) in enumerate(steps):
+            e = back_edge[t, :take].long()
+            p = back_rank[t, :take].long()
+            hops[i, :, i] = e
+            for j in range(i - 1, -1, -1):
+                node = src[e.clamp(min=0)]
+                p_safe = p.clamp(min=0)
+                e = steps[j][1][node, p_safe].long()
+                p = steps[j][2][node, p_safe].long()
+                hops[i, :, j] = e
+        safe = hops.clamp(min=0)
+        triples = torch.stack([src[safe], dst[safe], rel[safe]], dim=-1)                  # (L, take, L, 3)
+        # the one device-to-host copy: the values' f64 bits travel beside the int64 edge ids
+        packed = torch.cat([values.double().view(torch.int64).flatten(), triples.flatten()]).cpu()
+        n_val = n_layer * take
+        values = packed[:n_val].view(torch.float64).view(n_layer, take).tolist()
+        triples = packed[n_val:].view(n_layer, take, n_layer, 3).tolist()
+        weights, paths = [], []
+        for i in range(n_layer):
+            for k in range(take):
+                d = values[i][k]
+                if d == float("-inf"):
+                    break
+                paths.append([tuple(x) for x in triples[i][k][:i + 1]])
+                weights.append(d / (i + 1))
+        if not paths:
+            return (), ()
+        weights, paths = zip(*sorted(zip(weights, paths), reverse=True)[:topk])
+        return paths, weights
 
     def _relation_tables(self, batch_size):
         """On the GPU with per-query relation representations and the shipped 64 -> 64 -> 64 projections: the

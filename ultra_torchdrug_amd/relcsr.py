@@ -652,14 +652,21 @@ class RelCSR:
     def with_edge_weights(self, edge_weight):
         """RelCSR over the same edge set with other weights, given per ORIGINAL (un-coalesced) edge; duplicates of
         one triple add up, as ``coalesce()`` would.  Shares the sorted index arrays and chunk schedules."""
+        w = torch.zeros(self.n_edges, dtype=torch.float32, device=self.device)
+        w.index_add_(0, self.edge_of_input, edge_weight.to(torch.float32))
+        return self.with_coalesced_weights(w)
+
+    def with_coalesced_weights(self, weight):
+        """RelCSR over the same edge set whose coalesced edge ``e`` (forward-plan order, ``dst[e], src[e], rel_id[e]``)
+        carries ``weight[e]`` (fp32 ``(n_edges,)``).  Shares the sorted index arrays and chunk schedules."""
+        if tuple(weight.shape) != (self.n_edges,):
+            raise ValueError("one weight per coalesced edge expected: (%d,), got %s" % (self.n_edges, tuple(weight.shape)))
         other = RelCSR.__new__(RelCSR)
         other.shape, other._opts = self.shape, self._opts
         other.chunk_edges, other.piece_len = self.chunk_edges, self.piece_len
         other.dst, other.src, other.rel_id = self.dst, self.src, self.rel_id
         other.edge_of_input, other.n_edges = self.edge_of_input, self.n_edges
-        w = torch.zeros(self.n_edges, dtype=torch.float32, device=self.device)
-        w.index_add_(0, self.edge_of_input, edge_weight.to(torch.float32))
-        other.weight, other.unit_weight = w, False
+        other.weight, other.unit_weight = weight.to(torch.float32).contiguous(), False
         other.dense_form = False                    # per-edge weights: the edge list is walked
         # the object that owns the sorted plans and their permutations: reweighting a reweighted RelCSR goes back to it
         other._base = getattr(self, "_base", None) or self

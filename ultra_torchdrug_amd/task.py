@@ -337,6 +337,22 @@ class KnowledgeGraphCompletion(nn.Module):
         h_index, t_index, r_index = self.training_indices(batch)
         return self.model(self.fact_graph, rel_inputs, h_index, t_index, r_index, all_loss=all_loss, metric=metric)
 
+    def visualize(self, triple, head=False):
+        """Explain one prediction (an addition of this package; the reference task has none): the paths through which the
+        model scores ``t`` for ``(h, r, ?)`` -- ``TransferNBFNet.visualize`` on the fact graph, with the relation representations
+        of ``r`` from ``rel_models`` (computed without gradient: only the edge weights are differentiated).  ``triple``:
+        ``(h, t, r)`` with ``r`` in ``[0, R)``.  ``head=True`` explains ``h`` for ``(?, r, t)`` instead, as the query
+        ``(t, r + R, h)`` (``negative_sample_to_tail``).  Returns ``(paths, weights)``."""
+        triple = torch.as_tensor(triple, device=self.device).reshape(-1).long()
+        if triple.numel() != 3:
+            raise ValueError("visualize explains one triple (h, t, r), got %d ids" % triple.numel())
+        h, t, r = triple.view(3, 1)
+        with torch.no_grad():
+            rel_inputs = self.relation_representations(r)
+        if head:
+            h, t, r = t, h, r + self.fact_graph.num_relation
+        return self.model.visualize(self.fact_graph, rel_inputs, h, t, r)
+
     def training_indices(self, batch):
         """task.py:264-274: ``(B, 1 + num_negative)`` index grids, column 0 = the positive triple, the rest strict
         negatives (tails corrupted in the first half of the batch, heads in the second)."""
