@@ -346,6 +346,32 @@ int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd_host, const float 
                                     int64_t n_rel, int64_t F, int sum_op, int mul_op, void *stream);
 
 /*
+ * rspmm with RotatE messages (layer.message for message_func = "rotate", /root/reference/ultra/layer.py:69-75, :256-262):
+ * each query block of `block` columns (even) is `block / 2` complex pairs, real part in column c = b * block + d, imaginary part
+ * in c + block / 2 (d < block / 2), and the message of an edge is w * (input[src] (complex *) relation[rel]) per pair:
+ *     y_re = w * ((x_re * r_re) - (x_im * r_im)),   y_im = w * ((x_re * r_im) + (x_im * r_re))
+ * reduced with sum_op over the edges of a row; empty rows give 0 / FLT_MAX / -FLT_MAX as ultra_rspmm_forward_f32.  The order of
+ * every operation is fixed (csrc/rotate.inc); split rows are summed in pieces as by the other plan kernels.
+ *   fwd, relation [n_rel, F], input [n_src, F], out [fwd->n_rows, F]; optional epilogue: add_rows [n_rows, F] OR the sparse
+ *   boundary (boundary_node int32 [F / block], boundary_value fp32 [F]) exactly as in ultra_rspmm_forward_f32 /
+ *   ultra_rspmm_forward_boundary_f32.  workspace: ultra_rspmm_workspace_bytes(fwd, F).
+ * Errors: ULTRA_ERR_BAD_SHAPE for block <= 0, odd block or F % block != 0; ULTRA_ERR_BAD_OP for an unknown sum_op;
+ * ULTRA_ERR_ABI for a foreign plan. */
+int ultra_rspmm_rotate_forward_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
+                                   const float *add_rows, const int32_t *boundary_node, const float *boundary_value,
+                                   float *out, void *workspace, size_t workspace_bytes, int64_t n_src, int64_t n_rel,
+                                   int64_t F, int64_t block, int sum_op, void *stream);
+
+/* Gradients of the call above w.r.t. input (over by_src) and relation (over by_rel); either may be NULL to skip it.
+ * output: the forward result WITHOUT the epilogue (read for min / max: a component of an edge receives the gradient where its
+ * message equals the output, every tied edge included).  workspace: the larger ultra_rspmm_workspace_bytes of the two plans. */
+int ultra_rspmm_rotate_backward_f32(const ultra_segments *by_src_host, const ultra_segments *by_rel_host,
+                                    const float *relation, const float *input, const float *output,
+                                    const float *output_grad, float *d_input, float *d_relation, void *workspace,
+                                    size_t workspace_bytes, int64_t n_src, int64_t n_dst, int64_t n_rel, int64_t F,
+                                    int64_t block, int sum_op, void *stream);
+
+/*
  * One layer of the path beam search behind TransferNBFNet.visualize (csrc/beam_search.hip; DESIGN.md "Explaining a
  * prediction").  Over the coalesced dst-CSR of the graph with inverse edges:
  *   row_ptr int32 [n_node + 1], src int32 [n_edges]   (rows = destination nodes, edges in coalesced order)

@@ -129,6 +129,8 @@ EXPORTS = (
     "ultra_layer_forward_sources_f32",
     "ultra_layer_score_supported",
     "ultra_layer_score_forward_f32",
+    "ultra_rspmm_rotate_forward_f32",
+    "ultra_rspmm_rotate_backward_f32",
 )
 
 _lib = None
@@ -313,6 +315,10 @@ def load():
     lib.ultra_dense_layer_forward_f32.argtypes = [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp]
     lib.ultra_calibrate_gather_f32.restype = i32
     lib.ultra_calibrate_gather_f32.argtypes = [vp, i64, vp, i64, vp, ctypes.POINTER(i64), vp]
+    lib.ultra_rspmm_rotate_forward_f32.restype = i32
+    lib.ultra_rspmm_rotate_forward_f32.argtypes = [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]
+    lib.ultra_rspmm_rotate_backward_f32.restype = i32
+    lib.ultra_rspmm_rotate_backward_f32.argtypes = [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]
     if lib.ultra_rspmm_abi_version() != ABI_VERSION:
         raise UltraLibraryError("ABI mismatch: library %d, binding %d" % (lib.ultra_rspmm_abi_version(), ABI_VERSION))
     if lib.ultra_segments_bytes() != ctypes.sizeof(UltraSegments):

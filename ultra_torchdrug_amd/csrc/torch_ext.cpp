@@ -674,6 +674,266 @@ std::tuple<Tensor, Tensor> rspmm_bwd_cpu(const Tensor &row_ptr, const Tensor &sr
     return {d_relation, d_input};
 }
 
+// ------------------------------------------------------------------------------------------------ rotate messages
+// rspmm with RotatE messages (include/ultra_rspmm.h, ultra_rspmm_rotate_forward_f32).  Plan forms on the device; raw-CSR forms
+// with a CPU kernel only, which evaluates the expressions of csrc/rotate.inc in the same order: every row strictly
+// sequentially in (src, rel) order forward, the reference's sweep over the CSR backward (one thread per slab of pairs).
+void check_rotate(int64_t F, int64_t block, int64_t sum_op) {
+    TORCH_CHECK(sum_op >= 0 && sum_op <= 2, "ultra_mi (rotate): unknown sum operator code ", sum_op);
+    TORCH_CHECK(block > 0 && block % 2 == 0 && F % block == 0, "ultra_mi (rotate): block must be even, positive and divide F = ", F,
+                ", got ", block);
+}
+
+Tensor rspmm_rotate_plan_fwd(const Tensor &plan, const Tensor &relation, const Tensor &input, const optional<Tensor> &add_rows,
+                             const optional<Tensor> &boundary_node, const optional<Tensor> &boundary_value, int64_t n_src,
+                             int64_t block, int64_t sum_op) {
+    const ultra_segments *seg = plan_of(plan, "plan");
+    TORCH_CHECK(seg != nullptr, "ultra_mi::rspmm_rotate_plan_fwd: plan is required");
+    check_dense(input, "input", at::kFloat, input);
+    check_dense(relation, "relation", at::kFloat, input);
+    TORCH_CHECK(input.dim() == 2 && relation.dim() == 2 && input.size(1) == relation.size(1) && input.size(0) == n_src,
+                "ultra_mi::rspmm_rotate_plan_fwd: relation (R, F) and input (n_src, F) expected");
+    const int64_t F = input.size(1), n_rel = relation.size(0);
+    check_rotate(F, block, sum_op);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    Tensor rl = relation.contiguous(), x = input.contiguous();
+    Tensor out = at::empty({seg->n_rows, F}, input.options());
+    if (out.numel() == 0) return out;
+    const size_t ws_bytes = ultra_rspmm_workspace_bytes(seg, F);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes / 4, 1)}, input.options());
+    Tensor add, bn, bv;
+    if (boundary_node.has_value() && boundary_node->defined()) {
+        TORCH_CHECK(boundary_value.has_value() && boundary_value->defined() && !(add_rows.has_value() && add_rows->defined()),
+                    "ultra_mi::rspmm_rotate_plan_fwd: give the boundary either dense (add_rows) or sparse (node, value)");
+        check_dense(*boundary_node, "boundary_node", at::kInt, input);
+        check_dense(*boundary_value, "boundary_value", at::kFloat, input);
+        bv = boundary_value->contiguous();
+        bn = boundary_node->contiguous();
+        TORCH_CHECK(bv.dim() == 2 && bv.size(0) == bn.numel() && bv.numel() == F && bv.size(1) == block,
+                    "ultra_mi: boundary must be (B,), (B, block) with B * block == F");
+    } else if (add_rows.has_value() && add_rows->defined()) {
+        check_dense(*add_rows, "add_rows", at::kFloat, input);
+        TORCH_CHECK(add_rows->sizes() == out.sizes(), "ultra_mi: add_rows must have the shape of the output");
+        add = add_rows->contiguous();
+    }
+    check_status(ultra_rspmm_rotate_forward_f32(seg, rl.data_ptr<float>(), x.data_ptr<float>(),
+                                                add.defined() ? add.data_ptr<float>() : nullptr,
+                                                bn.defined() ? bn.data_ptr<int>() : nullptr,
+                                                bv.defined() ? bv.data_ptr<float>() : nullptr, out.data_ptr<float>(),
+                                                ws.data_ptr<float>(), ws_bytes, n_src, n_rel, F, block, (int)sum_op,
+                                                current_stream(input)),
+                 "ultra_rspmm_rotate_forward_f32");
+    return out;
+}
+
+// (d_input, d_relation); a gradient whose plan is not given comes back as an empty tensor
+std::tuple<Tensor, Tensor> rspmm_rotate_plan_bwd(const optional<Tensor> &by_src, const optional<Tensor> &by_rel,
+                                                 const Tensor &relation, const Tensor &input, const optional<Tensor> &output,
+                                                 const Tensor &output_grad, int64_t n_src, int64_t n_dst, int64_t block,
+                                                 int64_t sum_op) {
+    const ultra_segments *s_src = plan_of(by_src, "by_src"), *s_rel = plan_of(by_rel, "by_rel");
+    check_dense(input, "input", at::kFloat, input);
+    check_dense(relation, "relation", at::kFloat, input);
+    check_dense(output_grad, "output_grad", at::kFloat, input);
+    TORCH_CHECK(input.dim() == 2 && relation.dim() == 2 && input.size(1) == relation.size(1) && input.size(0) == n_src,
+                "ultra_mi::rspmm_rotate_plan_bwd: relation (R, F) and input (n_src, F) expected");
+    const int64_t F = input.size(1), n_rel = relation.size(0);
+    check_rotate(F, block, sum_op);
+    TORCH_CHECK(output_grad.dim() == 2 && output_grad.size(0) == n_dst && output_grad.size(1) == F,
+                "ultra_mi::rspmm_rotate_plan_bwd: output_grad must be (", n_dst, ", ", F, ")");
+    TORCH_CHECK(!s_src || s_src->n_rows == n_src, "ultra_mi::rspmm_rotate_plan_bwd: by_src plan rows != n_src");
+    TORCH_CHECK(!s_rel || s_rel->n_rows == n_rel, "ultra_mi::rspmm_rotate_plan_bwd: by_rel plan rows != relation rows");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    Tensor rl = relation.contiguous(), x = input.contiguous(), g = output_grad.contiguous(), o;
+    if (output.has_value() && output->defined()) {
+        check_dense(*output, "output", at::kFloat, input);
+        TORCH_CHECK(output->sizes() == output_grad.sizes(), "ultra_mi::rspmm_rotate_plan_bwd: output must have the shape of output_grad");
+        o = output->contiguous();
+    }
+    TORCH_CHECK(sum_op == 0 || o.defined(), "ultra_mi::rspmm_rotate_plan_bwd: min / max aggregation needs the forward output");
+    Tensor d_input = s_src ? at::empty_like(x) : at::empty({0}, input.options());
+    Tensor d_relation = s_rel ? at::empty_like(rl) : at::empty({0}, input.options());
+    if (!s_src && !s_rel) return {d_input, d_relation};
+    const size_t ws_bytes = std::max(s_src ? ultra_rspmm_workspace_bytes(s_src, F) : 0,
+                                     s_rel ? ultra_rspmm_workspace_bytes(s_rel, F) : 0);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes / 4, 1)}, input.options());
+    check_status(ultra_rspmm_rotate_backward_f32(s_src, s_rel, rl.data_ptr<float>(), x.data_ptr<float>(),
+                                                 o.defined() ? o.data_ptr<float>() : nullptr, g.data_ptr<float>(),
+                                                 s_src ? d_input.data_ptr<float>() : nullptr,
+                                                 s_rel ? d_relation.data_ptr<float>() : nullptr, ws.data_ptr<float>(),
+                                                 ws_bytes, n_src, n_dst, n_rel, F, block, (int)sum_op, current_stream(input)),
+                 "ultra_rspmm_rotate_backward_f32");
+    return {d_input, d_relation};
+}
+
+template <int SUM, bool HAS_W>
+void rotate_rows_cpu(const int *row_ptr, const int *src, const int *rel, const float *w, const float *relation, const float *x,
+                     float *out, int64_t n_rows, int64_t F, int64_t half) {
+    const float identity = SUM == 0 ? 0.0f : (SUM == 1 ? FLT_MAX : -FLT_MAX);
+    at::parallel_for(0, n_rows, 1, [&](int64_t v0, int64_t v1) {
+        for (int64_t v = v0; v < v1; ++v) {
+            float *__restrict__ o = out + v * F;
+            for (int64_t j = 0; j < F; ++j) o[j] = identity;
+            for (int64_t k = row_ptr[v]; k < row_ptr[v + 1]; ++k) {
+                const float *__restrict__ xr = x + (int64_t)src[k] * F;
+                const float *__restrict__ rr = relation + (int64_t)rel[k] * F;
+                const float wk = HAS_W ? w[k] : 1.0f;
+                for (int64_t c0 = 0; c0 < F; c0 += 2 * half) {
+                    for (int64_t c = c0; c < c0 + half; ++c) {
+                        const float a = xr[c] * rr[c], b = xr[c + half] * rr[c + half];
+                        const float cc = xr[c] * rr[c + half], d = xr[c + half] * rr[c];
+                        float yr = a - b, yi = cc + d;
+                        if (HAS_W) { yr = wk * yr; yi = wk * yi; }
+                        o[c] = reduce_op<SUM>(o[c], yr);
+                        o[c + half] = reduce_op<SUM>(o[c + half], yi);
+                    }
+                }
+            }
+        }
+    });
+}
+
+template <int SUM, bool HAS_W>
+void rotate_sweep_backward_cpu(const int *row_ptr, const int *src, const int *rel, const float *w, const float *relation,
+                               const float *x, const float *out, const float *g, float *d_rel, float *d_x, int64_t n_rows,
+                               int64_t F, int64_t half) {
+    const int64_t n_pairs = F / 2, slab = 32, n_slab = (n_pairs + slab - 1) / slab;
+    at::parallel_for(0, n_slab, 1, [&](int64_t s0, int64_t s1) {
+        for (int64_t sl = s0; sl < s1; ++sl) {
+            const int64_t q0 = sl * slab, q1 = std::min(n_pairs, q0 + slab);
+            for (int64_t v = 0; v < n_rows; ++v) {
+                for (int64_t k = row_ptr[v]; k < row_ptr[v + 1]; ++k) {
+                    const float *__restrict__ xr = x + (int64_t)src[k] * F;
+                    const float *__restrict__ rr = relation + (int64_t)rel[k] * F;
+                    float *__restrict__ dx = d_x + (int64_t)src[k] * F;
+                    float *__restrict__ dr = d_rel + (int64_t)rel[k] * F;
+                    const float wk = HAS_W ? w[k] : 1.0f;
+                    for (int64_t q = q0; q < q1; ++q) {
+                        const int64_t c = (q / half) * 2 * half + q % half, ci = c + half;
+                        float gr = g[v * F + c], gi = g[v * F + ci];
+                        if (SUM != 0) {
+                            const float a = xr[c] * rr[c], b = xr[ci] * rr[ci], cc = xr[c] * rr[ci], d = xr[ci] * rr[c];
+                            float yr = a - b, yi = cc + d;
+                            if (HAS_W) { yr = wk * yr; yi = wk * yi; }
+                            gr = gr * ((out[v * F + c] == yr) ? 1.0f : 0.0f);
+                            gi = gi * ((out[v * F + ci] == yi) ? 1.0f : 0.0f);
+                        }
+                        {   // d_input: the relation pair as the factor
+                            const float a = gr * rr[c], b = gi * rr[ci], cc = gi * rr[c], d = gr * rr[ci];
+                            float tr = a + b, ti = cc - d;
+                            if (HAS_W) { tr = wk * tr; ti = wk * ti; }
+                            dx[c] = dx[c] + tr;
+                            dx[ci] = dx[ci] + ti;
+                        }
+                        {   // d_relation: the input pair as the factor
+                            const float a = gr * xr[c], b = gi * xr[ci], cc = gi * xr[c], d = gr * xr[ci];
+                            float tr = a + b, ti = cc - d;
+                            if (HAS_W) { tr = wk * tr; ti = wk * ti; }
+                            dr[c] = dr[c] + tr;
+                            dr[ci] = dr[ci] + ti;
+                        }
+                    }
+                }
+            }
+        }
+    });
+}
+
+Tensor rspmm_rotate_fwd_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &rel, const optional<Tensor> &w,
+                            const Tensor &relation, const Tensor &input, int64_t block, int64_t sum_op) {
+    const CsrArgs a = check_csr_cpu(row_ptr, src, rel, w, relation, input, sum_op, 0);
+    check_rotate(a.F, block, sum_op);
+    Tensor rp = row_ptr.contiguous(), s = src.contiguous(), r = rel.contiguous(), rl = relation.contiguous(),
+           x = input.contiguous(), wt;
+    if (w.has_value() && w->defined()) wt = w->contiguous();
+    Tensor out = at::empty({a.n_rows, a.F}, input.options());
+    if (out.numel() == 0) return out;
+    const float *wp = wt.defined() ? wt.data_ptr<float>() : nullptr;
+#define ULTRA_ROT_FWD(S)                                                                                                    \
+    (wp ? rotate_rows_cpu<S, true>(rp.data_ptr<int>(), s.data_ptr<int>(), r.data_ptr<int>(), wp, rl.data_ptr<float>(),     \
+                                   x.data_ptr<float>(), out.data_ptr<float>(), a.n_rows, a.F, block / 2)                  \
+        : rotate_rows_cpu<S, false>(rp.data_ptr<int>(), s.data_ptr<int>(), r.data_ptr<int>(), wp, rl.data_ptr<float>(),   \
+                                    x.data_ptr<float>(), out.data_ptr<float>(), a.n_rows, a.F, block / 2))
+    if (sum_op == 0) ULTRA_ROT_FWD(0);
+    else if (sum_op == 1) ULTRA_ROT_FWD(1);
+    else ULTRA_ROT_FWD(2);
+#undef ULTRA_ROT_FWD
+    return out;
+}
+
+std::tuple<Tensor, Tensor> rspmm_rotate_bwd_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &rel,
+                                                const optional<Tensor> &w, const Tensor &relation, const Tensor &input,
+                                                const Tensor &output, const Tensor &output_grad, int64_t block, int64_t sum_op) {
+    const CsrArgs a = check_csr_cpu(row_ptr, src, rel, w, relation, input, sum_op, 0);
+    check_rotate(a.F, block, sum_op);
+    check_host(output_grad, "output_grad", at::kFloat);
+    TORCH_CHECK(output_grad.dim() == 2 && output_grad.size(0) == a.n_rows && output_grad.size(1) == a.F,
+                "ultra_mi::rspmm_rotate_bwd: output_grad must be (", a.n_rows, ", ", a.F, ")");
+    if (sum_op != 0) {
+        check_host(output, "output", at::kFloat);
+        TORCH_CHECK(output.sizes() == output_grad.sizes(), "ultra_mi::rspmm_rotate_bwd: output must have the shape of output_grad");
+    }
+    Tensor d_relation = at::zeros_like(relation, at::MemoryFormat::Contiguous);
+    Tensor d_input = at::zeros_like(input, at::MemoryFormat::Contiguous);
+    if (a.n_edges == 0 || a.F == 0) return {d_relation, d_input};
+    Tensor rp = row_ptr.contiguous(), s = src.contiguous(), r = rel.contiguous(), rl = relation.contiguous(),
+           x = input.contiguous(), g = output_grad.contiguous(), o, wt;
+    if (sum_op != 0) o = output.contiguous();
+    if (w.has_value() && w->defined()) wt = w->contiguous();
+    const float *wp = wt.defined() ? wt.data_ptr<float>() : nullptr;
+    const float *op = o.defined() ? o.data_ptr<float>() : nullptr;
+#define ULTRA_ROT_BWD(S)                                                                                                     \
+    (wp ? rotate_sweep_backward_cpu<S, true>(rp.data_ptr<int>(), s.data_ptr<int>(), r.data_ptr<int>(), wp,                   \
+                                             rl.data_ptr<float>(), x.data_ptr<float>(), op, g.data_ptr<float>(),             \
+                                             d_relation.data_ptr<float>(), d_input.data_ptr<float>(), a.n_rows, a.F,         \
+                                             block / 2)                                                                      \
+        : rotate_sweep_backward_cpu<S, false>(rp.data_ptr<int>(), s.data_ptr<int>(), r.data_ptr<int>(), wp,                  \
+                                              rl.data_ptr<float>(), x.data_ptr<float>(), op, g.data_ptr<float>(),            \
+                                              d_relation.data_ptr<float>(), d_input.data_ptr<float>(), a.n_rows, a.F,        \
+                                              block / 2))
+    if (sum_op == 0) ULTRA_ROT_BWD(0);
+    else if (sum_op == 1) ULTRA_ROT_BWD(1);
+    else ULTRA_ROT_BWD(2);
+#undef ULTRA_ROT_BWD
+    return {d_relation, d_input};
+}
+
+class RotateCsrFunction : public torch::autograd::Function<RotateCsrFunction> {
+   public:
+    static Tensor forward(torch::autograd::AutogradContext *ctx, const Tensor &row_ptr, const Tensor &src, const Tensor &rel,
+                          const optional<Tensor> &w, const Tensor &relation, const Tensor &input, int64_t block,
+                          int64_t sum_op) {
+        at::AutoDispatchBelowADInplaceOrView guard;
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("ultra_mi::rspmm_rotate_fwd", "")
+                             .typed<Tensor(const Tensor &, const Tensor &, const Tensor &, const optional<Tensor> &,
+                                           const Tensor &, const Tensor &, int64_t, int64_t)>();
+        Tensor out = op.call(row_ptr, src, rel, w, relation, input, block, sum_op);
+        ctx->save_for_backward({row_ptr, src, rel, (w.has_value() && w->defined()) ? *w : Tensor(), relation, input, out});
+        ctx->saved_data["block"] = block;
+        ctx->saved_data["sum_op"] = sum_op;
+        return out;
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext *ctx,
+                                                   torch::autograd::variable_list grads) {
+        auto saved = ctx->get_saved_variables();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("ultra_mi::rspmm_rotate_bwd", "")
+                             .typed<std::tuple<Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &,
+                                                               const optional<Tensor> &, const Tensor &, const Tensor &,
+                                                               const Tensor &, const Tensor &, int64_t, int64_t)>();
+        optional<Tensor> w;
+        if (saved[3].defined()) w = saved[3];
+        auto result = op.call(saved[0], saved[1], saved[2], w, saved[4], saved[5], saved[6], grads[0].contiguous(),
+                              ctx->saved_data["block"].toInt(), ctx->saved_data["sum_op"].toInt());
+        return {Tensor(), Tensor(), Tensor(), Tensor(), std::get<0>(result), std::get<1>(result), Tensor(), Tensor()};
+    }
+};
+
+Tensor rspmm_rotate_fwd_autograd(const Tensor &row_ptr, const Tensor &src, const Tensor &rel, const optional<Tensor> &w,
+                                 const Tensor &relation, const Tensor &input, int64_t block, int64_t sum_op) {
+    return RotateCsrFunction::apply(row_ptr, src, rel, w, relation, input, block, sum_op);
+}
+
 // ------------------------------------------------------------------------------------------------ beam_search_step
 // One layer of the path beam search of TransferNBFNet.visualize (include/ultra_rspmm.h, ultra_beam_search_step_f32; DESIGN.md
 // "Explaining a prediction").  The CPU kernel below is the same definition as csrc/beam_search.hip, bit for bit: the same f32
@@ -813,6 +1073,29 @@ TORCH_LIBRARY(ultra_mi, m) {
           "Tensor(a!)? d_input, bool accumulate, int n_src, int n_dst, int sum_op, int mul_op) -> Tensor");
     m.def("beam_search_step(Tensor row_ptr, Tensor src, Tensor edge_grad, Tensor input, int tail) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int", []() -> int64_t { return ultra_rspmm_abi_version(); });
+    m.def("rspmm_rotate_fwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, int block, "
+          "int sum_op) -> Tensor");
+    m.def("rspmm_rotate_bwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, Tensor output, "
+          "Tensor output_grad, int block, int sum_op) -> (Tensor, Tensor)");
+    m.def("rspmm_rotate_plan_fwd(Tensor plan, Tensor relation, Tensor input, Tensor? add_rows, Tensor? boundary_node, "
+          "Tensor? boundary_value, int n_src, int block, int sum_op) -> Tensor");
+    m.def("rspmm_rotate_plan_bwd(Tensor? by_src, Tensor? by_rel, Tensor relation, Tensor input, Tensor? output, "
+          "Tensor output_grad, int n_src, int n_dst, int block, int sum_op) -> (Tensor, Tensor)");
+}
+
+// rotate messages: the raw-CSR operators have a CPU kernel only (device tensors take the plan forms)
+TORCH_LIBRARY_IMPL(ultra_mi, CPU, m) {
+    m.impl("rspmm_rotate_fwd", rspmm_rotate_fwd_cpu);
+    m.impl("rspmm_rotate_bwd", rspmm_rotate_bwd_cpu);
+}
+
+TORCH_LIBRARY_IMPL(ultra_mi, CompositeExplicitAutograd, m) {
+    m.impl("rspmm_rotate_plan_fwd", rspmm_rotate_plan_fwd);
+    m.impl("rspmm_rotate_plan_bwd", rspmm_rotate_plan_bwd);
+}
+
+TORCH_LIBRARY_IMPL(ultra_mi, Autograd, m) {
+    m.impl("rspmm_rotate_fwd", rspmm_rotate_fwd_autograd);
 }
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch

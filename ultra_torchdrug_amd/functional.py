@@ -21,7 +21,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward","first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1577,6 +1577,140 @@ def generalized_rspmm(sparse, relation, input, sum="add", mul="mul", edge_weight
     else:
         out = _RSPMMFunction.apply(sparse_leaf, relation, input, csr, sum, mul, None, None, None, edge_weight)
     return out.squeeze(-1) if squeeze else out
+
+
+def _rotate_ops(csr, relation, input, sum, block, require_hip):
+    """Validates a rotate call: ``(sum_op, block)``.  Unknown ``sum`` names raise ``ValueError``; a ``block`` that is not even,
+    positive and a divisor of ``F`` raises ``RuntimeError`` (a shape problem)."""
+    if sum not in _lib.SUM_OPS:
+        raise ValueError("Can't find a rotate rspmm operator for sum=`%s` (expected add, min or max)" % sum)
+    _check_dense(csr, relation, input, require_hip=require_hip)
+    block, F = int(block), input.shape[1]
+    if block <= 0 or block % 2 or F % block:
+        raise RuntimeError("rotate messages need an even block width that divides F = %d, got block = %d" % (F, block))
+    return _lib.SUM_OPS[sum], block
+
+
+def rotate_rspmm_forward(csr, relation, input, sum="add", block=64, add_rows=None, boundary=None):
+    """Forward of :func:`rotate_rspmm` without autograd (``ultra_rspmm_rotate_forward_f32``).  ``add_rows`` / ``boundary =
+    (node, value)``: the epilogue ``(+ | min | max) boundary`` inside the kernel, as in :func:`rspmm_forward`."""
+    sum_op, block = _rotate_ops(csr, relation, input, sum, block, True)
+    relation, input = relation.contiguous(), input.contiguous()
+    F = input.shape[1]
+    out = torch.empty(csr.shape[0], F, dtype=torch.float32, device=input.device)
+    b_node = b_value = None
+    if add_rows is not None:
+        if boundary is not None:
+            raise RuntimeError("give the boundary either dense (add_rows) or sparse (boundary), not both")
+        add_rows = add_rows.contiguous()
+        if add_rows.shape != out.shape or add_rows.dtype != torch.float32 or add_rows.device != out.device:
+            raise RuntimeError("add_rows must be fp32 %s on %s" % (tuple(out.shape), out.device))
+    if boundary is not None:
+        b_node, b_value = boundary[0], boundary[1].contiguous()
+        if (b_node.dtype != torch.int32 or b_value.dtype != torch.float32 or b_node.dim() != 1 or b_value.dim() != 2
+                or b_value.shape != (b_node.shape[0], block) or b_value.numel() != F or b_node.device != out.device
+                or b_value.device != out.device or not b_node.is_contiguous()):
+            raise RuntimeError("boundary must be (int32 (B,), fp32 (B, %d)) with B * %d == %d on %s" % (block, block, F, out.device))
+    if out.numel() == 0:
+        return out
+    seg = csr.fwd
+    if _torch_ext.binding() == "torch":
+        return _torch_ext.load().rspmm_rotate_plan_fwd(seg.plan_tensor, relation, input, add_rows, b_node, b_value, csr.shape[1],
+                                                       block, sum_op)
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(seg, F, input.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(input.device):
+        _lib.check(lib.ultra_rspmm_rotate_forward_f32(
+            seg.pointer, relation.data_ptr(), input.data_ptr(), ptr(add_rows), ptr(b_node), ptr(b_value), out.data_ptr(),
+            ptr(ws), ws_bytes, csr.shape[1], csr.shape[2], F, block, sum_op, _stream()))
+    return out
+
+
+def rotate_rspmm_backward(csr, relation, input, output, output_grad, sum="add", block=64, need_input=True, need_relation=True):
+    """``(d_input, d_relation)`` of :func:`rotate_rspmm_forward` (``ultra_rspmm_rotate_backward_f32``); ``output`` is the forward
+    result without the epilogue (read for min / max only)."""
+    sum_op, block = _rotate_ops(csr, relation, input, sum, block, True)
+    relation, input, output_grad = relation.contiguous(), input.contiguous(), output_grad.contiguous()
+    output = output.contiguous() if output is not None else None
+    F, dev = input.shape[1], input.device
+    if not need_input and not need_relation:
+        return None, None
+    by_src = csr.by_src if need_input else None
+    by_rel = csr.by_rel if need_relation else None
+    if _torch_ext.binding() == "torch":
+        d_input, d_relation = _torch_ext.load().rspmm_rotate_plan_bwd(
+            by_src.plan_tensor if by_src is not None else None, by_rel.plan_tensor if by_rel is not None else None,
+            relation, input, output, output_grad, csr.shape[1], csr.shape[0], block, sum_op)
+        return (d_input if need_input else None), (d_relation if need_relation else None)
+    d_input = torch.empty_like(input) if need_input else None
+    d_relation = torch.empty_like(relation) if need_relation else None
+    lib = _lib.load()
+    n_ws = max(by_src.workspace_rows if by_src is not None else 0, by_rel.workspace_rows if by_rel is not None else 0) * F
+    ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.ultra_rspmm_rotate_backward_f32(
+            by_src.pointer if by_src is not None else None, by_rel.pointer if by_rel is not None else None,
+            relation.data_ptr(), input.data_ptr(), ptr(output), output_grad.data_ptr(), ptr(d_input), ptr(d_relation),
+            ptr(ws), n_ws * 4, csr.shape[1], csr.shape[0], csr.shape[2], F, block, sum_op, _stream()))
+    return d_input, d_relation
+
+
+class _RotateFunction(torch.autograd.Function):
+    """Autograd of :func:`rotate_rspmm` on device tensors; ``add_rows`` / ``(b_node, b_value)`` as in :class:`_RSPMMFunction`."""
+
+    @staticmethod
+    def forward(ctx, relation, input, csr, sum, block, add_rows=None, b_node=None, b_value=None):
+        boundary = None if b_node is None else (b_node, b_value.detach())
+        out = rotate_rspmm_forward(csr, relation, input, sum, block, add_rows=add_rows, boundary=boundary)
+        ctx.csr, ctx.sum, ctx.block = csr, sum, block
+        ctx.has_add_rows, ctx.b_node = add_rows is not None, b_node
+        ctx.save_for_backward(relation, input, out if sum != "add" else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, output_grad):
+        relation, input, out = ctx.saved_tensors
+        d_input, d_relation = rotate_rspmm_backward(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.block,
+                                                    need_input=ctx.needs_input_grad[1], need_relation=ctx.needs_input_grad[0])
+        d_add = output_grad if (ctx.has_add_rows and ctx.needs_input_grad[5]) else None
+        d_value = None
+        if ctx.b_node is not None and ctx.needs_input_grad[7]:
+            n_query = ctx.b_node.shape[0]
+            blocks = output_grad.view(output_grad.shape[0], n_query, -1)
+            d_value = blocks[ctx.b_node.long(), torch.arange(n_query, device=output_grad.device)]
+        return d_relation, d_input, None, None, None, d_add, None, d_value
+
+
+def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, boundary=None):
+    r"""Relational sparse-dense product with RotatE messages (the ``message_func="rotate"`` layers without an ``(E, F)`` tensor).
+
+    .. math::  out_{v,:} = \bigoplus_{(v, u, r) \in sparse} w_{vur} \cdot (input_{u,:} \circledast relation_{r,:})
+
+    where every query block of ``block`` columns holds ``block / 2`` complex numbers, real parts first, and
+    :math:`\circledast` is their element-wise complex product (``layer.message``'s rotate branch); :math:`\oplus` = ``sum``
+    in {add, min, max}.  ``sparse``: as in :func:`generalized_rspmm` (duplicate triples merged by summing their weights);
+    differentiable in ``relation`` and ``input``, on CPU tensors (``torch.ops.ultra_mi.rspmm_rotate_fwd``, every row strictly
+    sequentially) or MI355X tensors (the plan kernels of ``csrc/rotate.inc``).  The sparse values may not require grad.
+    Extension (device tensors, ``sum="add"``): ``add_rows`` / ``boundary = (node, value)`` -- the epilogue ``+ boundary`` inside
+    the kernel, differentiable in ``add_rows`` / ``value`` (see :func:`rspmm_forward`)."""
+    if sum not in _lib.SUM_OPS:
+        raise ValueError("Can't find a rotate rspmm operator for sum=`%s` (expected add, min or max)" % sum)
+    csr, sparse_leaf = _as_relcsr(sparse)
+    if sparse_leaf is not None:
+        raise RuntimeError("rotate_rspmm has no gradient for the sparse values (the reference takes its message + "
+                           "aggregate path then, ultra/layer.py:299)")
+    if (add_rows is not None or boundary is not None) and sum != "add":
+        raise RuntimeError("rotate_rspmm: the fused boundary is for sum aggregation (max: torch.max after the call)")
+    sum_op, block = _rotate_ops(csr, relation, input, sum, block, False)
+    if not input.is_cuda:
+        if add_rows is not None or boundary is not None:
+            raise RuntimeError("rotate_rspmm: the fused boundary runs on an MI355X (HIP) device only")
+        row_ptr, src, rel, w = csr.csr_arrays
+        return _torch_ext.load().rspmm_rotate_fwd(row_ptr, src, rel, w, relation, input, block, sum_op)
+    b_node, b_value = boundary if boundary is not None else (None, None)
+    return _RotateFunction.apply(relation, input, csr, sum, block, add_rows, b_node, b_value)
 
 
 BEAM_MAX = 32        # beams per node the beam-search step takes (csrc/beam_search.hip: register top-K of at most 32)

@@ -263,6 +263,12 @@ class _RelationalConvBase(nn.Module):
 
     # ---- rspmm path (layer.py:111-182, :298-384) -------------------------------------------------------
     def message_and_aggregate(self, graph, input, input_is_boundary=False):
+        # rotate messages through the native operator: fp32, sum / mean / max, even width; device tensors only where the
+        # backend takes them (a backend that declines keeps the materialised route), host tensors through its CPU twin
+        if (self.message_func == "rotate" and not graph.requires_grad and self.aggregate_func in ("sum", "mean", "max")
+                and input.shape[-1] % 2 == 0 and input.dtype == torch.float32
+                and (backend.get().accepts(input) or not input.is_cuda)):
+            return self._rotate_aggregate(graph, input)
         if graph.requires_grad or self.message_func == "rotate":
             return self.aggregate(graph, self.message(graph, input))
         if self.message_func not in self.message2mul:
@@ -333,6 +339,36 @@ class _RelationalConvBase(nn.Module):
                 sum, sq_sum = sum + boundary, sq_sum + boundary ** 2
                 max, min = torch.max(max, boundary), torch.min(min, boundary)
             update = self._pna(sum / degree_out, sq_sum / degree_out, max, min, degree_out)
+        return update.view(len(update), batch_size, -1)
+
+    def _rotate_aggregate(self, graph, input):
+        """``aggregate(message(graph, input))`` for rotate messages with sum / mean / max through the native operator
+        (``functional.rotate_rspmm``): no ``(E, B, D)`` tensor.  The same boundary handling as the DistMult branches above:
+        fused in the kernel in inference, ``add_rows`` or the sparse form in training sums, ``torch.max`` after an unfused
+        max in training."""
+        batch_size, dim = len(graph.query), input.shape[-1]
+        input = input.flatten(1)
+        boundary = graph.boundary.flatten(1)
+        tables = getattr(graph, "relation_tables", None)
+        if tables is not None and id(self) in tables:
+            relation_input = tables[id(self)]
+        else:
+            relation_input = self._relation_table(graph, batch_size).flatten(1)    # (R, B*D)
+        adjacency = graph.relcsr
+        ops = backend.get()
+        reduce = "max" if self.aggregate_func == "max" else "add"
+        sparse_bound = getattr(graph, "boundary_sparse", None)
+        bound_args = dict(add_rows=boundary) if sparse_bound is None else dict(boundary=sparse_bound)
+        if ops.accepts(input) and self._no_grad(input, relation_input, boundary):
+            update = ops.rotate_rspmm_forward(adjacency, relation_input, input, reduce, dim, **bound_args)
+        elif reduce == "max":
+            update = torch.max(ops.rotate_rspmm(adjacency, relation_input, input, "max", dim), boundary)
+        elif ops.accepts(input):
+            update = ops.rotate_rspmm(adjacency, relation_input, input, "add", dim, **bound_args)
+        else:
+            update = ops.rotate_rspmm(adjacency, relation_input, input, "add", dim) + boundary
+        if self.aggregate_func == "mean":
+            update = update / (graph.degree_out.unsqueeze(-1) + 1)
         return update.view(len(update), batch_size, -1)
 
     def combine(self, input, update):
