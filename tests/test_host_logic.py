@@ -34,6 +34,44 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.UltraSegments) == 23 * 8 == lib.ultra_segments_bytes()     # (ABI 8: + the struct_bytes | abi_version fence)
 
 
+def test_binding_signatures_match_the_header_prototypes():
+    """Argument count and kind of every row of ``_lib.SIGNATURES`` == the prototype of include/ultra_rspmm.h (ctypes converts a
+    Python int to whatever ``argtypes`` says: an ``int64_t`` listed where the header has ``int``, or one argument too few, is an
+    error nowhere else -- only a garbage pointer on the device)."""
+    import ctypes
+    from ultra_torchdrug_amd import _lib
+    header = open(os.path.join(ROOT, "include", "ultra_rspmm.h")).read()
+    header = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    prototypes = re.findall(r"^(int|size_t|const char \*)\s*(ultra_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    assert sorted(name for _, name, _ in prototypes) == sorted(_lib.SIGNATURES) and len(prototypes) == len(_lib.SIGNATURES)
+
+    def header_kind(text):
+        text = " ".join(text.split())
+        if "*" in text:
+            return "pointer"
+        words = [w for w in text.split() if w != "const"]
+        kind = words[0]                                     # the type; a parameter name may follow
+        assert kind in ("int64_t", "int", "float", "size_t"), text
+        return kind
+
+    simple = {ctypes.c_int64: "int64_t", ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
+
+    def binding_kind(ctype):
+        if ctype in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ctype, ctypes._Pointer):
+            return "pointer"
+        return simple[ctype]
+
+    assert len(set(simple)) == 4        # (on this ABI the four scalar kinds are distinct ctypes classes)
+    for restype, name, params in prototypes:
+        params = [p for p in params.split(",") if p.strip() and p.strip() != "void"]
+        want_restype, want_argtypes = _lib.SIGNATURES[name]
+        assert binding_kind(want_restype) == header_kind(restype), name
+        assert [binding_kind(t) for t in want_argtypes] == [header_kind(p) for p in params], name
+    lib = _lib.load()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():           # ... and load() applied the table
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == list(argtypes), name
+
+
 def test_library_exports_nothing_but_the_header():
     """`nm -D` of the built library == the functions include/ultra_rspmm.h declares (a thread_local and two
     kernel handles leaked out).  -fvisibility=hidden + the header's visibility pragma; `__hip_cuid_*` are the HIP

@@ -6,6 +6,8 @@ cannot be loaded every operator of this package raises immediately.
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ULTRA_RSPMM_LIB: load another build of the same ABI (kernel A/B runs, tools/kbench.py)
 LIB_PATH = os.environ.get("ULTRA_RSPMM_LIB") or os.path.join(_HERE, "libultra_rspmm.so")
@@ -54,84 +56,95 @@ class UltraSegments(ctypes.Structure):
             self.abi_version = ABI_VERSION
 
 
-EXPORTS = (
-    "ultra_rspmm_abi_version",
-    "ultra_segments_bytes",
-    "ultra_rspmm_status_string",
-    "ultra_rspmm_last_hip_error",
-    "ultra_rspmm_device_info",
-    "ultra_rspmm_profile_next",
-    "ultra_rspmm_event_create",
-    "ultra_rspmm_event_destroy",
-    "ultra_rspmm_event_elapsed_ms",
-    "ultra_rspmm_force_general_path",
-    "ultra_rspmm_reserve_cus",
-    "ultra_rspmm_workspace_bytes",
-    "ultra_rspmm_forward_f32",
-    "ultra_rspmm_fwd_f32",
-    "ultra_rspmm_forward_boundary_f32",
-    "ultra_rspmm_frontier_f32",
-    "ultra_first_layer_sparse_supported",
-    "ultra_first_layer_sparse_f32",
-    "ultra_rspmm_backward_boundary_rows_f32",
-    "ultra_rspmm_backward_boundary_rows_workspace",
-    "ultra_rspmm_backward_f32",
-    "ultra_rspmm_backward_accumulate_f32",
-    "ultra_rspmm_backward_weight_f32",
-    "ultra_beam_search_step_f32",
-    "ultra_rspmm_backward_active_f32",
-    "ultra_node_bitmap",
-    "ultra_rspmm_drelation_boundary_f32",
-    "ultra_combine_forward_f32",
-    "ultra_combine_forward_boundary_f32",
-    "ultra_combine_backward_waves",
-    "ultra_combine_backward_f32",
-    "ultra_combine_dxdu_f32",
-    "ultra_combine_backward_fused_waves",
-    "ultra_combine_backward_fused_f32",
-    "ultra_linear_forward_f32",
-    "ultra_score_forward_f32",
-    "ultra_relation_project_f32",
-    "ultra_relation_project_backward_blocks",
-    "ultra_relation_project_backward_f32",
-    "ultra_filtered_rank",
-    "ultra_filtered_rank_keys",
-    "ultra_strict_negative",
-    "ultra_edge_removal_weights",
-    "ultra_edge_removal_marks",
-    "ultra_prepare_queries",
-    "ultra_relation_stack_inputs",
-    "ultra_statistics_blocks",
-    "ultra_statistics_f32",
-    "ultra_bce_adversarial_f32",
-    "ultra_candidate_tiles",
-    "ultra_score_rows_forward_f32",
-    "ultra_score_rows_backward_f32",
-    "ultra_gather_boundary_rows_f32",
-    "ultra_relcsr_coalesce_temp_bytes",
-    "ultra_relcsr_coalesce",
-    "ultra_relcsr_plan_temp_bytes",
-    "ultra_relcsr_plan",
-    "ultra_relcsr_dense_bytes",
-    "ultra_relcsr_dense",
-    "ultra_relation_graph_marks",
-    "ultra_calibrate_gather_f32",
-    "ultra_first_layer_sparse_train_f32",
-    "ultra_first_layer_epilogue_backward_workspace",
-    "ultra_first_layer_epilogue_backward_f32",
-    "ultra_column_sum_blocks",
-    "ultra_column_sum_f32",
-    "ultra_dense_layer_supported",
-    "ultra_dense_layer_forward_f32",
-    "ultra_layer_forward_supported",
-    "ultra_layer_forward_f32",
-    "ultra_second_layer_sources",
-    "ultra_layer_forward_sources_f32",
-    "ultra_layer_score_supported",
-    "ultra_layer_score_forward_f32",
-    "ultra_rspmm_rotate_forward_f32",
-    "ultra_rspmm_rotate_backward_f32",
-)
+# The binding as data: exported function of include/ultra_rspmm.h -> (restype, argtypes).  load() applies it;
+# tests/test_host_logic.py compares every row's argument count and kinds with the header's prototype.
+vp, i64, i32, sz, f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
+seg = ctypes.POINTER(UltraSegments)
+SIGNATURES = {
+    "ultra_rspmm_abi_version": (i32, []),
+    "ultra_segments_bytes": (sz, []),
+    "ultra_rspmm_status_string": (ctypes.c_char_p, [i32]),
+    "ultra_rspmm_last_hip_error": (i32, []),
+    "ultra_rspmm_device_info": (i32, [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.c_char_p, sz]),
+    "ultra_rspmm_profile_next": (i32, [vp, vp]),
+    "ultra_rspmm_event_create": (i32, [ctypes.POINTER(vp)]),
+    "ultra_rspmm_event_destroy": (i32, [vp]),
+    "ultra_rspmm_event_elapsed_ms": (i32, [vp, vp, ctypes.POINTER(f32)]),
+    "ultra_rspmm_force_general_path": (i32, [i32]),
+    "ultra_rspmm_reserve_cus": (i32, [i32]),
+    "ultra_rspmm_workspace_bytes": (sz, [seg, i64]),
+    "ultra_rspmm_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_fwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_forward_boundary_f32": (i32, [seg, vp, vp, vp, vp, i64, vp, vp, sz, i64, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_frontier_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp]),
+    "ultra_first_layer_sparse_supported": (i32, [i64, i64, i64]),
+    "ultra_first_layer_sparse_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp, i64, i64, vp, i64,
+                                          i64, vp]),
+    "ultra_rspmm_backward_boundary_rows_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, vp]),
+    "ultra_rspmm_backward_boundary_rows_workspace": (sz, [i64]),
+    "ultra_rspmm_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_backward_accumulate_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]),
+    "ultra_beam_search_step_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]),
+    "ultra_rspmm_backward_active_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp, i64, vp, vp]),
+    "ultra_node_bitmap": (i32, [vp, i64, i64, i64, vp, vp]),
+    "ultra_rspmm_drelation_boundary_f32": (i32, [seg, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, vp]),
+    "ultra_combine_forward_f32": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, i64, i64, vp]),
+    "ultra_combine_forward_boundary_f32": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, f32, i32, i32, vp, i64, i64, vp]),
+    "ultra_combine_backward_waves": (i32, [i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+    "ultra_combine_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "ultra_combine_dxdu_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, vp]),
+    "ultra_combine_backward_fused_waves": (i32, [i32, i64, ctypes.POINTER(i32)]),
+    "ultra_combine_backward_fused_f32": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, i64,
+                                              i64, i64, vp]),
+    "ultra_linear_forward_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, vp]),
+    "ultra_score_forward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "ultra_relation_project_f32": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
+    "ultra_relation_project_backward_blocks": (i32, [i32, i64, i64, i64, vp]),
+    "ultra_relation_project_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, vp]),
+    "ultra_filtered_rank": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "ultra_filtered_rank_keys": (i32, [vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
+    "ultra_strict_negative": (i32, [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "ultra_edge_removal_weights": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
+    "ultra_edge_removal_marks": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "ultra_prepare_queries": (i32, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "ultra_relation_stack_inputs": (i32, [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "ultra_statistics_blocks": (i32, [i64]),
+    "ultra_statistics_f32": (i32, [vp, i64, vp, i64, i64, vp, vp, vp]),
+    "ultra_bce_adversarial_f32": (i32, [vp, i64, i64, f32, vp, vp, vp]),
+    "ultra_candidate_tiles": (i32, [vp, i64, i64, i64, i64, vp, vp]),
+    "ultra_score_rows_forward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "ultra_score_rows_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp]),
+    "ultra_gather_boundary_rows_f32": (i32, [vp, vp, i64, vp, vp]),
+    "ultra_relcsr_coalesce_temp_bytes": (sz, [i64]),
+    "ultra_relcsr_coalesce": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i32), vp,
+                                   sz, vp]),
+    "ultra_relcsr_plan_temp_bytes": (sz, [i64, i64, i64]),
+    "ultra_relcsr_plan": (i32, [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64,
+                               ctypes.POINTER(i64), vp, sz, vp]),
+    "ultra_relcsr_dense_bytes": (sz, [i64, i64, i32]),
+    "ultra_relcsr_dense": (i32, [seg, i64, i64, i32, vp, vp]),
+    "ultra_relation_graph_marks": (i32, [vp, vp, vp, vp, i64, i64, vp, vp]),
+    "ultra_calibrate_gather_f32": (i32, [vp, i64, vp, i64, vp, ctypes.POINTER(i64), vp]),
+    "ultra_first_layer_sparse_train_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, i64, i64,
+                                                vp, i64, i64, vp]),
+    "ultra_first_layer_epilogue_backward_workspace": (sz, [i32, i64]),
+    "ultra_first_layer_epilogue_backward_f32": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                     sz, i64, vp]),
+    "ultra_column_sum_blocks": (i32, []),
+    "ultra_column_sum_f32": (i32, [vp, i64, vp, vp, vp, vp]),
+    "ultra_dense_layer_supported": (i32, [seg, i64]),
+    "ultra_dense_layer_forward_f32": (i32, [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
+    "ultra_layer_forward_supported": (i32, [seg, i64, i64]),
+    "ultra_layer_forward_f32": (i32, [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, i64, vp]),
+    "ultra_second_layer_sources": (i32, [vp, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp, vp]),
+    "ultra_layer_forward_sources_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, i64, vp]),
+    "ultra_layer_score_supported": (i32, [seg, i64, i64]),
+    "ultra_layer_score_forward_f32": (i32, [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ultra_rspmm_rotate_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]),
+    "ultra_rspmm_rotate_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 _lib = None
 
@@ -157,168 +170,8 @@ def load():
     if missing:
         raise UltraLibraryError("%s lacks symbols %s" % (LIB_PATH, missing))
 
-    vp, i64, i32, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
-    seg = ctypes.POINTER(UltraSegments)
-    lib.ultra_rspmm_abi_version.restype = i32
-    lib.ultra_rspmm_abi_version.argtypes = []
-    lib.ultra_layer_forward_supported.restype = i32
-    lib.ultra_layer_forward_supported.argtypes = [seg, i64, i64]
-    lib.ultra_layer_forward_f32.restype = i32
-    lib.ultra_layer_forward_f32.argtypes = [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, i64, vp]
-    lib.ultra_second_layer_sources.restype = i32
-    lib.ultra_second_layer_sources.argtypes = [vp, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp, vp]
-    lib.ultra_layer_forward_sources_f32.restype = i32
-    lib.ultra_layer_forward_sources_f32.argtypes = [seg, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, i64, vp]
-    lib.ultra_layer_score_supported.restype = i32
-    lib.ultra_layer_score_supported.argtypes = [seg, i64, i64]
-    lib.ultra_layer_score_forward_f32.restype = i32
-    lib.ultra_layer_score_forward_f32.argtypes = [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, vp, vp,
-                                                  vp, vp, vp, i64, vp]
-    lib.ultra_relation_graph_marks.restype = i32
-    lib.ultra_relation_graph_marks.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp]
-    lib.ultra_segments_bytes.restype = sz
-    lib.ultra_segments_bytes.argtypes = []
-    lib.ultra_rspmm_status_string.restype = ctypes.c_char_p
-    lib.ultra_rspmm_status_string.argtypes = [i32]
-    lib.ultra_rspmm_last_hip_error.restype = i32
-    lib.ultra_rspmm_last_hip_error.argtypes = []
-    lib.ultra_rspmm_device_info.restype = i32
-    lib.ultra_rspmm_device_info.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.c_char_p, sz]
-    lib.ultra_rspmm_profile_next.restype = i32
-    lib.ultra_rspmm_profile_next.argtypes = [vp, vp]
-    lib.ultra_rspmm_event_create.restype = i32
-    lib.ultra_rspmm_event_create.argtypes = [ctypes.POINTER(vp)]
-    lib.ultra_rspmm_event_destroy.restype = i32
-    lib.ultra_rspmm_event_destroy.argtypes = [vp]
-    lib.ultra_rspmm_event_elapsed_ms.restype = i32
-    lib.ultra_rspmm_event_elapsed_ms.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
-    lib.ultra_rspmm_force_general_path.restype = i32
-    lib.ultra_rspmm_force_general_path.argtypes = [i32]
-    lib.ultra_rspmm_reserve_cus.restype = i32
-    lib.ultra_rspmm_reserve_cus.argtypes = [i32]
-    lib.ultra_rspmm_workspace_bytes.restype = sz
-    lib.ultra_rspmm_workspace_bytes.argtypes = [seg, i64]
-    lib.ultra_rspmm_forward_f32.restype = i32
-    lib.ultra_rspmm_forward_f32.argtypes = [seg, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, i32, vp]
-    lib.ultra_rspmm_fwd_f32.restype = i32
-    lib.ultra_rspmm_fwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp]
-    lib.ultra_rspmm_forward_boundary_f32.restype = i32
-    lib.ultra_rspmm_forward_boundary_f32.argtypes = [seg, vp, vp, vp, vp, i64, vp, vp, sz, i64, i64, i64, i32, i32, vp]
-    lib.ultra_rspmm_backward_boundary_rows_f32.restype = i32
-    lib.ultra_rspmm_backward_boundary_rows_f32.argtypes = [seg, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, vp]
-    lib.ultra_rspmm_backward_boundary_rows_workspace.restype = sz
-    lib.ultra_rspmm_backward_boundary_rows_workspace.argtypes = [i64]
-    lib.ultra_rspmm_frontier_f32.restype = i32
-    lib.ultra_rspmm_frontier_f32.argtypes = [seg, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, vp]
-    lib.ultra_first_layer_sparse_supported.restype = i32
-    lib.ultra_first_layer_sparse_supported.argtypes = [i64, i64, i64]
-    lib.ultra_first_layer_sparse_f32.restype = i32
-    lib.ultra_first_layer_sparse_f32.argtypes = [seg, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, i64, i64,
-                                                 vp, i64, i64, vp]
-    lib.ultra_rspmm_backward_f32.restype = i32
-    lib.ultra_rspmm_backward_f32.argtypes = [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]
-    lib.ultra_rspmm_backward_accumulate_f32.restype = i32
-    lib.ultra_rspmm_backward_accumulate_f32.argtypes = [seg, seg, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32,
-                                                        i32, vp]
-    lib.ultra_rspmm_backward_active_f32.restype = i32
-    lib.ultra_rspmm_backward_active_f32.argtypes = [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp, i64, vp, vp]
-    lib.ultra_node_bitmap.restype = i32
-    lib.ultra_node_bitmap.argtypes = [vp, i64, i64, i64, vp, vp]
-    lib.ultra_rspmm_drelation_boundary_f32.restype = i32
-    lib.ultra_rspmm_drelation_boundary_f32.argtypes = [seg, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, vp]
-    lib.ultra_rspmm_backward_weight_f32.restype = i32
-    lib.ultra_rspmm_backward_weight_f32.argtypes = [seg, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
-    lib.ultra_beam_search_step_f32.restype = i32
-    lib.ultra_beam_search_step_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]
-    lib.ultra_combine_forward_f32.restype = i32
-    lib.ultra_combine_forward_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, i64, i64, vp]
-    lib.ultra_combine_forward_boundary_f32.restype = i32
-    lib.ultra_combine_forward_boundary_f32.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, i64, i64, vp]
-    lib.ultra_prepare_queries.restype = i32
-    lib.ultra_prepare_queries.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]
-    lib.ultra_statistics_blocks.restype = i32
-    lib.ultra_statistics_blocks.argtypes = [i64]
-    lib.ultra_statistics_f32.restype = i32
-    lib.ultra_statistics_f32.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
-    lib.ultra_gather_boundary_rows_f32.restype = i32
-    lib.ultra_gather_boundary_rows_f32.argtypes = [vp, vp, i64, vp, vp]
-    lib.ultra_score_rows_forward_f32.restype = i32
-    lib.ultra_score_rows_forward_f32.argtypes = [vp] * 10 + [i64, i64, vp]
-    lib.ultra_score_rows_backward_f32.restype = i32
-    lib.ultra_score_rows_backward_f32.argtypes = [vp] * 16 + [i64, i64, i64, vp]
-    lib.ultra_candidate_tiles.restype = i32
-    lib.ultra_candidate_tiles.argtypes = [vp, i64, i64, i64, i64, vp, vp]
-    lib.ultra_bce_adversarial_f32.restype = i32
-    lib.ultra_bce_adversarial_f32.argtypes = [vp, i64, i64, ctypes.c_float, vp, vp, vp]
-    lib.ultra_relation_stack_inputs.restype = i32
-    lib.ultra_relation_stack_inputs.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp]
-    lib.ultra_combine_backward_waves.restype = i32
-    lib.ultra_combine_backward_waves.argtypes = [i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.ultra_combine_backward_f32.restype = i32
-    lib.ultra_combine_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp]
-    lib.ultra_combine_dxdu_f32.restype = i32
-    lib.ultra_combine_dxdu_f32.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp]
-    lib.ultra_combine_backward_fused_waves.restype = i32
-    lib.ultra_combine_backward_fused_waves.argtypes = [i32, i64, ctypes.POINTER(i32)]
-    lib.ultra_combine_backward_fused_f32.restype = i32
-    lib.ultra_combine_backward_fused_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp,
-                                                     vp, vp, sz, vp, i64, i64, i64, vp]
-    lib.ultra_linear_forward_f32.restype = i32
-    lib.ultra_linear_forward_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp]
-    lib.ultra_score_forward_f32.restype = i32
-    lib.ultra_score_forward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]
-    lib.ultra_relation_project_f32.restype = i32
-    lib.ultra_relation_project_f32.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]
-    lib.ultra_relation_project_backward_blocks.restype = i32
-    lib.ultra_relation_project_backward_blocks.argtypes = [i32, i64, i64, i64, vp]
-    lib.ultra_relation_project_backward_f32.restype = i32
-    lib.ultra_relation_project_backward_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, vp]
-    lib.ultra_filtered_rank.restype = i32
-    lib.ultra_filtered_rank.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp]
-    lib.ultra_filtered_rank_keys.restype = i32
-    lib.ultra_filtered_rank_keys.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]
-    lib.ultra_strict_negative.restype = i32
-    lib.ultra_strict_negative.argtypes = [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]
-    lib.ultra_edge_removal_weights.restype = i32
-    lib.ultra_edge_removal_weights.argtypes = [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]
-    lib.ultra_edge_removal_marks.restype = i32
-    lib.ultra_edge_removal_marks.argtypes = [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]
-    lib.ultra_relcsr_coalesce_temp_bytes.restype = sz
-    lib.ultra_relcsr_coalesce_temp_bytes.argtypes = [i64]
-    lib.ultra_relcsr_coalesce.restype = i32
-    lib.ultra_relcsr_coalesce.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp,
-                                          ctypes.POINTER(i64), ctypes.POINTER(i32), vp, sz, vp]
-    lib.ultra_relcsr_plan_temp_bytes.restype = sz
-    lib.ultra_relcsr_plan_temp_bytes.argtypes = [i64, i64, i64]
-    lib.ultra_relcsr_plan.restype = i32
-    lib.ultra_relcsr_plan.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, i32, i32, i64, i64, i64, vp, i64, vp, i64,
-                                      vp, i64, ctypes.POINTER(i64), vp, sz, vp]
-    lib.ultra_relcsr_dense_bytes.restype = sz
-    lib.ultra_relcsr_dense_bytes.argtypes = [i64, i64, i32]
-    lib.ultra_relcsr_dense.restype = i32
-    lib.ultra_relcsr_dense.argtypes = [seg, i64, i64, i32, vp, vp]
-    lib.ultra_first_layer_sparse_train_f32.restype = i32
-    lib.ultra_first_layer_sparse_train_f32.argtypes = [seg, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp,
-                                                       vp, i64, i64, vp, i64, i64, vp]
-    lib.ultra_first_layer_epilogue_backward_workspace.restype = sz
-    lib.ultra_first_layer_epilogue_backward_workspace.argtypes = [i32, i64]
-    lib.ultra_first_layer_epilogue_backward_f32.restype = i32
-    lib.ultra_first_layer_epilogue_backward_f32.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp, vp,
-                                                            vp, vp, vp, vp, sz, i64, vp]
-    lib.ultra_column_sum_blocks.restype = i32
-    lib.ultra_column_sum_blocks.argtypes = []
-    lib.ultra_column_sum_f32.restype = i32
-    lib.ultra_column_sum_f32.argtypes = [vp, i64, vp, vp, vp, vp]
-    lib.ultra_dense_layer_supported.restype = i32
-    lib.ultra_dense_layer_supported.argtypes = [seg, i64]
-    lib.ultra_dense_layer_forward_f32.restype = i32
-    lib.ultra_dense_layer_forward_f32.argtypes = [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp, vp]
-    lib.ultra_calibrate_gather_f32.restype = i32
-    lib.ultra_calibrate_gather_f32.argtypes = [vp, i64, vp, i64, vp, ctypes.POINTER(i64), vp]
-    lib.ultra_rspmm_rotate_forward_f32.restype = i32
-    lib.ultra_rspmm_rotate_forward_f32.argtypes = [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]
-    lib.ultra_rspmm_rotate_backward_f32.restype = i32
-    lib.ultra_rspmm_rotate_backward_f32.argtypes = [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     if lib.ultra_rspmm_abi_version() != ABI_VERSION:
         raise UltraLibraryError("ABI mismatch: library %d, binding %d" % (lib.ultra_rspmm_abi_version(), ABI_VERSION))
     if lib.ultra_segments_bytes() != ctypes.sizeof(UltraSegments):
@@ -336,6 +189,24 @@ def check(status):
         if status == 5:
             msg += " [hipError_t=%d]" % lib.ultra_rspmm_last_hip_error()
         raise RuntimeError("libultra_rspmm: %s" % msg)
+
+
+def ptr(tensor):
+    """The device address of ``tensor`` as it is (``data_ptr()``: never a copy), NULL for ``None``."""
+    return None if tensor is None else tensor.data_ptr()
+
+
+def launch(device, name, *args):
+    """Run the exported launch ``name`` on ``device``: tensors among ``args`` become their ``data_ptr()`` and ``None`` NULL, the
+    current HIP stream is appended and a non-zero status raises (:func:`check`).  A tensor is passed as it is -- an output that
+    got copied here would be written into a temporary and lost -- so the caller makes its inputs contiguous and passes the
+    copies, which ``args`` keeps alive until the C call has returned."""
+    entry = getattr(load(), name)
+    if len(args) + 1 != len(entry.argtypes):        # (ctypes itself lets surplus arguments of a cdecl function pass)
+        raise TypeError("%s takes %d arguments and the stream, got %d" % (name, len(entry.argtypes) - 1, len(args)))
+    with torch.cuda.device(device):
+        check(entry(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                    torch.cuda.current_stream().cuda_stream))
 
 
 def device_info(device=0):

@@ -15,6 +15,8 @@ ranking and sampling) are MI355X-only and raise on CPU tensors.  Without the nat
 is no Python or PyTorch fallback, and the CPU oracle under ``oracle/`` is test infrastructure that is never imported here.
 """
 import collections
+import ctypes
+import os
 
 import torch
 
@@ -82,8 +84,45 @@ def _check_dense(csr, relation, input, require_hip=True):
                            % (csr.device, relation.device, input.device))
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+# The one way across the C boundary (``_lib.launch``): tensors -> pointers, None -> NULL, current stream, status check.
+_launch, _ptr = _lib.launch, _lib.ptr
+
+
+def _env_bool(name, default):
+    """An ``ULTRA_*`` switch: on unless set to ``0`` where ``default`` is True, off unless set to ``1`` where it is False."""
+    return os.environ.get(name, "1") != "0" if default else os.environ.get(name, "0") == "1"
+
+
+def _env_float(name, default):
+    return float(os.environ.get(name, default))
+
+
+def _env_int(name, default):
+    return int(os.environ.get(name, default))
+
+
+def _not_fp32_on(device, tensors):
+    """True unless every tensor is fp32 on the HIP device ``device``."""
+    return any(t.dtype != torch.float32 or not t.is_cuda or t.device != device for t in tensors)
+
+
+def _epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut=None):
+    """The argument run ``weight, bias, ln_weight, ln_bias, ln_eps, relu[, shortcut]`` of the epilogue kernels: the parameters
+    contiguous, both LayerNorm vectors NULL without ``ln_weight``.  ``shortcut=None``: the entry has no such argument (the split
+    three-kernel backward)."""
+    has_ln = ln_weight is not None
+    run = (weight.contiguous(), bias.contiguous(), ln_weight.contiguous() if has_ln else None,
+           ln_bias.contiguous() if has_ln else None, float(ln_eps), int(bool(relu)))
+    return run if shortcut is None else run + (int(bool(shortcut)),)
+
+
+def _pointer_array(tensors):
+    """``void *[len(tensors)]`` of the tensors' addresses (NULL for ``None``); the caller keeps the tensors alive."""
+    return (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
+
+
+def _plan(seg):
+    return None if seg is None else seg.pointer
 
 
 def _workspace(seg, F, device):
@@ -92,6 +131,52 @@ def _workspace(seg, F, device):
         return None, 0
     ws = torch.empty(n, dtype=torch.float32, device=device)
     return ws, n * 4
+
+
+def _backward_workspace(by_src, by_rel, F, device):
+    """``(workspace, bytes)`` of a backward over the plans in use (``None`` = that gradient is not wanted)."""
+    n_ws = max(by_src.workspace_rows if by_src is not None else 0, by_rel.workspace_rows if by_rel is not None else 0) * F
+    return (torch.empty(n_ws, dtype=torch.float32, device=device) if n_ws else None), n_ws * 4
+
+
+def _check_boundary_epilogue(out, add_rows, boundary, block=None):
+    """The boundary epilogue of ``rspmm_forward`` / ``rotate_rspmm_forward`` validated against the output ``out``:
+    ``(add_rows, b_node, b_value)``, the dense form and the sparse form's values contiguous.  ``block`` (rotate): the value
+    rows are exactly that wide."""
+    F = out.shape[1]
+    both = "give the boundary either dense (add_rows) or sparse (boundary), not both"
+    if block is not None and add_rows is not None and boundary is not None:     # (rotate reports this before a bad add_rows)
+        raise RuntimeError(both)
+    if add_rows is not None:
+        add_rows = add_rows.contiguous()
+        if add_rows.shape != out.shape or add_rows.dtype != torch.float32 or add_rows.device != out.device:
+            raise RuntimeError("add_rows must be fp32 %s on %s" % (tuple(out.shape), out.device))
+    b_node = b_value = None
+    if boundary is not None:
+        if add_rows is not None:
+            raise RuntimeError(both)
+        b_node, b_value = boundary
+        b_value = b_value.contiguous()
+        if (b_node.dtype != torch.int32 or b_value.dtype != torch.float32 or b_node.dim() != 1 or b_value.dim() != 2
+                or (b_value.shape[0] != b_node.shape[0] if block is None else b_value.shape != (b_node.shape[0], block))
+                or b_value.numel() != F or b_node.device != out.device
+                or b_value.device != out.device or not b_node.is_contiguous()):
+            width = "D" if block is None else "%d" % block
+            raise RuntimeError("boundary must be (int32 (B,), fp32 (B, %s)) with B * %s == %d on %s" % (width, width, F, out.device))
+    return add_rows, b_node, b_value
+
+
+def _check_d_input_add(d_input_add, input, sum, need_input):
+    if d_input_add is not None and (not need_input or sum != "add" or not d_input_add.is_contiguous()
+                                    or d_input_add.shape != input.shape or d_input_add.dtype != torch.float32):
+        raise RuntimeError("d_input_add: contiguous fp32 tensor of input's shape, sum aggregation, with need_input")
+
+
+def _boundary_value_grad(output_grad, b_node):
+    """Gradient of a sparse boundary's values: row ``b_node[q]`` of query block ``q`` of ``output_grad``."""
+    n_query = b_node.shape[0]
+    blocks = output_grad.view(output_grad.shape[0], n_query, -1)
+    return blocks[b_node.long(), torch.arange(n_query, device=output_grad.device)]
 
 
 def rspmm_forward(csr, relation, input, sum="add", mul="mul", add_rows=None, boundary=None):
@@ -104,40 +189,20 @@ def rspmm_forward(csr, relation, input, sum="add", mul="mul", add_rows=None, bou
     relation, input = relation.contiguous(), input.contiguous()
     F = input.shape[1]
     out = torch.empty(csr.shape[0], F, dtype=torch.float32, device=input.device)
-    if add_rows is not None:
-        add_rows = add_rows.contiguous()
-        if add_rows.shape != out.shape or add_rows.dtype != torch.float32 or add_rows.device != out.device:
-            raise RuntimeError("add_rows must be fp32 %s on %s" % (tuple(out.shape), out.device))
-    if boundary is not None:
-        if add_rows is not None:
-            raise RuntimeError("give the boundary either dense (add_rows) or sparse (boundary), not both")
-        b_node, b_value = boundary
-        b_value = b_value.contiguous()
-        if (b_node.dtype != torch.int32 or b_value.dtype != torch.float32 or b_node.dim() != 1 or b_value.dim() != 2
-                or b_value.shape[0] != b_node.shape[0] or b_value.numel() != F or b_node.device != out.device
-                or b_value.device != out.device or not b_node.is_contiguous()):
-            raise RuntimeError("boundary must be (int32 (B,), fp32 (B, D)) with B * D == %d on %s" % (F, out.device))
+    add_rows, b_node, b_value = _check_boundary_epilogue(out, add_rows, boundary)
     if out.numel() == 0:
         return out
     seg = csr.fwd
     if _torch_ext.binding() == "torch":         # through the dispatcher: torch.ops.ultra_mi (csrc/torch_ext.cpp)
-        b_node_, b_value_ = (boundary[0], b_value) if boundary is not None else (None, None)
-        return _torch_ext.load().rspmm_plan_fwd(seg.plan_tensor, relation, input, add_rows, b_node_, b_value_,
+        return _torch_ext.load().rspmm_plan_fwd(seg.plan_tensor, relation, input, add_rows, b_node, b_value,
                                                 csr.shape[1], sum_op, mul_op)
-    lib = _lib.load()
     ws, ws_bytes = _workspace(seg, F, input.device)
     if boundary is not None:
-        with torch.cuda.device(input.device):
-            _lib.check(lib.ultra_rspmm_forward_boundary_f32(
-                seg.pointer, relation.data_ptr(), input.data_ptr(), b_node.data_ptr(), b_value.data_ptr(),
-                b_value.shape[1], out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, csr.shape[1],
-                csr.shape[2], F, sum_op, mul_op, _stream()))
+        _launch(input.device, "ultra_rspmm_forward_boundary_f32", seg.pointer, relation, input, b_node, b_value,
+                b_value.shape[1], out, ws, ws_bytes, csr.shape[1], csr.shape[2], F, sum_op, mul_op)
         return out
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_rspmm_forward_f32(
-            seg.pointer, relation.data_ptr(), input.data_ptr(), add_rows.data_ptr() if add_rows is not None else None,
-            out.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, csr.shape[1], csr.shape[2], F, sum_op,
-            mul_op, _stream()))
+    _launch(input.device, "ultra_rspmm_forward_f32", seg.pointer, relation, input, add_rows, out, ws, ws_bytes, csr.shape[1],
+            csr.shape[2], F, sum_op, mul_op)
     return out
 
 
@@ -164,12 +229,9 @@ def rspmm_forward_csr(row_ptr, src, rel, weight, relation, input, sum="add", mul
     out = torch.empty(n_rows, F, dtype=torch.float32, device=input.device)
     if out.numel() == 0:
         return out
-    lib = _lib.load()
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_rspmm_fwd_f32(
-            row_ptr.contiguous().data_ptr(), src.contiguous().data_ptr(), rel.contiguous().data_ptr(),
-            weight.contiguous().data_ptr() if weight is not None else None, relation.data_ptr(), input.data_ptr(),
-            out.data_ptr(), n_rows, n_edges, relation.shape[0], F, sum_op, mul_op, _stream()))
+    _launch(input.device, "ultra_rspmm_fwd_f32", row_ptr.contiguous(), src.contiguous(), rel.contiguous(),
+            weight.contiguous() if weight is not None else None, relation, input, out, n_rows, n_edges, relation.shape[0], F,
+            sum_op, mul_op)
     return out
 
 
@@ -203,16 +265,13 @@ def rspmm_frontier(csr, relation, boundary):
     if out.numel() == 0:
         return out
     src_ptr, fwd_rank = csr.frontier_index
-    lib = _lib.load()
-    with torch.cuda.device(relation.device):
-        _lib.check(lib.ultra_rspmm_frontier_f32(
-            csr.by_src.pointer, src_ptr.data_ptr(), fwd_rank.data_ptr(), relation.data_ptr(), b_node.data_ptr(),
-            b_value.data_ptr(), 64, out.data_ptr(), n_dst, n_rel, F, _stream()))
+    _launch(relation.device, "ultra_rspmm_frontier_f32", csr.by_src.pointer, src_ptr, fwd_rank, relation, b_node, b_value, 64,
+            out, n_dst, n_rel, F)
     return out
 
 
 # Sparse first layer in inference (ultra_first_layer_sparse_f32).  ULTRA_SPARSE_FIRST_LAYER=0: frontier kernel + dense epilogue.
-SPARSE_FIRST_LAYER = __import__("os").environ.get("ULTRA_SPARSE_FIRST_LAYER", "1") != "0"
+SPARSE_FIRST_LAYER = _env_bool("ULTRA_SPARSE_FIRST_LAYER", True)
 # ... from this many output rows (nodes x queries) on: on a small dense graph a hub's out-edges reach most nodes, the list is
 # most of the rows and its indexed epilogue loses to the dense one (S-codexs, 65 k rows: 17 us against 13; S-fb15k237, 465 k rows:
 # 24 us against 108 on the hub-heaviest batch)
@@ -223,9 +282,27 @@ SPARSE_FIRST_LAYER_MIN_ROWS = 1 << 17
 # n_query * (max_runs + 1) slots.  The density gates look at the degree-weighted mean; one hub that reaches most of the nodes in an
 # otherwise sparse graph would pass them and allocate several (N, B, 64)-sized scratch tensors per step: the sparse
 # forms are taken only where the longest list is at most this fraction of the nodes (ULTRA_SPARSE_FIRST_LAYER_MAX_LIST).
-SPARSE_FIRST_LAYER_MAX_LIST = float(__import__("os").environ.get("ULTRA_SPARSE_FIRST_LAYER_MAX_LIST", "1.0"))
+SPARSE_FIRST_LAYER_MAX_LIST = _env_float("ULTRA_SPARSE_FIRST_LAYER_MAX_LIST", 1.0)
 # ... and, in training, where the backward's compacted workspace (5 rows of 64 floats per slot) stays within this many bytes
-SPARSE_FIRST_LAYER_TRAIN_MAX_BYTES = int(__import__("os").environ.get("ULTRA_SPARSE_FIRST_LAYER_TRAIN_MAX_BYTES", str(2 << 30)))
+SPARSE_FIRST_LAYER_TRAIN_MAX_BYTES = _env_int("ULTRA_SPARSE_FIRST_LAYER_TRAIN_MAX_BYTES", 2 << 30)
+
+
+def _first_layer_arguments(csr, relation, b_node, b_value):
+    """What both sparse first-layer entries pass around their epilogue run: ``(device, head, tail, out, row_list, list_offset)``
+    -- ``head`` the frontier index and the operands, ``tail`` the freshly allocated output, row list and list offsets with
+    their sizes (``ultra_first_layer_sparse_f32`` / ``..._train_f32``)."""
+    n_dst, _, n_rel = csr.shape
+    n_query = b_node.shape[0]
+    relation = relation.contiguous()
+    dev = relation.device
+    src_ptr, fwd_rank = csr.frontier_index
+    run_prefix, max_runs = csr.frontier_runs
+    out = torch.empty(n_dst, n_query, 64, dtype=torch.float32, device=dev)
+    row_list = torch.empty(n_query * (max_runs + 1), dtype=torch.int32, device=dev)
+    list_offset = torch.empty(n_query + 1, dtype=torch.int32, device=dev)
+    head = (csr.by_src.pointer, src_ptr, fwd_rank, run_prefix, relation, b_node, b_value, n_query)
+    tail = (out, row_list, row_list.numel(), int(max_runs), list_offset, n_dst, n_rel)
+    return dev, head, tail, out, row_list, list_offset
 
 
 def first_layer_forward(csr, relation, boundary, weight, bias, ln_weight=None, ln_bias=None, ln_eps=1e-5, relu=True,
@@ -250,24 +327,12 @@ def first_layer_forward(csr, relation, boundary, weight, bias, ln_weight=None, l
     tensors = [relation, b_value, weight, bias] + ([ln_weight, ln_bias] if ln_weight is not None else [])
     if (relation.dim() != 2 or tuple(relation.shape) != (n_rel, F) or tuple(b_value.shape) != (n_query, 64) or b_node.dtype != torch.int32
             or not b_node.is_contiguous() or tuple(weight.shape) != (64, 128)
-            or any(t.dtype != torch.float32 or not t.is_cuda or t.device != relation.device for t in tensors)
+            or _not_fp32_on(relation.device, tensors)
             or b_node.device != relation.device or csr.device != relation.device):
         raise RuntimeError("first_layer_forward: relation fp32 (%d, %d), boundary (int32 (Q,), fp32 (Q, 64)), a (64, 128) weight, "
                            "all on one HIP device" % (n_rel, F))
-    relation = relation.contiguous()
-    dev = relation.device
-    src_ptr, fwd_rank = csr.frontier_index
-    run_prefix, max_runs = csr.frontier_runs
-    out = torch.empty(n_dst, n_query, 64, dtype=torch.float32, device=dev)
-    row_list = torch.empty(n_query * (max_runs + 1), dtype=torch.int32, device=dev)
-    list_offset = torch.empty(n_query + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_first_layer_sparse_f32(
-            csr.by_src.pointer, src_ptr.data_ptr(), fwd_rank.data_ptr(), run_prefix.data_ptr(), relation.data_ptr(),
-            b_node.data_ptr(), b_value.data_ptr(), n_query, weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-            ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-            out.data_ptr(), row_list.data_ptr(), row_list.numel(), int(max_runs), list_offset.data_ptr(), n_dst, n_rel, _stream()))
+    dev, head, tail, out, row_list, list_offset = _first_layer_arguments(csr, relation, b_node, b_value)
+    _launch(dev, "ultra_first_layer_sparse_f32", *head, *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), *tail)
     if want_list:           # (out, the rows that differ from the layer's constant row, their count on the device): second_layer_sources
         return out, row_list, list_offset[n_query:]
     return out
@@ -275,10 +340,10 @@ def first_layer_forward(csr, relation, boundary, weight, bias, ln_weight=None, l
 
 # First layer in TRAINING sparse end to end (csrc/first_layer_train.inc).  ULTRA_SPARSE_FIRST_LAYER_TRAIN=0: the dense epilogue forward
 # and backward over all N x B rows (same gradients up to the association of three 64-float sums).
-SPARSE_FIRST_LAYER_TRAIN = __import__("os").environ.get("ULTRA_SPARSE_FIRST_LAYER_TRAIN", "1") != "0"
+SPARSE_FIRST_LAYER_TRAIN = _env_bool("ULTRA_SPARSE_FIRST_LAYER_TRAIN", True)
 # ... on graphs where a training batch's boundary nodes (heads of sampled edges: hubs are likely) reach at most this fraction of the
 # nodes each (RelCSR.frontier_fraction): the sparse form's cost grows with the listed rows, the dense form's does not.
-SPARSE_FIRST_LAYER_TRAIN_MAX_FRACTION = float(__import__("os").environ.get("ULTRA_SPARSE_FIRST_LAYER_TRAIN_MAX_FRACTION", "0.2"))
+SPARSE_FIRST_LAYER_TRAIN_MAX_FRACTION = _env_float("ULTRA_SPARSE_FIRST_LAYER_TRAIN_MAX_FRACTION", 0.2)
 
 
 def first_layer_train_forward(csr, relation, boundary, weight, bias, ln_weight=None, ln_bias=None, ln_eps=1e-5, relu=True,
@@ -306,37 +371,25 @@ def first_layer_train_forward(csr, relation, boundary, weight, bias, ln_weight=N
     if (tuple(relation.shape) != (n_rel, F) or tuple(b_value.shape) != (n_query, 64) or b_node.dtype != torch.int32
             or not b_node.is_contiguous() or tuple(weight.shape) != (64, 128)):
         return None
-    relation = relation.contiguous()
-    dev = relation.device
-    src_ptr, fwd_rank = csr.frontier_index
-    run_prefix, max_runs = csr.frontier_runs
-    update = torch.empty(n_dst, n_query, 64, dtype=torch.float32, device=dev)
-    out = torch.empty(n_dst, n_query, 64, dtype=torch.float32, device=dev)
-    row_list = torch.empty(n_query * (max_runs + 1), dtype=torch.int32, device=dev)
-    list_offset = torch.empty(n_query + 1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_first_layer_sparse_train_f32(
-            csr.by_src.pointer, src_ptr.data_ptr(), fwd_rank.data_ptr(), run_prefix.data_ptr(), relation.data_ptr(),
-            b_node.data_ptr(), b_value.data_ptr(), n_query, weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-            ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-            update.data_ptr(), out.data_ptr(), row_list.data_ptr(), row_list.numel(), int(max_runs), list_offset.data_ptr(),
-            n_dst, n_rel, _stream()))
+    update = torch.empty(n_dst, n_query, 64, dtype=torch.float32, device=relation.device)
+    dev, head, tail, out, row_list, list_offset = _first_layer_arguments(csr, relation, b_node, b_value)
+    _launch(dev, "ultra_first_layer_sparse_train_f32", *head, *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut),
+            update, *tail)
     return update, out, row_list, list_offset[n_query:]
 
 
 # Entity layers in inference as ONE launch (rspmm + epilogue, csrc/layer_fused.hip) on plans that run one row per lane group
 # (big graphs: row pointers, no split rows).  ULTRA_FUSED_LAYER=0: the two launches (same bits).
-FUSED_LAYER = __import__("os").environ.get("ULTRA_FUSED_LAYER", "1") != "0"
+FUSED_LAYER = _env_bool("ULTRA_FUSED_LAYER", True)
 # ... and the last layer with the score head inside the same launch (ULTRA_FUSED_SCORE=0: layer launch + score launch)
-FUSED_SCORE = __import__("os").environ.get("ULTRA_FUSED_SCORE", "1") != "0"
+FUSED_SCORE = _env_bool("ULTRA_FUSED_SCORE", True)
 
 
 # The SECOND layer's gathers when the first layer was sparse: all but the listed rows of its input hold one constant vector, so
 # every edge whose source is not listed gathers ONE fixed unlisted row instead (cache hits; same bits).  ULTRA_SECOND_LAYER_SOURCES=0:
 # the plan's own sources.  Taken where the list is at most 1 / 64 of the nodes (beyond that the remapped gathers are DRAM
 # gathers again and the pass over the edges that builds them is pure cost).
-SECOND_LAYER_SOURCES = __import__("os").environ.get("ULTRA_SECOND_LAYER_SOURCES", "1") != "0"
+SECOND_LAYER_SOURCES = _env_bool("ULTRA_SECOND_LAYER_SOURCES", True)
 
 
 def second_layer_sources(csr, row_list, list_count, n_query):
@@ -358,10 +411,8 @@ def second_layer_sources(csr, row_list, list_count, n_query):
     sources = torch.empty(E + slack, dtype=torch.int32, device=dev)
     bitmap = torch.empty((n_src + 31) // 32, dtype=torch.int32, device=dev)
     c_node = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_second_layer_sources(plan.node_a.data_ptr(), E, slack, row_list.data_ptr(), list_count.data_ptr(),
-                                                  row_list.numel(), n_query, n_src, bitmap.data_ptr(), c_node.data_ptr(),
-                                                  sources.data_ptr(), _stream()))
+    _launch(dev, "ultra_second_layer_sources", plan.node_a, E, slack, row_list, list_count, row_list.numel(), n_query, n_src,
+            bitmap, c_node, sources)
     return sources
 
 
@@ -386,7 +437,7 @@ def layer_forward(csr, relation, input, boundary, weight, bias, ln_weight=None, 
     if (ln_weight is not None and ln_bias is None) or any(t.numel() != 64 for t in tensors[3:4 + (2 if ln_weight is not None else 0)]):
         return None                                  # (bias, LayerNorm vectors: 64 entries each -- the kernel reads 64)
     if (tuple(relation.shape) != (n_rel, F) or tuple(weight.shape) != (64, 128)
-            or any(t.dtype != torch.float32 or not t.is_cuda or t.device != input.device for t in tensors)
+            or _not_fp32_on(input.device, tensors)
             or (b_node is not None and (b_node.dtype != torch.int32 or tuple(b_node.shape) != (n_query,) or tuple(b_value.shape) != (n_query, 64)))):
         return None
     relation, input = relation.contiguous(), input.contiguous()
@@ -394,22 +445,12 @@ def layer_forward(csr, relation, input, boundary, weight, bias, ln_weight=None, 
     if sources is not None:
         if sources.dtype != torch.int32 or sources.numel() != plan.node_a.numel() or sources.device != input.device:
             raise RuntimeError("layer_forward: sources must be second_layer_sources() of this plan")
-        with torch.cuda.device(input.device):
-            _lib.check(lib.ultra_layer_forward_sources_f32(
-                plan.pointer, sources.data_ptr(), relation.data_ptr(), input.data_ptr(),
-                b_node.contiguous().data_ptr() if b_node is not None else None,
-                b_value.contiguous().data_ptr() if b_value is not None else None, n_query, weight.contiguous().data_ptr(),
-                bias.contiguous().data_ptr(), ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-                ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-                out.data_ptr(), n_rel, _stream()))
-        return out
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_layer_forward_f32(
-            plan.pointer, relation.data_ptr(), input.data_ptr(), b_node.contiguous().data_ptr() if b_node is not None else None,
-            b_value.contiguous().data_ptr() if b_value is not None else None, n_query, weight.contiguous().data_ptr(),
-            bias.contiguous().data_ptr(), ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-            out.data_ptr(), n_rel, _stream()))
+        entry, lead = "ultra_layer_forward_sources_f32", (plan.pointer, sources)
+    else:
+        entry, lead = "ultra_layer_forward_f32", (plan.pointer,)
+    _launch(input.device, entry, *lead, relation, input, b_node.contiguous() if b_node is not None else None,
+            b_value.contiguous() if b_value is not None else None, n_query,
+            *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), out, n_rel)
     return out
 
 
@@ -435,26 +476,22 @@ def layer_score_forward(csr, relation, input, boundary, weight, bias, ln_weight,
         return None
     if (tuple(relation.shape) != (n_rel, F) or tuple(weight.shape) != (64, 128) or tuple(w1.shape) != (128, 128) or w2.numel() != 128
             or b2.numel() != 1 or tuple(query.shape) != (n_query, 64)
-            or any(t.dtype != torch.float32 or not t.is_cuda or t.device != input.device for t in tensors)
+            or _not_fp32_on(input.device, tensors)
             or (b_node is not None and (b_node.dtype != torch.int32 or tuple(b_node.shape) != (n_query,) or tuple(b_value.shape) != (n_query, 64)))):
         return None
     relation, input = relation.contiguous(), input.contiguous()
     score = torch.empty(n_query, n_src, dtype=torch.float32, device=input.device)
     qbias = torch.empty(n_query, 128, dtype=torch.float32, device=input.device)
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_layer_score_forward_f32(
-            plan.pointer, relation.data_ptr(), input.data_ptr(), b_node.contiguous().data_ptr() if b_node is not None else None,
-            b_value.contiguous().data_ptr() if b_value is not None else None, n_query, weight.contiguous().data_ptr(),
-            bias.contiguous().data_ptr(), ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-            query.contiguous().data_ptr(), w1.contiguous().data_ptr(), b1.contiguous().data_ptr(), w2.contiguous().data_ptr(),
-            b2.contiguous().data_ptr(), qbias.data_ptr(), score.data_ptr(), n_rel, _stream()))
+    _launch(input.device, "ultra_layer_score_forward_f32", plan.pointer, relation, input,
+            b_node.contiguous() if b_node is not None else None, b_value.contiguous() if b_value is not None else None, n_query,
+            *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), query.contiguous(), w1.contiguous(),
+            b1.contiguous(), w2.contiguous(), b2.contiguous(), qbias, score, n_rel)
     return score
 
 
 # Relation-graph layers in inference as ONE launch where the plan carries its dense form (ultra_dense_layer_forward_f32).
 # ULTRA_DENSE_LAYER=0: the dense rspmm and the epilogue as two launches (same bits).
-DENSE_LAYER = __import__("os").environ.get("ULTRA_DENSE_LAYER", "1") != "0"
+DENSE_LAYER = _env_bool("ULTRA_DENSE_LAYER", True)
 
 
 def dense_layer_forward(csr, relation, input, boundary, weight, bias, ln_weight=None, ln_bias=None, ln_eps=1e-5, relu=True,
@@ -477,30 +514,25 @@ def dense_layer_forward(csr, relation, input, boundary, weight, bias, ln_weight=
     tensors = [relation, input, b_value, weight, bias] + ([ln_weight, ln_bias] if ln_weight is not None else [])
     if (tuple(relation.shape) != (4, F) or tuple(b_value.shape) != (n_query, 64) or b_node.dtype != torch.int32
             or not b_node.is_contiguous() or tuple(weight.shape) != (64, 128)
-            or any(t.dtype != torch.float32 or not t.is_cuda or t.device != input.device for t in tensors)
+            or _not_fp32_on(input.device, tensors)
             or b_node.device != input.device or csr.device != input.device):
         raise RuntimeError("dense_layer_forward: input fp32 (N, Q, 64), relation fp32 (4, Q * 64), boundary (int32 (Q,), fp32 "
                            "(Q, 64)), a (64, 128) weight, all on one HIP device")
     relation, input = relation.contiguous(), input.contiguous()
     out = torch.empty_like(input)
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_dense_layer_forward_f32(
-            seg.pointer, relation.data_ptr(), input.data_ptr(), b_node.data_ptr(), b_value.data_ptr(), n_query,
-            weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-            ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)), int(bool(shortcut)),
-            out.data_ptr(), _stream()))
+    _launch(input.device, "ultra_dense_layer_forward_f32", seg.pointer, relation, input, b_node, b_value, n_query,
+            *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), out)
     return out
 
 
 # Training: the backward's gathers skipped where the caller knows the gradient (last layer) or the input (first layer) rows are
 # zero -- see rspmm_backward(active_dst=, active_src=).  ULTRA_ACTIVE_ROW_BACKWARD=0: every edge gathers.
-ACTIVE_ROW_BACKWARD = __import__("os").environ.get("ULTRA_ACTIVE_ROW_BACKWARD", "1") != "0"
+ACTIVE_ROW_BACKWARD = _env_bool("ULTRA_ACTIVE_ROW_BACKWARD", True)
 
 
 # d_relation of the first layer from the boundary nodes' out-edges alone (ultra_rspmm_drelation_boundary_f32) instead of the masked
 # walk over every edge of the graph; ULTRA_BOUNDARY_DRELATION=0: the masked walk.
-BOUNDARY_DRELATION = __import__("os").environ.get("ULTRA_BOUNDARY_DRELATION", "1") != "0"
+BOUNDARY_DRELATION = _env_bool("ULTRA_BOUNDARY_DRELATION", True)
 
 
 def rspmm_drelation_boundary(csr, input, output_grad, b_node):
@@ -521,12 +553,8 @@ def rspmm_drelation_boundary(csr, input, output_grad, b_node):
     d_relation = torch.empty(n_rel, F, dtype=torch.float32, device=dev)
     n_ws = int(plan.n_pieces) * F
     ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_rspmm_drelation_boundary_f32(
-            plan.pointer, items.data_ptr(), items.shape[0], src_ptr.data_ptr(), src_relpos.data_ptr(), b_node.data_ptr(),
-            input.data_ptr(), output_grad.data_ptr(), d_relation.data_ptr(), ws.data_ptr() if ws is not None else None, n_ws * 4,
-            n_src, n_rel, F, _stream()))
+    _launch(dev, "ultra_rspmm_drelation_boundary_f32", plan.pointer, items, items.shape[0], src_ptr, src_relpos, b_node, input,
+            output_grad, d_relation, ws, n_ws * 4, n_src, n_rel, F)
     return d_relation
 
 
@@ -541,10 +569,7 @@ def candidate_rows(t_index, n_node):
         return None
     t_index = t_index.contiguous()
     bits = torch.empty(t_index.shape[0], n_words, dtype=torch.int32, device=t_index.device)
-    lib = _lib.load()
-    with torch.cuda.device(t_index.device):
-        _lib.check(lib.ultra_node_bitmap(t_index.data_ptr(), t_index.shape[0], t_index.shape[1], int(n_node), bits.data_ptr(),
-                                         _stream()))
+    _launch(t_index.device, "ultra_node_bitmap", t_index, t_index.shape[0], t_index.shape[1], int(n_node), bits)
     return bits
 
 
@@ -571,29 +596,17 @@ def rspmm_backward(csr, relation, input, output, output_grad, sum="add", mul="mu
         if active_src is not None and (active_src.dtype != torch.int32 or not active_src.is_contiguous() or active_src.device != dev
                                        or tuple(active_src.shape) != (n_tiles,)):
             raise RuntimeError("rspmm_backward: active_src must be contiguous int32 (%d,) on %s" % (n_tiles, dev))
-        if d_input_add is not None and (not need_input or not d_input_add.is_contiguous() or d_input_add.shape != input.shape
-                                        or d_input_add.dtype != torch.float32):
-            raise RuntimeError("d_input_add: contiguous fp32 tensor of input's shape, sum aggregation, with need_input")
+        _check_d_input_add(d_input_add, input, sum, need_input)
         d_input = (d_input_add if d_input_add is not None else torch.empty_like(input)) if need_input else None
         d_relation = torch.empty_like(relation) if need_relation else None
         by_src = csr.by_src if need_input else None
         by_rel = csr.by_rel if need_relation else None
-        lib = _lib.load()
-        n_ws = max(by_src.workspace_rows if by_src is not None else 0, by_rel.workspace_rows if by_rel is not None else 0) * F
-        ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_rspmm_backward_active_f32(
-                by_src.pointer if by_src is not None else None, by_rel.pointer if by_rel is not None else None,
-                relation.data_ptr(), input.data_ptr(), output_grad.data_ptr(),
-                d_input_add.data_ptr() if d_input_add is not None else None,
-                d_input.data_ptr() if d_input is not None else None, d_relation.data_ptr() if d_relation is not None else None,
-                ws.data_ptr() if ws is not None else None, n_ws * 4, csr.shape[1], csr.shape[0], csr.shape[2], F, mul_op,
-                active_dst.data_ptr() if active_dst is not None else None, active_dst.shape[1] if active_dst is not None else 0,
-                active_src.data_ptr() if (active_src is not None and mul == "mul") else None, _stream()))
+        ws, ws_bytes = _backward_workspace(by_src, by_rel, F, dev)
+        _launch(dev, "ultra_rspmm_backward_active_f32", _plan(by_src), _plan(by_rel), relation, input, output_grad, d_input_add,
+                d_input, d_relation, ws, ws_bytes, csr.shape[1], csr.shape[0], csr.shape[2], F, mul_op, active_dst,
+                active_dst.shape[1] if active_dst is not None else 0, active_src if mul == "mul" else None)
         return d_input, d_relation
-    if d_input_add is not None and (not need_input or sum != "add" or not d_input_add.is_contiguous()
-                                    or d_input_add.shape != input.shape or d_input_add.dtype != torch.float32):
-        raise RuntimeError("d_input_add: contiguous fp32 tensor of input's shape, sum aggregation, with need_input")
+    _check_d_input_add(d_input_add, input, sum, need_input)
     d_input = (d_input_add if d_input_add is not None else torch.empty_like(input)) if need_input else None
     d_relation = torch.empty_like(relation) if need_relation else None
     if F == 0 or (not need_input and not need_relation):
@@ -605,17 +618,9 @@ def rspmm_backward(csr, relation, input, output, output_grad, sum="add", mul="mu
             by_src.plan_tensor if by_src is not None else None, by_rel.plan_tensor if by_rel is not None else None,
             relation, input, output, output_grad, d_input, d_input_add is not None, csr.shape[1], csr.shape[0], sum_op, mul_op)
         return d_input, (d_rel if need_relation else None)
-    lib = _lib.load()
-    n_ws = max(by_src.workspace_rows if by_src is not None else 0, by_rel.workspace_rows if by_rel is not None else 0) * F
-    ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_rspmm_backward_accumulate_f32(
-            by_src.pointer if by_src is not None else None, by_rel.pointer if by_rel is not None else None,
-            relation.data_ptr(), input.data_ptr(), output.data_ptr() if output is not None else None,
-            output_grad.data_ptr(), d_input_add.data_ptr() if d_input_add is not None else None,
-            d_input.data_ptr() if d_input is not None else None,
-            d_relation.data_ptr() if d_relation is not None else None, ws.data_ptr() if ws is not None else None,
-            n_ws * 4, csr.shape[1], csr.shape[0], csr.shape[2], F, sum_op, mul_op, _stream()))
+    ws, ws_bytes = _backward_workspace(by_src, by_rel, F, dev)
+    _launch(dev, "ultra_rspmm_backward_accumulate_f32", _plan(by_src), _plan(by_rel), relation, input, output, output_grad,
+            d_input_add, d_input, d_relation, ws, ws_bytes, csr.shape[1], csr.shape[0], csr.shape[2], F, sum_op, mul_op)
     return d_input, d_relation
 
 
@@ -636,10 +641,8 @@ def rspmm_backward_boundary_rows(csr, relation, output_grad, boundary_node, d_in
     lib = _lib.load()
     ws = torch.empty(max(int(lib.ultra_rspmm_backward_boundary_rows_workspace(n_query)) // 4, 1), dtype=torch.float32,
                      device=d_input.device)
-    with torch.cuda.device(d_input.device):
-        _lib.check(lib.ultra_rspmm_backward_boundary_rows_f32(
-            csr.by_src.pointer, src_ptr.data_ptr(), relation.data_ptr(), output_grad.data_ptr(), boundary_node.data_ptr(),
-            d_input.data_ptr(), ws.data_ptr(), ws.numel() * 4, csr.shape[1], n_query, F, mul_op, _stream()))
+    _launch(d_input.device, "ultra_rspmm_backward_boundary_rows_f32", csr.by_src.pointer, src_ptr, relation, output_grad,
+            boundary_node, d_input, ws, ws.numel() * 4, csr.shape[1], n_query, F, mul_op)
     return d_input
 
 
@@ -650,11 +653,8 @@ def rspmm_backward_weight(csr, relation, input, output, output_grad, sum="add", 
     d_w = torch.zeros(csr.n_edges, dtype=torch.float32, device=input.device)
     if csr.n_edges == 0 or input.shape[1] == 0:
         return d_w
-    lib = _lib.load()
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_rspmm_backward_weight_f32(
-            csr.fwd.pointer, relation.data_ptr(), input.data_ptr(), output.data_ptr() if output is not None else None,
-            output_grad.data_ptr(), d_w.data_ptr(), csr.shape[2], input.shape[1], sum_op, mul_op, _stream()))
+    _launch(input.device, "ultra_rspmm_backward_weight_f32", csr.fwd.pointer, relation, input, output, output_grad, d_w,
+            csr.shape[2], input.shape[1], sum_op, mul_op)
     return d_w
 
 
@@ -678,23 +678,18 @@ def combine_forward(input, update, weight, bias, ln_weight=None, ln_bias=None, l
                 or b_node.dtype != torch.int32 or not b_node.is_contiguous() or b_value.shape != (n_query, 64)):
             raise RuntimeError("combine_forward(input_boundary=...): update (N, B, 64), node int32 (B,), value (B, 64)")
         tensors = [update, weight, bias, b_value] + ([ln_weight, ln_bias] if ln_weight is not None else [])
-        if any(t.dtype != torch.float32 or not t.is_cuda or t.device != update.device for t in tensors) or b_node.device != update.device:
+        if _not_fp32_on(update.device, tensors) or b_node.device != update.device:
             raise RuntimeError("combine_forward needs fp32 tensors on one HIP device (no CPU fallback)")
         update = update.contiguous()
         out = update if reuse_update else torch.empty_like(update)
-        lib = _lib.load()
-        with torch.cuda.device(update.device):
-            _lib.check(lib.ultra_combine_forward_boundary_f32(
-                b_node.data_ptr(), b_value.data_ptr(), n_query, update.data_ptr(), weight.contiguous().data_ptr(),
-                bias.contiguous().data_ptr(), ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-                ln_bias.contiguous().data_ptr() if ln_weight is not None else None, float(ln_eps), int(bool(relu)),
-                int(bool(shortcut)), out.data_ptr(), update.numel() // 64, 64, _stream()))
+        _launch(update.device, "ultra_combine_forward_boundary_f32", b_node, b_value, n_query, update,
+                *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), out, update.numel() // 64, 64)
         return out
     if input.shape != update.shape or input.shape[-1] != 64 or tuple(weight.shape) != (64, 128):
         raise RuntimeError("combine_forward handles 64 -> 64 layers with a (64, 128) weight; got input %s, update %s, "
                            "weight %s" % (tuple(input.shape), tuple(update.shape), tuple(weight.shape)))
     tensors = [input, update, weight, bias] + ([ln_weight, ln_bias] if ln_weight is not None else [])
-    if any(t.dtype != torch.float32 or not t.is_cuda or t.device != input.device for t in tensors):
+    if _not_fp32_on(input.device, tensors):
         raise RuntimeError("combine_forward needs fp32 tensors on one HIP device (no CPU fallback)")
     input, update = input.contiguous(), update.contiguous()
     out = update if reuse_update else torch.empty_like(input)
@@ -702,14 +697,8 @@ def combine_forward(input, update, weight, bias, ln_weight=None, ln_bias=None, l
     if z_out is not None and (z_out.shape != input.shape or z_out.dtype != torch.float32 or not z_out.is_contiguous()
                               or z_out.device != input.device):
         raise RuntimeError("combine_forward: z_out must be a contiguous fp32 tensor of the input's shape on its device")
-    lib = _lib.load()
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_combine_forward_f32(
-            input.data_ptr(), update.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-            ln_weight.contiguous().data_ptr() if ln_weight is not None else None,
-            ln_bias.contiguous().data_ptr() if ln_weight is not None else None,
-            float(ln_eps), int(bool(relu)), int(bool(shortcut)), out.data_ptr(),
-            z_out.data_ptr() if z_out is not None else None, rows, 64, _stream()))
+    _launch(input.device, "ultra_combine_forward_f32", input, update,
+            *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), out, z_out, rows, 64)
     return out
 
 
@@ -724,15 +713,13 @@ def linear_forward(input, weight, bias, relu=False):
     out_dim, in_dim = weight.shape
     if not linear_supported(in_dim, out_dim) or input.shape[-1] != in_dim or bias is None:
         raise RuntimeError("linear_forward: unsupported shape %s x %s" % (tuple(input.shape), tuple(weight.shape)))
-    if any(t.dtype != torch.float32 or not t.is_cuda or t.device != input.device for t in (input, weight, bias)):
+    if _not_fp32_on(input.device, (input, weight, bias)):
         raise RuntimeError("linear_forward needs fp32 tensors on one HIP device (no CPU fallback)")
     x = input.contiguous()
     rows = x.numel() // in_dim
     out = torch.empty(tuple(input.shape[:-1]) + (out_dim,), dtype=torch.float32, device=input.device)
-    lib = _lib.load()
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_linear_forward_f32(x.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                                                out.data_ptr(), rows, in_dim, out_dim, int(bool(relu)), _stream()))
+    _launch(input.device, "ultra_linear_forward_f32", x, weight.contiguous(), bias.contiguous(), out, rows, in_dim, out_dim,
+            int(bool(relu)))
     return out
 
 
@@ -743,16 +730,12 @@ def score_all_entities(hidden, query, w1, b1, w2, b2):
     if dim != 64 or tuple(query.shape) != (batch, 64) or tuple(w1.shape) != (128, 128) or w2.numel() != 128:
         raise RuntimeError("score_all_entities handles the 64-d model with a 128 -> 128 -> 1 head")
     tensors = (hidden, query, w1, b1, w2, b2)
-    if any(t.dtype != torch.float32 or not t.is_cuda or t.device != hidden.device for t in tensors):
+    if _not_fp32_on(hidden.device, tensors):
         raise RuntimeError("score_all_entities needs fp32 tensors on one HIP device (no CPU fallback)")
     out = torch.empty(batch, n_node, dtype=torch.float32, device=hidden.device)
     query_bias = torch.empty(batch, 128, dtype=torch.float32, device=hidden.device)     # the queries' share of layer 1
-    lib = _lib.load()
-    with torch.cuda.device(hidden.device):
-        _lib.check(lib.ultra_score_forward_f32(hidden.contiguous().data_ptr(), query.contiguous().data_ptr(),
-                                               w1.contiguous().data_ptr(), b1.contiguous().data_ptr(),
-                                               w2.contiguous().data_ptr(), b2.contiguous().data_ptr(),
-                                               query_bias.data_ptr(), out.data_ptr(), n_node, batch, _stream()))
+    _launch(hidden.device, "ultra_score_forward_f32", hidden.contiguous(), query.contiguous(), w1.contiguous(), b1.contiguous(),
+            w2.contiguous(), b2.contiguous(), query_bias, out, n_node, batch)
     return out
 
 
@@ -777,10 +760,8 @@ def statistics(values, repeated=None, repeat=0):
     lib = _lib.load()
     out = torch.empty(3, dtype=torch.float32, device=a.device)
     partials = torch.empty(2 * lib.ultra_statistics_blocks(a.numel()), dtype=torch.float64, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(lib.ultra_statistics_f32(a.data_ptr(), a.numel(), b.data_ptr() if b is not None else None,
-                                            b.numel() if b is not None else 0, int(repeat) if b is not None else 0,
-                                            partials.data_ptr(), out.data_ptr(), _stream()))
+    _launch(a.device, "ultra_statistics_f32", a, a.numel(), b, b.numel() if b is not None else 0,
+            int(repeat) if b is not None else 0, partials, out)
     return out
 
 
@@ -791,10 +772,7 @@ class _BCEAdversarial(torch.autograd.Function):
         rows, cols = pred.shape
         loss = torch.empty(rows, dtype=torch.float32, device=pred.device)
         dpred = torch.empty_like(pred)
-        lib = _lib.load()
-        with torch.cuda.device(pred.device):
-            _lib.check(lib.ultra_bce_adversarial_f32(pred.data_ptr(), rows, cols, float(temperature), loss.data_ptr(),
-                                                     dpred.data_ptr(), _stream()))
+        _launch(pred.device, "ultra_bce_adversarial_f32", pred, rows, cols, float(temperature), loss, dpred)
         ctx.save_for_backward(dpred)
         return loss
 
@@ -827,11 +805,7 @@ class _ScoreRows(torch.autograd.Function):
         h = torch.empty(n_batch * per_row, 128, dtype=torch.float32, device=dev)
         in_rows = torch.empty(n_batch * per_row, 128, dtype=torch.float32, device=dev)
         score = torch.empty(n_batch, per_row, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_score_rows_forward_f32(hidden.data_ptr(), query.data_ptr(), t_index.data_ptr(), w1.data_ptr(),
-                                                        b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), h.data_ptr(), in_rows.data_ptr(),
-                                                        score.data_ptr(), n_batch, per_row, _stream()))
+        _launch(dev, "ultra_score_rows_forward_f32", hidden, query, t_index, w1, b1, w2, b2, h, in_rows, score, n_batch, per_row)
         # the backward never reads `hidden` (its rows are in `in_rows`): only the shape is kept, so the step's largest
         # activation is not held alive until the score head's backward
         ctx.hidden_shape = tuple(hidden.shape)
@@ -852,12 +826,8 @@ class _ScoreRows(torch.autograd.Function):
         d_b1 = torch.empty(128, dtype=torch.float32, device=dev)
         d_w2 = torch.empty(128, dtype=torch.float32, device=dev)
         d_b2 = torch.empty(1, dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_score_rows_backward_f32(
-                None, query.data_ptr(), t_index.data_ptr(), w1.data_ptr(), w2.data_ptr(), h.data_ptr(), in_rows.data_ptr(),
-                grad.data_ptr(), d_pre.data_ptr(), partial.data_ptr(), d_hidden.data_ptr(), d_query.data_ptr(), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(),
-                d_b2.data_ptr(), ctx.hidden_shape[0], n_batch, per_row, _stream()))
+        _launch(dev, "ultra_score_rows_backward_f32", None, query, t_index, w1, w2, h, in_rows, grad, d_pre, partial, d_hidden,
+                d_query, d_w1, d_b1, d_w2, d_b2, ctx.hidden_shape[0], n_batch, per_row)
         return d_hidden, d_query, None, d_w1, d_b1, d_w2.view(1, 128), d_b2
 
 
@@ -901,10 +871,7 @@ def relation_graph_blocks(edge_list, n_node, n_rel):
         rel = (key % n_rel).to(torch.int32)
         lists += [ptr, rel]
     marks = torch.empty(4, n_rel, n_rel, dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_relation_graph_marks(lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
-                                                  n_node, n_rel, marks.data_ptr(), _stream()))
+    _launch(dev, "ultra_relation_graph_marks", *lists, n_node, n_rel, marks)
     return marks.bool()
 
 
@@ -913,7 +880,6 @@ def relation_stack_inputs(weights, h_index):
     relation embeddings, each fp32 ``(R4, 64)``; ``h_index`` int64 ``(Q,)``.  Returns ``(tables (L, R4, Q * 64), ones (Q, 64),
     node32 int32 (Q,))`` -- ``stack(weights).unsqueeze(2).expand(-1, -1, Q, -1).reshape(L, R4, Q * 64)``, ``torch.ones(Q, 64)``
     and ``h_index.to(int32)`` (``ultra/rel_model.py:351-378``, ``ultra/layer.py:143-151``)."""
-    import ctypes
     n = len(weights)
     keep = [w.detach().contiguous() for w in weights]
     if (n == 0 or n > 8 or h_index.dtype != torch.int64 or h_index.dim() != 1 or not h_index.is_cuda
@@ -925,11 +891,8 @@ def relation_stack_inputs(weights, h_index):
     ones = torch.empty(n_query, 64, dtype=torch.float32, device=dev)
     node32 = torch.empty(n_query, dtype=torch.int32, device=dev)
     if n_query:
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_relation_stack_inputs((ctypes.c_void_p * n)(*[w.data_ptr() for w in keep]), n, n_rel, n_query,
-                                                       h_index.data_ptr(), h_index.stride(0), tables.data_ptr(), ones.data_ptr(),
-                                                       node32.data_ptr(), _stream()))
+        _launch(dev, "ultra_relation_stack_inputs", _pointer_array(keep), n, n_rel, n_query, h_index, h_index.stride(0), tables,
+                ones, node32)
     return tables, ones, node32
 
 
@@ -940,30 +903,24 @@ def relation_project(relation, weights, repeat=1):
     -- ``relation_projection(relation).transpose(0, 1).flatten(1)`` (``layer.py:325-326``), bit for bit.
     ``repeat``: the tables of ``torch.cat([relation] * repeat)`` -- ``(R, repeat * B * 64)``, query block ``b + j B`` a copy of
     block ``b`` -- computed once (full-batch evaluation: tail and head queries share the relation representations)."""
-    import ctypes
     if relation.dim() != 3 or relation.shape[-1] != 64 or relation.dtype != torch.float32 or not relation.is_cuda:
         raise RuntimeError("relation_project: fp32 (B, R, 64) on a HIP device, got %s" % (tuple(relation.shape),))
     relation = _rows_in_place(relation)
     batch, n_rel, _ = relation.shape
     n = len(weights)
-    keep, cols = [], [[], [], [], []]
+    cols = [[], [], [], []]
     for layer_weights in weights:
         for k, t in enumerate(layer_weights):
             t = t.detach().contiguous()
             if t.dtype != torch.float32 or t.device != relation.device or t.shape != ((64, 64) if k % 2 == 0 else (64,)):
                 raise RuntimeError("relation_project: 64 -> 64 -> 64 fp32 projections only")
-            keep.append(t)
-            cols[k].append(t.data_ptr())
+            cols[k].append(t)
     repeat = int(repeat)
     outs = [torch.empty(n_rel, repeat * batch * 64, dtype=torch.float32, device=relation.device) for _ in range(n)]
     if n == 0 or relation.numel() == 0:
         return outs
-    arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
-    lib = _lib.load()
-    with torch.cuda.device(relation.device):
-        _lib.check(lib.ultra_relation_project_f32(
-            relation.data_ptr(), relation.stride(0), relation.stride(1), arr(cols[0]), arr(cols[1]), arr(cols[2]), arr(cols[3]),
-            arr([o.data_ptr() for o in outs]), n, batch, repeat, n_rel, 64, _stream()))
+    _launch(relation.device, "ultra_relation_project_f32", relation, relation.stride(0), relation.stride(1),
+            *[_pointer_array(col) for col in cols], _pointer_array(outs), n, batch, repeat, n_rel, 64)
     return outs
 
 
@@ -982,7 +939,6 @@ class _ProjectFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        import ctypes
         relation, *flat_weights = ctx.saved_tensors
         relation = relation.contiguous()
         n = len(flat_weights) // 4
@@ -996,14 +952,9 @@ class _ProjectFunction(torch.autograd.Function):
         blocks = ctypes.c_int64(0)
         _lib.check(lib.ultra_relation_project_backward_blocks(dev.index or 0, batch, n_rel, n, ctypes.byref(blocks)))
         ws = torch.empty(n * blocks.value * (2 * 64 * 64 + 128), dtype=torch.float32, device=dev)
-        arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_relation_project_backward_f32(
-                relation.data_ptr(), arr([w[4 * l].data_ptr() for l in range(n)]), arr([w[4 * l + 1].data_ptr() for l in range(n)]),
-                arr([w[4 * l + 2].data_ptr() for l in range(n)]), arr([None if g is None else g.data_ptr() for g in keep]),
-                d_layers.data_ptr(), arr([d_w[4 * l].data_ptr() for l in range(n)]), arr([d_w[4 * l + 1].data_ptr() for l in range(n)]),
-                arr([d_w[4 * l + 2].data_ptr() for l in range(n)]), arr([d_w[4 * l + 3].data_ptr() for l in range(n)]),
-                ws.data_ptr(), ws.numel() * 4, n, batch, n_rel, 64, _stream()))
+        _launch(dev, "ultra_relation_project_backward_f32", relation, _pointer_array(w[0::4]), _pointer_array(w[1::4]),
+                _pointer_array(w[2::4]), _pointer_array(keep), d_layers, _pointer_array(d_w[0::4]), _pointer_array(d_w[1::4]),
+                _pointer_array(d_w[2::4]), _pointer_array(d_w[3::4]), ws, ws.numel() * 4, n, batch, n_rel, 64)
         d_relation = d_layers.sum(0).view(batch, n_rel, 64) if ctx.needs_input_grad[0] else None
         return (d_relation, *[g if need else None for g, need in zip(d_w, ctx.needs_input_grad[1:])])
 
@@ -1036,12 +987,8 @@ def prepare_queries(batch, rel_rep, n_base_rel):
     relation = torch.empty(2 * n_batch, dtype=torch.int64, device=dev)
     query = torch.empty(2 * n_batch, 64, dtype=torch.float32, device=dev)
     if n_batch:
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_prepare_queries(batch.data_ptr(), rel_rep.data_ptr(), rel_rep.stride(0), rel_rep.stride(1), n_batch,
-                                                 rel_rep.shape[1], int(n_base_rel),
-                                                 anchor.data_ptr(), anchor32.data_ptr(), relation.data_ptr(), query.data_ptr(),
-                                                 _stream()))
+        _launch(dev, "ultra_prepare_queries", batch, rel_rep, rel_rep.stride(0), rel_rep.stride(1), n_batch, rel_rep.shape[1],
+                int(n_base_rel), anchor, anchor32, relation, query)
     return anchor, anchor32, relation, query
 
 
@@ -1061,12 +1008,8 @@ def filtered_rank(pred, target, filt_ptr=None, filt_node=None):
     rank = torch.empty(rows, dtype=torch.int64, device=pred.device)
     if rows == 0:
         return rank
-    lib = _lib.load()
-    with torch.cuda.device(pred.device):
-        _lib.check(lib.ultra_filtered_rank(
-            pred.data_ptr(), rows, n_cand, n_cand, target.data_ptr(),
-            filt_ptr.data_ptr() if filt_ptr is not None else None,
-            filt_node.data_ptr() if filt_ptr is not None else None, rank.data_ptr(), _stream()))
+    _launch(pred.device, "ultra_filtered_rank", pred, rows, n_cand, n_cand, target, filt_ptr,
+            filt_node if filt_ptr is not None else None, rank)
     return rank
 
 
@@ -1108,12 +1051,8 @@ def filtered_rank_keys(pred, target, keys, anchor, rel, n_rel, n_node=None):
     if rows == 0:
         return rank
     anchor, rel = anchor.contiguous(), rel.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(pred.device):
-        _lib.check(lib.ultra_filtered_rank_keys(
-            pred.data_ptr(), rows, n_cand, pred.stride(0), target.data_ptr(), target.stride(0),
-            keys.data_ptr() if keys is not None else None, keys.numel() if keys is not None else 0, anchor.data_ptr(),
-            rel.data_ptr(), 1, int(n_rel), rank.data_ptr(), 1, _stream()))
+    _launch(pred.device, "ultra_filtered_rank_keys", pred, rows, n_cand, pred.stride(0), target, target.stride(0), keys,
+            keys.numel() if keys is not None else 0, anchor, rel, 1, int(n_rel), rank, 1)
     return rank
 
 
@@ -1134,11 +1073,8 @@ def strict_negatives(keys, anchor, rel, n_rel, n_node, rand):
     out = torch.empty(rows, n_sample, dtype=torch.int64, device=rand.device)
     if out.numel() == 0:
         return out
-    lib = _lib.load()
-    with torch.cuda.device(rand.device):
-        _lib.check(lib.ultra_strict_negative(keys.data_ptr(), keys.numel(), anchor.data_ptr(), rel.data_ptr(), rows,
-                                             int(n_rel), int(n_node), rand.data_ptr(), n_sample, out.data_ptr(),
-                                             _stream()))
+    _launch(rand.device, "ultra_strict_negative", keys, keys.numel(), anchor, rel, rows, int(n_rel), int(n_node), rand, n_sample,
+            out)
     return out
 
 
@@ -1147,7 +1083,33 @@ def strict_negatives(keys, anchor, rel, n_rel, n_node, rand):
 # work, identical gradients.  Measured on an MI355X it only moves the backward kernel 380 -> 365 us at 655 k rows (the kernel
 # waits on memory 38 % of its cycles, PMC; its matrix cores are busy 44 %) and the forward pays 12 us for writing z: no gain
 # per step, hence off by default.
-KEEP_PRE_NORM = __import__("os").environ.get("ULTRA_KEEP_PRE_NORM", "0") == "1"
+KEEP_PRE_NORM = _env_bool("ULTRA_KEEP_PRE_NORM", False)
+
+
+def _epilogue_gradients(input_c, update_c, has_ln, zero_update=False):
+    """Outputs of the one-pass epilogue backward: ``[d_input, d_update, d_weight, d_bias, d_gamma, d_beta]`` (the LayerNorm
+    pair ``None`` without LayerNorm)."""
+    dev = input_c.device
+    d_input = torch.empty_like(input_c)
+    d_update = torch.zeros_like(update_c) if zero_update else torch.empty_like(update_c)
+    d_weight = torch.empty(64, 128, dtype=torch.float32, device=dev)
+    d_bias = torch.empty(64, dtype=torch.float32, device=dev)
+    d_g = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
+    d_b = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
+    return [d_input, d_update, d_weight, d_bias, d_g, d_b]
+
+
+def _combine_backward_fused(input_c, update_c, epilogue, grad_out, z, grads, tiles=None):
+    """``ultra_combine_backward_fused_f32`` into ``grads`` (:func:`_epilogue_gradients`): one pass over the rows -- recompute z
+    (or load ``z``), LayerNorm / ReLU backward, d_weight, d_input | d_update (3 row-sized reads + 2 writes); parameter gradients
+    come out finished.  ``epilogue``: the layer's :func:`_epilogue` run; ``tiles``: see :func:`candidate_tiles`."""
+    dev = input_c.device
+    rows = input_c.numel() // 64
+    n_waves = ctypes.c_int(0)
+    _lib.check(_lib.load().ultra_combine_backward_fused_waves(dev.index or 0, rows, ctypes.byref(n_waves)))
+    ws = torch.empty(n_waves.value * (64 * 128 + 192), dtype=torch.float32, device=dev)
+    _launch(dev, "ultra_combine_backward_fused_f32", input_c, update_c, *epilogue, grad_out, z, *grads, ws, ws.numel() * 4, tiles,
+            tiles.numel() if tiles is not None else 0, rows, 64)
 
 
 class _CombineFunction(torch.autograd.Function):
@@ -1170,57 +1132,34 @@ class _CombineFunction(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         input_c, update_c = input.contiguous(), update.contiguous()
         rows = input.numel() // 64
-        lib = _lib.load()
         dev = input.device
-        import ctypes
-        import os
         if os.environ.get("ULTRA_COMBINE_BWD", "fused") == "fused":
-            # one pass over the rows: recompute z, LayerNorm / ReLU backward, d_weight, d_input | d_update (3 row-sized
-            # reads + 2 writes); parameter gradients come out finished.  ULTRA_COMBINE_BWD=split: the three-kernel form.
+            # the one-pass form (_combine_backward_fused).  ULTRA_COMBINE_BWD=split: the three-kernel form.
             has_ln = ln_weight is not None
-            n_waves = ctypes.c_int(0)
-            _lib.check(lib.ultra_combine_backward_fused_waves(dev.index or 0, rows, ctypes.byref(n_waves)))
-            ws = torch.empty(n_waves.value * (64 * 128 + 192), dtype=torch.float32, device=dev)
-            d_input, d_update = torch.empty_like(input_c), torch.empty_like(update_c)
-            d_weight = torch.empty(64, 128, dtype=torch.float32, device=dev)
-            d_bias = torch.empty(64, dtype=torch.float32, device=dev)
-            d_g = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
-            d_b = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
-            with torch.cuda.device(dev):
-                _lib.check(lib.ultra_combine_backward_fused_f32(
-                    input_c.data_ptr(), update_c.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                    ln_weight.contiguous().data_ptr() if has_ln else None, ln_bias.contiguous().data_ptr() if has_ln else None,
-                    ln_eps, int(relu), int(shortcut), grad_out.data_ptr(), z.data_ptr() if z is not None else None,
-                    d_input.data_ptr(), d_update.data_ptr(),
-                    d_weight.data_ptr(), d_bias.data_ptr(), d_g.data_ptr() if has_ln else None,
-                    d_b.data_ptr() if has_ln else None, ws.data_ptr(), ws.numel() * 4, None, 0, rows, 64, _stream()))
+            grads = _epilogue_gradients(input_c, update_c, has_ln)
+            _combine_backward_fused(input_c, update_c, _epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), grad_out,
+                                    z, grads)
+            d_input, d_update, d_weight, d_bias, d_g, d_b = grads
             needs = ctx.needs_input_grad
             return (d_input.view_as(input) if needs[0] else None, d_update.view_as(update) if needs[1] else None,
                     d_weight if needs[2] else None, d_bias if needs[3] else None, d_g if (has_ln and needs[4]) else None,
                     d_b if (has_ln and needs[5]) else None, None, None, None)
         n_ln, n_wg = ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(lib.ultra_combine_backward_waves(dev.index or 0, rows, ctypes.byref(n_ln), ctypes.byref(n_wg)))
+        _lib.check(_lib.load().ultra_combine_backward_waves(dev.index or 0, rows, ctypes.byref(n_ln), ctypes.byref(n_wg)))
         d_z = torch.empty(rows, 64, dtype=torch.float32, device=dev)
         has_ln = ln_weight is not None
         dg_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
         db_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
         dw_p = torch.empty(n_wg.value, 64 * 128, dtype=torch.float32, device=dev)
         dbias_p = torch.empty(n_wg.value, 64, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_combine_backward_f32(
-                input_c.data_ptr(), update_c.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                ln_weight.contiguous().data_ptr() if has_ln else None, ln_bias.contiguous().data_ptr() if has_ln else None,
-                ln_eps, int(relu), grad_out.data_ptr(), d_z.data_ptr(), dg_p.data_ptr() if has_ln else None,
-                db_p.data_ptr() if has_ln else None, dw_p.data_ptr(),
-                dbias_p.data_ptr() if dbias_p is not None else None, rows, 64, _stream()))
+        _launch(dev, "ultra_combine_backward_f32", input_c, update_c, *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu),
+                grad_out, d_z, dg_p, db_p, dw_p, dbias_p, rows, 64)
         needs = ctx.needs_input_grad
         d_input = d_update = d_weight = d_bias = d_g = d_b = None
         if needs[0] and needs[1]:       # both activation gradients: one pass over d_z instead of two GEMMs
             d_input, d_update = torch.empty_like(input_c), torch.empty_like(update_c)
-            with torch.cuda.device(dev):
-                _lib.check(lib.ultra_combine_dxdu_f32(
-                    d_z.data_ptr(), weight.contiguous().data_ptr(), grad_out.data_ptr() if shortcut else None,
-                    d_input.data_ptr(), d_update.data_ptr(), rows, 64, _stream()))
+            _launch(dev, "ultra_combine_dxdu_f32", d_z, weight.contiguous(), grad_out if shortcut else None, d_input, d_update,
+                    rows, 64)
             d_input, d_update = d_input.view_as(input), d_update.view_as(update)
         elif needs[0]:
             if shortcut:        # d_input = grad_out + d_z . W[:, :64] in one GEMM call (beta = 1)
@@ -1243,7 +1182,7 @@ class _CombineFunction(torch.autograd.Function):
 # The fused inference fast paths of model.py / rel_model.py (one query-preparation kernel, projection tables computed once
 # for both sides, the first layer's boundary never materialised) run on this backend; the oracle-backed backend of the
 # tests keeps the reference's op-by-op path, so the two are compared against each other.
-FAST_INFERENCE = __import__("os").environ.get("ULTRA_FAST_INFERENCE", "1") != "0"
+FAST_INFERENCE = _env_bool("ULTRA_FAST_INFERENCE", True)
 
 
 def combine(input, update, weight, bias, ln_weight=None, ln_bias=None, ln_eps=1e-5, relu=True, shortcut=False,
@@ -1296,9 +1235,7 @@ class _RSPMMFunction(torch.autograd.Function):
         d_add = output_grad if (ctx.has_add_rows and ctx.needs_input_grad[6]) else None
         d_value = None
         if ctx.b_node is not None and ctx.needs_input_grad[8]:
-            n_query = ctx.b_node.shape[0]
-            blocks = output_grad.view(output_grad.shape[0], n_query, -1)
-            d_value = blocks[ctx.b_node.long(), torch.arange(n_query, device=output_grad.device)]
+            d_value = _boundary_value_grad(output_grad, ctx.b_node)
         d_edge = None
         if len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]:
             d_edge = rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul)
@@ -1321,11 +1258,11 @@ def tables_finite(relation):
 
 
 # (see rspmm_backward_boundary_rows).  ULTRA_BOUNDARY_ROWS_BACKWARD=0: the full d_input pass.
-BOUNDARY_ROWS_BACKWARD = __import__("os").environ.get("ULTRA_BOUNDARY_ROWS_BACKWARD", "1") != "0"
+BOUNDARY_ROWS_BACKWARD = _env_bool("ULTRA_BOUNDARY_ROWS_BACKWARD", True)
 
 
 # Training, last layer: the epilogue's backward over the candidate rows' tiles only (see sum_layer).  ULTRA_SPARSE_LAST_LAYER=0: all tiles.
-SPARSE_LAST_LAYER_BACKWARD = __import__("os").environ.get("ULTRA_SPARSE_LAST_LAYER", "1") != "0"
+SPARSE_LAST_LAYER_BACKWARD = _env_bool("ULTRA_SPARSE_LAST_LAYER", True)
 
 
 def candidate_tiles(t_index, n_query, n_node=None):
@@ -1343,10 +1280,8 @@ def candidate_tiles(t_index, n_query, n_node=None):
         if t_index.is_cuda and t_index.dtype == torch.int64 and t_index.dim() == 2 and n_rows <= (32 << 20):
             t_index = t_index.contiguous()
             out = torch.empty(t_index.numel(), dtype=torch.int32, device=t_index.device)
-            lib = _lib.load()
-            with torch.cuda.device(t_index.device):
-                _lib.check(lib.ultra_candidate_tiles(t_index.data_ptr(), t_index.shape[0], t_index.shape[1], int(n_query), n_rows,
-                                                     out.data_ptr(), _stream()))
+            _launch(t_index.device, "ultra_candidate_tiles", t_index, t_index.shape[0], t_index.shape[1], int(n_query), n_rows,
+                    out)
             return out
     rows = t_index.long() * int(n_query) + torch.arange(t_index.shape[0], device=t_index.device).unsqueeze(-1)
     tiles = torch.div(rows.reshape(-1), 32, rounding_mode="floor")
@@ -1413,7 +1348,6 @@ class _SumLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        import ctypes
         relation, input, update, weight, bias, ln_weight, ln_bias, z = ctx.saved_tensors
         ln_eps, relu, shortcut = ctx.flags
         needs = ctx.needs_input_grad
@@ -1424,47 +1358,27 @@ class _SumLayerFunction(torch.autograd.Function):
         input_c, update_c = input.contiguous(), update.contiguous()
         rows = input.numel() // 64
         has_ln = ln_weight is not None
-        lib = _lib.load()
-        n_waves = ctypes.c_int(0)
-        _lib.check(lib.ultra_combine_backward_fused_waves(dev.index or 0, rows, ctypes.byref(n_waves)))
-        ws = torch.empty(n_waves.value * (64 * 128 + 192), dtype=torch.float32, device=dev)
+        epilogue = _epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut)
         first_rows = getattr(ctx, "first_rows", None)
         # first layer: d_relation from the boundary nodes' out-edges (reads d_update at the rows those edges reach only)?
         drel_boundary = bool(ctx.boundary_rows_only and needs[2] and needs[1] and BOUNDARY_DRELATION and ctx.mul == "mul"
                              and not ctx.csr.kernel_order("add", "mul", update_c[0].numel())[1])
-        d_input = torch.empty_like(input_c)
         # The sparse first-layer backward writes d_update at the LISTED rows only.  Any other consumer than the boundary kernels
         # (a knob or switch flipped between forward and backward: the full / masked d_relation kernels multiply every d_update row
         # by the zero input row, and 0 * NaN of uninitialised memory is NaN) gets zeros elsewhere.
-        d_update = torch.empty_like(update_c) if (first_rows is None or drel_boundary) else torch.zeros_like(update_c)
-        d_weight = torch.empty(64, 128, dtype=torch.float32, device=dev)
-        d_bias = torch.empty(64, dtype=torch.float32, device=dev)
-        d_g = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
-        d_b = torch.empty(64, dtype=torch.float32, device=dev) if has_ln else None
+        grads = _epilogue_gradients(input_c, update_c, has_ln, zero_update=not (first_rows is None or drel_boundary))
+        d_input, d_update, d_weight, d_bias, d_g, d_b = grads
         if first_rows is not None:
             # sparse first layer (csrc/first_layer_train.inc): the listed rows compacted and run through the one-pass backward, every
             # other row's share of d_bias / d_gamma / d_beta from the column sums of grad_out; d_update is written (and later read) at
             # the listed rows only, d_input -- which leaves this node -- is zero elsewhere
             row_list, list_count = first_rows
-            ws1 = torch.empty(int(lib.ultra_first_layer_epilogue_backward_workspace(dev.index or 0, row_list.numel())) // 4,
+            ws1 = torch.empty(int(_lib.load().ultra_first_layer_epilogue_backward_workspace(dev.index or 0, row_list.numel())) // 4,
                               dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.ultra_first_layer_epilogue_backward_f32(
-                    input_c.data_ptr(), update_c.data_ptr(), grad_out.data_ptr(), row_list.data_ptr(), list_count.data_ptr(),
-                    row_list.numel(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                    ln_weight.contiguous().data_ptr() if has_ln else None, ln_bias.contiguous().data_ptr() if has_ln else None,
-                    ln_eps, int(relu), int(shortcut), d_input.data_ptr(), d_update.data_ptr(), d_weight.data_ptr(), d_bias.data_ptr(),
-                    d_g.data_ptr() if has_ln else None, d_b.data_ptr() if has_ln else None, ws1.data_ptr(), ws1.numel() * 4, rows,
-                    _stream()))
-        with torch.cuda.device(dev):
-            _lib.check(0 if first_rows is not None else lib.ultra_combine_backward_fused_f32(
-                input_c.data_ptr(), update_c.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr(),
-                ln_weight.contiguous().data_ptr() if has_ln else None, ln_bias.contiguous().data_ptr() if has_ln else None,
-                ln_eps, int(relu), int(shortcut), grad_out.data_ptr(), z.data_ptr() if z is not None else None,
-                d_input.data_ptr(), d_update.data_ptr(),
-                d_weight.data_ptr(), d_bias.data_ptr(), d_g.data_ptr() if has_ln else None,
-                d_b.data_ptr() if has_ln else None, ws.data_ptr(), ws.numel() * 4,
-                tiles.data_ptr() if tiles is not None else None, tiles.numel() if tiles is not None else 0, rows, 64, _stream()))
+            _launch(dev, "ultra_first_layer_epilogue_backward_f32", input_c, update_c, grad_out, row_list, list_count,
+                    row_list.numel(), *epilogue, *grads, ws1, ws1.numel() * 4, rows)
+        else:
+            _combine_backward_fused(input_c, update_c, epilogue, grad_out, z, grads, tiles)
         # the edge gradient accumulates into the epilogue's d_input (same buffer) inside the rspmm backward
         flat_du = d_update.flatten(1)
         if ctx.boundary_rows_only and needs[2]:
@@ -1485,9 +1399,7 @@ class _SumLayerFunction(torch.autograd.Function):
         if ctx.b_node is not None and needs[5]:
             n_query = ctx.b_node.shape[0]
             d_value = torch.empty(n_query, 64, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.ultra_gather_boundary_rows_f32(d_update.data_ptr(), ctx.b_node.data_ptr(), n_query,
-                                                              d_value.data_ptr(), _stream()))
+            _launch(dev, "ultra_gather_boundary_rows_f32", d_update, ctx.b_node, n_query, d_value)
         return (None, d_relation, d_in.view(shape) if d_in is not None else None, d_add, None, d_value, None,
                 d_weight if needs[7] else None, d_bias if needs[8] else None, d_g if (has_ln and needs[9]) else None,
                 d_b if (has_ln and needs[10]) else None, None, None, None, None, None, None)
@@ -1598,32 +1510,16 @@ def rotate_rspmm_forward(csr, relation, input, sum="add", block=64, add_rows=Non
     relation, input = relation.contiguous(), input.contiguous()
     F = input.shape[1]
     out = torch.empty(csr.shape[0], F, dtype=torch.float32, device=input.device)
-    b_node = b_value = None
-    if add_rows is not None:
-        if boundary is not None:
-            raise RuntimeError("give the boundary either dense (add_rows) or sparse (boundary), not both")
-        add_rows = add_rows.contiguous()
-        if add_rows.shape != out.shape or add_rows.dtype != torch.float32 or add_rows.device != out.device:
-            raise RuntimeError("add_rows must be fp32 %s on %s" % (tuple(out.shape), out.device))
-    if boundary is not None:
-        b_node, b_value = boundary[0], boundary[1].contiguous()
-        if (b_node.dtype != torch.int32 or b_value.dtype != torch.float32 or b_node.dim() != 1 or b_value.dim() != 2
-                or b_value.shape != (b_node.shape[0], block) or b_value.numel() != F or b_node.device != out.device
-                or b_value.device != out.device or not b_node.is_contiguous()):
-            raise RuntimeError("boundary must be (int32 (B,), fp32 (B, %d)) with B * %d == %d on %s" % (block, block, F, out.device))
+    add_rows, b_node, b_value = _check_boundary_epilogue(out, add_rows, boundary, block)
     if out.numel() == 0:
         return out
     seg = csr.fwd
     if _torch_ext.binding() == "torch":
         return _torch_ext.load().rspmm_rotate_plan_fwd(seg.plan_tensor, relation, input, add_rows, b_node, b_value, csr.shape[1],
                                                        block, sum_op)
-    lib = _lib.load()
     ws, ws_bytes = _workspace(seg, F, input.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(input.device):
-        _lib.check(lib.ultra_rspmm_rotate_forward_f32(
-            seg.pointer, relation.data_ptr(), input.data_ptr(), ptr(add_rows), ptr(b_node), ptr(b_value), out.data_ptr(),
-            ptr(ws), ws_bytes, csr.shape[1], csr.shape[2], F, block, sum_op, _stream()))
+    _launch(input.device, "ultra_rspmm_rotate_forward_f32", seg.pointer, relation, input, add_rows, b_node, b_value, out, ws,
+            ws_bytes, csr.shape[1], csr.shape[2], F, block, sum_op)
     return out
 
 
@@ -1645,15 +1541,9 @@ def rotate_rspmm_backward(csr, relation, input, output, output_grad, sum="add", 
         return (d_input if need_input else None), (d_relation if need_relation else None)
     d_input = torch.empty_like(input) if need_input else None
     d_relation = torch.empty_like(relation) if need_relation else None
-    lib = _lib.load()
-    n_ws = max(by_src.workspace_rows if by_src is not None else 0, by_rel.workspace_rows if by_rel is not None else 0) * F
-    ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.ultra_rspmm_rotate_backward_f32(
-            by_src.pointer if by_src is not None else None, by_rel.pointer if by_rel is not None else None,
-            relation.data_ptr(), input.data_ptr(), ptr(output), output_grad.data_ptr(), ptr(d_input), ptr(d_relation),
-            ptr(ws), n_ws * 4, csr.shape[1], csr.shape[0], csr.shape[2], F, block, sum_op, _stream()))
+    ws, ws_bytes = _backward_workspace(by_src, by_rel, F, dev)
+    _launch(dev, "ultra_rspmm_rotate_backward_f32", _plan(by_src), _plan(by_rel), relation, input, output, output_grad, d_input,
+            d_relation, ws, ws_bytes, csr.shape[1], csr.shape[0], csr.shape[2], F, block, sum_op)
     return d_input, d_relation
 
 
@@ -1677,9 +1567,7 @@ class _RotateFunction(torch.autograd.Function):
         d_add = output_grad if (ctx.has_add_rows and ctx.needs_input_grad[5]) else None
         d_value = None
         if ctx.b_node is not None and ctx.needs_input_grad[7]:
-            n_query = ctx.b_node.shape[0]
-            blocks = output_grad.view(output_grad.shape[0], n_query, -1)
-            d_value = blocks[ctx.b_node.long(), torch.arange(n_query, device=output_grad.device)]
+            d_value = _boundary_value_grad(output_grad, ctx.b_node)
         return d_relation, d_input, None, None, None, d_add, None, d_value
 
 

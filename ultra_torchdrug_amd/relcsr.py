@@ -43,7 +43,6 @@ def auto_sizes(n_edges, wide=False, n_rows=None):
     per wave, kernel variants 2 / 3): 128 / 512.  ``ULTRA_CHUNK_EDGES`` overrides the chunk size (experiments)."""
     if wide:
         return 128, 512
-    import os
     forced = os.environ.get("ULTRA_CHUNK_EDGES")            # experiments (tools/kbench.py has --chunk for single kernels)
     piece = os.environ.get("ULTRA_PIECE_LEN")
     if n_edges >= 300_000:
@@ -188,13 +187,9 @@ class Segments:
         packed = torch.empty(E + PACK_SLACK, dtype=i32, device=dev) if E else None
         temp = torch.empty(int(lib.ultra_relcsr_plan_temp_bytes(E, R, piece_len)), dtype=torch.uint8, device=dev)
         counts = (ctypes.c_int64 * 4)()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_relcsr_plan(
-                self.row.data_ptr(), self.node_a.data_ptr(), self.rel.data_ptr(), E, R, n_a, n_rel,
-                int(self.node_b is not None), int(bool(wide_ids)), int(bool(balance)), chunk_edges, chunk_rows, piece_len,
-                chunks.data_ptr(), cap_chunks, long_rows.data_ptr(), cap_long,
-                packed.data_ptr() if packed is not None else None, PACK_SLACK, counts, temp.data_ptr(), temp.numel(),
-                torch.cuda.current_stream().cuda_stream))
+        _lib.launch(dev, "ultra_relcsr_plan", self.row, self.node_a, self.rel, E, R, n_a, n_rel,
+                    int(self.node_b is not None), int(bool(wide_ids)), int(bool(balance)), chunk_edges, chunk_rows, piece_len,
+                    chunks, cap_chunks, long_rows, cap_long, packed, PACK_SLACK, counts, temp, temp.numel())
         n_chunks, n_long, n_pieces, shift = (int(c) for c in counts)
         self.chunks = chunks[:n_chunks].clone()
         self.long_rows = long_rows[:n_long].clone()
@@ -212,28 +207,27 @@ class Segments:
             self.row_ptr = torch.searchsorted(self.row, rows).to(torch.int32).contiguous()
 
     def _refresh_struct(self):
-        s = self.struct
+        s, ptr = self.struct, _lib.ptr
         s.n_rows, s.n_edges = self.n_rows, self.n_edges
-        s.row = self.row.data_ptr()
-        s.node_a = self.node_a.data_ptr()
-        s.node_b = self.node_b.data_ptr() if self.node_b is not None else None
-        s.rel = self.rel.data_ptr()
-        s.weight = self.weight.data_ptr() if self.weight is not None else None
+        s.row = ptr(self.row)
+        s.node_a = ptr(self.node_a)
+        s.node_b = ptr(self.node_b)
+        s.rel = ptr(self.rel)
+        s.weight = ptr(self.weight)
         s.n_chunks = int(self.chunks.shape[0])
-        s.chunks = self.chunks.data_ptr()
+        s.chunks = ptr(self.chunks)
         s.n_long_rows = int(self.long_rows.shape[0])
-        s.long_rows = self.long_rows.data_ptr()
+        s.long_rows = ptr(self.long_rows)
         s.n_pieces = self.n_pieces
         s.piece_len = self.piece_len
-        s.packed = self.packed.data_ptr() if self.packed is not None else None
+        s.packed = ptr(self.packed)
         s.packed_src_shift = self.packed_src_shift
         s.n_hot = self.n_hot
-        s.hot_nodes = self.hot_nodes.data_ptr() if self.hot_nodes is not None else None
-        s.row_ptr = self.row_ptr.data_ptr() if self.row_ptr is not None else None
-        s.dense = self.dense.data_ptr() if self.dense is not None else None
+        s.hot_nodes = ptr(self.hot_nodes)
+        s.row_ptr = ptr(self.row_ptr)
+        s.dense = ptr(self.dense)
         s.dense_rows, s.dense_cols = self.dense_rows, self.dense_cols
-        dead = getattr(self, "packed_dead", None)
-        s.packed_dead = dead.data_ptr() if dead is not None else None
+        s.packed_dead = ptr(getattr(self, "packed_dead", None))
 
     def attach_dense(self, n_rows, n_cols, kind):
         """Build the plan's 0/1 matrix natively (``ultra_relcsr_dense``) and hang it on the struct.  ``kind`` 0: rows of the
@@ -243,9 +237,7 @@ class Segments:
         if size == 0 or self.weight is not None or not self.row.is_cuda:
             return False
         dense = torch.empty(size // 4, dtype=torch.int32, device=self.row.device)
-        with torch.cuda.device(self.row.device):
-            _lib.check(lib.ultra_relcsr_dense(self.pointer, n_rows, n_cols, kind, dense.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream))
+        _lib.launch(self.row.device, "ultra_relcsr_dense", self.pointer, n_rows, n_cols, kind, dense)
         self.dense, self.dense_rows, self.dense_cols = dense, int(n_rows), int(n_cols)
         self._refresh_struct()
         return True
@@ -442,13 +434,8 @@ class RelCSR:
         edge_of_input = torch.empty(n, dtype=torch.long, device=dev)
         temp = torch.empty(int(lib.ultra_relcsr_coalesce_temp_bytes(n)), dtype=torch.uint8, device=dev)
         n_unique, unit = ctypes.c_int64(0), ctypes.c_int(1)
-        with torch.cuda.device(dev):
-            _lib.check(lib.ultra_relcsr_coalesce(
-                dst.data_ptr(), src.data_ptr(), rel.data_ptr(), weight.data_ptr() if weight is not None else None, n, n_dst,
-                n_src, n_rel,
-                out_idx[0].data_ptr(), out_idx[1].data_ptr(), out_idx[2].data_ptr(), out_w.data_ptr(),
-                edge_of_input.data_ptr(), ctypes.byref(n_unique), ctypes.byref(unit), temp.data_ptr(), temp.numel(),
-                torch.cuda.current_stream().cuda_stream))
+        _lib.launch(dev, "ultra_relcsr_coalesce", dst, src, rel, weight, n, n_dst, n_src, n_rel, out_idx[0], out_idx[1], out_idx[2],
+                    out_w, edge_of_input, ctypes.byref(n_unique), ctypes.byref(unit), temp, temp.numel())
         m = int(n_unique.value)
         ids = out_idx[:, :m].long()        # int64: the by_src / by_rel sort keys are products of these
         return ids[0], ids[1], ids[2], out_w[:m].clone(), edge_of_input, bool(unit.value)
@@ -680,7 +667,6 @@ class RelCSR:
         all three plans by binary search in their sorted index arrays: no ``match``, no host synchronisation, static
         shapes (capturable).  Shares every index array and schedule with this object."""
         base = getattr(self, "_base", None) or self
-        lib = _lib.load()
         dev = self.device
         h, t, r = (x.reshape(-1).contiguous() for x in (h, t, r))
         E = base.n_edges
@@ -694,17 +680,11 @@ class RelCSR:
                 all(p.weight is None and p.packed is not None and p.packed_src_shift < 31
                     and (n_node - 1) >> (31 - p.packed_src_shift) == 0 for p in plans)):
             marks = [torch.empty(E + PACK_SLACK, dtype=torch.int32, device=dev) for _ in range(3)]
-        with torch.cuda.device(dev):
-            if marks[0] is not None:
-                _lib.check(lib.ultra_edge_removal_marks(
-                    plans[0].pointer, plans[1].pointer, plans[2].pointer, h.data_ptr(), t.data_ptr(), r.data_ptr(),
-                    h.numel(), int(n_base_rel), w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr(), PACK_SLACK,
-                    marks[0].data_ptr(), marks[1].data_ptr(), marks[2].data_ptr(), n_node, torch.cuda.current_stream().cuda_stream))
-            else:
-                _lib.check(lib.ultra_edge_removal_weights(
-                    plans[0].pointer, plans[1].pointer, plans[2].pointer, h.data_ptr(), t.data_ptr(), r.data_ptr(),
-                    h.numel(), int(n_base_rel), w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr(), PACK_SLACK,
-                    torch.cuda.current_stream().cuda_stream))
+        removal = (*[p.pointer for p in plans], h, t, r, h.numel(), int(n_base_rel), *w, PACK_SLACK)
+        if marks[0] is not None:
+            _lib.launch(dev, "ultra_edge_removal_marks", *removal, *marks, n_node)
+        else:
+            _lib.launch(dev, "ultra_edge_removal_weights", *removal)
         other = RelCSR.__new__(RelCSR)
         other.shape, other._opts = self.shape, self._opts
         other.chunk_edges, other.piece_len = self.chunk_edges, self.piece_len
