@@ -27,12 +27,18 @@ def _tail_with_both_directions(row_ptr, src):
 @pytest.mark.parametrize("K", [1, 3, 10, 32])
 def test_cpu_operator_equals_the_restatement(K):
     """Random graphs with duplicate triples, isolated nodes and self-loops; a row with more than 64 K candidates; near-equal and
-    exactly tied values; a tail with in- and out-edges and one without out-edges."""
+    exactly tied values; a tail with in- and out-edges and one without out-edges; a dense graph (mean in-degree above 48, the
+    one the GPU test runs on 64 lanes per row) with non-finite gradients."""
     cases = [coalesced_csr(1, 200, 3000, 5, isolated=20, self_loops=50, duplicates=300),
-             coalesced_csr(2, 3000, 4000 + 300 * K, 3, hub_row=7, hub_edges=300 * K + 300, duplicates=50)]
+             coalesced_csr(2, 3000, 4000 + 300 * K, 3, hub_row=7, hub_edges=300 * K + 300, duplicates=50),
+             coalesced_csr(9, 403, 40000, 11, isolated=15, hub_row=5, hub_edges=1500, self_loops=40, duplicates=200)]
     for i, (row_ptr, src) in enumerate(cases):
         n = row_ptr.numel() - 1
-        beams, grad = beam_inputs(10 + i, n, K, src.numel(), empty=0.1)
+        beams, grad = beam_inputs(10 + (3 if i == 2 else i), n, K, src.numel(), empty=0.1)     # the GPU test's seeds
+        if i == 2:
+            assert src.numel() // n >= 48
+            grad[::17] = float("nan")
+            grad[3::19] = float("inf")
         for tail in (_tail_with_both_directions(row_ptr, src), n - 1):
             got = _op(row_ptr, src, grad, beams, tail)
             want = beam_step(row_ptr, src, grad, beams, tail)

@@ -38,15 +38,21 @@ def _three_way(row_ptr, src, grad, beams, tail, dev):
 @pytest.mark.parametrize("K", [1, 3, 10, 32])
 def test_hip_operator_equals_cpu_operator_and_restatement(K):
     """The CPU test's cases (duplicates, isolated nodes, self-loops, a row of more than 64 K candidates, near-equal values, exact
-    ties, non-finite gradients, tails with and without out-edges) on the device."""
+    ties, non-finite gradients, tails with and without out-edges) on the device, one graph at least per group width (the lanes
+    per row follow the mean in-degree: 64 from 48 on, 32 from 24 on, else 16)."""
     dev = _dev()
     cases = [coalesced_csr(1, 200, 3000, 5, isolated=20, self_loops=50, duplicates=300),
              coalesced_csr(2, 3000, 4000 + 300 * K, 3, hub_row=7, hub_edges=300 * K + 300, duplicates=50),
-             coalesced_csr(5, 5000, 200000, 7, isolated=100)]          # mean degree 40: 32-lane groups
+             coalesced_csr(5, 5000, 200000, 7, isolated=100),
+             # 403 rows: the last block of four 64-lane groups is ragged
+             coalesced_csr(9, 403, 40000, 11, isolated=15, hub_row=5, hub_edges=1500, self_loops=40, duplicates=200)]
+    lanes = (16, 16, 32, 64)
     for i, (row_ptr, src) in enumerate(cases):
         n = row_ptr.numel() - 1
+        mean = src.numel() // n
+        assert {16: mean < 24, 32: 24 <= mean < 48, 64: mean >= 48}[lanes[i]], (i, mean)
         beams, grad = beam_inputs(10 + i, n, K, src.numel(), empty=0.1)
-        if i == 0:
+        if i in (0, 3):
             grad[::17] = float("nan")
             grad[3::19] = float("inf")
         deg_in = row_ptr[1:] - row_ptr[:-1]
@@ -55,12 +61,13 @@ def test_hip_operator_equals_cpu_operator_and_restatement(K):
 
 
 def test_hip_operator_on_a_two_million_node_graph_with_a_hub_row():
-    """2 M nodes, 6 M edges, one row of 60 000 in-edges (the Zipf heads of S-fb15k237 reach tens of thousands); 64-lane and
-    16-lane groups both run (mean degree 3 here; the hub row is walked by one 16-lane group)."""
+    """2 M nodes, 6 M edges, one row of 60 000 in-edges (the Zipf heads of S-fb15k237 reach tens of thousands); only 16-lane
+    groups run here (mean degree 3), the hub row is walked by one of them."""
     dev = _dev()
     n = 2_000_000
     row_ptr, src = coalesced_csr(7, n, 6_000_000, 20, hub_row=123_456, hub_edges=60_000)
     assert int(row_ptr[123_457] - row_ptr[123_456]) > 50_000
+    assert src.numel() // n < 24
     beams, grad = beam_inputs(8, n, 10, src.numel(), empty=0.2)
     hip = _three_way(row_ptr, src, grad, beams, 42, dev)
     assert torch.isfinite(hip[0][123_456]).all()

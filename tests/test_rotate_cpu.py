@@ -12,13 +12,14 @@ import pytest
 import torch
 
 import rotate_restatement as RR
-from graphs import random_graph
+from graphs import ROTATE_VARIANTS, random_graph
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rotate_handcomputed.json")
 CASES = {
     "d64_unit": (dict(n_edge=3000), 200, 7, 128, 64),
     "d32_weights_dups": (dict(n_edge=4000, weights=True, skew=True), 150, 5, 96, 32),
     "d6_hub_isolated": (dict(n_edge=3000, weights=True, hub_row=3, hub_edges=1200, isolated=30), 120, 9, 12, 6),
+    **ROTATE_VARIANTS,
 }
 
 
@@ -31,29 +32,60 @@ def _csr(g, n, r):
 @pytest.mark.parametrize("case", list(CASES))
 @pytest.mark.parametrize("sum", ["add", "min", "max"])
 def test_cpu_forward_and_backward_match_the_fp64_restatement(case, sum):
+    """Forward and both gradients of the CPU twin against fp64, entry by entry: |error| <= 1e-6 x the sum of the |terms| of
+    that entry (forward under min / max: the largest |terms| of one message of the row).  1e-6 is the forward yardstick
+    of this suite = 4 x the worst ratio of the fp32 ATen definition on these cases (2.4e-7).  Under min / max the output
+    gradient is zeroed in both runs where the fp64 runner-up is within 4e-6 of the winner (``RR.ambiguous_cells``: fp32 may
+    pick the other edge there); at most 0.1 % of the cells may be such, none an exact tie.
+
+    Measured max |error| / yardstick of the twin (forward, d_input, d_relation), add / min / max,
+    in units of 1e-7 (worst 3.22e-7):
+        d64_unit           1.38 1.51 2.23  /  1.15 1.42 1.39  /  1.07 1.72 1.28
+        d32_weights_dups   1.91 1.62 1.61  /  2.11 3.22 1.89  /  2.02 2.01 1.66
+        d6_hub_isolated    1.10 2.25 0.96  /  1.46 1.30 1.09  /  1.25 1.18 1.39
+        beyond_lds         1.82 2.53 1.80  /  1.42 1.47 1.44  /  1.42 1.60 1.44
+        straddle_hub       2.86 2.23 1.92  /  2.37 2.39 1.84  /  2.44 1.97 1.88
+        nine_tiles         1.89 1.69 1.56  /  1.12 1.61 1.71  /  1.12 1.67 1.77
+        eight_tiles        1.84 1.85 1.57  /  1.72 2.07 1.92  /  1.56 1.78 2.07
+        block2             0.91 0.92 1.18  /  1.10 1.09 1.09  /  1.11 0.98 0.94
+        unit_weights       1.48 1.86 1.14  /  1.11 1.35 1.83  /  1.01 1.51 1.70
+    At most 4 cells of a case are ambiguous (nine_tiles, min: 4 of 115 200)."""
     from ultra_torchdrug_amd import rotate_rspmm
     kw, n, r, F, block = CASES[case]
     g = random_graph(seed=len(case) + 3, n_node=n, n_rel=r, **kw)
     gen = torch.Generator().manual_seed(4)
     relation, x, grad = torch.randn(r, F, generator=gen), torch.randn(n, F, generator=gen), torch.randn(n, F, generator=gen)
+    dst, src, rel, w = RR.coalesce(g["dst"], g["src"], g["rel"], g["w"], n, r)
+    empty = torch.from_numpy(np.bincount(dst, minlength=n) == 0)
+    assert empty.any() == (kw.get("isolated", 0) > 0)
+    selected = None
+    if sum != "add":
+        selected = RR.selected_edges(dst, src, rel, w, relation, x, n, block, sum)
+        ambiguous = RR.ambiguous_cells(dst, src, rel, w, relation, x, n, block, sum)
+        cells = int((~empty).sum()) * F
+        print("%s %s: %d ambiguous cells of %d" % (case, sum, int(ambiguous.sum()), cells))
+        assert not RR.exact_ties(dst, selected, n).any()
+        assert int(ambiguous.sum()) <= 1e-3 * cells
+        grad = grad * ~ambiguous
+
     rel_t, x_t = relation.clone().requires_grad_(), x.clone().requires_grad_()
     out = rotate_rspmm(_csr(g, n, r), rel_t, x_t, sum=sum, block=block)
     out.backward(grad)
-
-    dst, src, rel, w = RR.coalesce(g["dst"], g["src"], g["rel"], g["w"], n, r)
     rel64, x64 = relation.double().requires_grad_(), x.double().requires_grad_()
     want = RR.rotate_rspmm(dst, src, rel, w, rel64, x64, n, block, sum)
-    scale = RR.abs_scale(dst, src, rel, w, relation, x, n, block)
-    assert ((out.detach().double() - want.detach()).abs() <= 1e-6 * scale + 1e-30).all()
-    empty = torch.from_numpy(np.bincount(dst, minlength=n) == 0)
-    assert empty.any() == (kw.get("isolated", 0) > 0)
+    want.backward(grad.double() * (~empty).unsqueeze(-1))
+
+    scale = (RR.abs_scale if sum == "add" else RR.abs_max_scale)(dst, src, rel, w, relation, x, n, block)
+    bound_x, bound_rel = RR.grad_abs_scale(dst, src, rel, w, relation, x, grad, block, selected)
     ident = {"add": 0.0, "min": RR.FLT_MAX, "max": -RR.FLT_MAX}[sum]
     assert (out.detach()[empty] == ident).all()
-    want.backward(grad.double() * (~empty).unsqueeze(-1))
-    for got, truth, factor in ((x_t.grad, x64.grad, relation), (rel_t.grad, rel64.grad, x)):
-        # terms of a gradient entry: |g| * |w| * |factor| summed over the edges that reach it (an upper bound for min / max)
-        bound = 1e-5 * (grad.abs().double().sum() * factor.abs().max().double() * float(np.abs(w).max())) + 1e-12
-        assert ((got.double() - truth).abs() <= bound).all()
+    for what, got, truth, bound in (("forward", out.detach(), want.detach(), scale), ("d_input", x_t.grad, x64.grad, bound_x),
+                                    ("d_relation", rel_t.grad, rel64.grad, bound_rel)):
+        err = (got.double() - truth).abs()
+        ratio = (err / (bound + 1e-24)).max().item()
+        print("%s %s %s: max err / yardstick %.3g" % (case, sum, what, ratio))
+        assert bound.max() > 0
+        assert (err <= 1e-6 * bound + 1e-30).all(), "%s: max err / yardstick %.3g" % (what, ratio)
 
 
 def test_duplicate_triples_are_merged_by_weight_sum():
