@@ -371,6 +371,18 @@ int ultra_rspmm_rotate_backward_f32(const ultra_segments *by_src_host, const ult
                                     size_t workspace_bytes, int64_t n_src, int64_t n_dst, int64_t n_rel, int64_t F,
                                     int64_t block, int sum_op, void *stream);
 
+/* d_weight of ultra_rspmm_rotate_forward_f32, one entry per edge of `fwd` in forward-plan order (written completely):
+ *     d_weight[e] = sum over the pairs of every query block of (g_re * y_re) + (g_im * y_im)
+ * with y the UNWEIGHTED message of edge e and g = output_grad[dst_e], masked per component for min / max by
+ * (output[dst_e] == w_e * y): every tied edge is fed, as in ultra_rspmm_rotate_backward_f32.  No workspace; the order of every
+ * operation is fixed (csrc/rotate.inc).  output: the forward result without the epilogue, required for min / max only.
+ * Errors, all before any device work: ULTRA_ERR_ABI for a foreign plan; ULTRA_ERR_BAD_SHAPE for F <= 0, block <= 0, odd block
+ * or F % block != 0; ULTRA_ERR_BAD_OP for an unknown sum_op; ULTRA_ERR_NULL_POINTER as in ultra_rspmm_backward_weight_f32.
+ * A plan without edges returns ULTRA_OK. */
+int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
+                                           const float *output, const float *output_grad, float *d_weight, int64_t n_rel,
+                                           int64_t F, int64_t block, int sum_op, void *stream);
+
 /*
  * One layer of the path beam search behind TransferNBFNet.visualize (csrc/beam_search.hip; DESIGN.md "Explaining a
  * prediction").  Over the coalesced dst-CSR of the graph with inverse edges:

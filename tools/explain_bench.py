@@ -1,16 +1,23 @@
 """Explaining one prediction (``TransferNBFNet.visualize``) at B = 1 on S-fb15k237 and S-stress (GPU only).
 
-    python tools/explain_bench.py [--workloads S-fb15k237,S-stress] [--reps 3] [--beams 10] [--json PATH]
+    python tools/explain_bench.py [--workloads S-fb15k237,S-stress] [--messages distmult] [--materialised S-fb15k237]
+                                  [--reps 3] [--beams 10] [--json PATH]
 
-Per workload: the shipped 6 x 64d entity stack (DistMult, sum, LayerNorm, shortcut, projected relations; seeded random init and
-random relation representations -- the relation stack is not part of an explanation), the graph with inverse edges and its plans
-built first.  Reported:
+Per workload and message function (``--messages distmult,rotate``): the shipped 6 x 64d entity stack (sum, LayerNorm, shortcut,
+projected relations; seeded random init and random relation representations -- the relation stack is not part of an
+explanation), the graph with inverse edges and its plans built first.  ``--materialised WORKLOADS``: on these workloads a second
+leg (``route: materialised``) with every layer on the materialised ``message()`` + ``aggregate()`` route -- for rotate messages
+what ``visualize`` ran before the native rotate edge gradient existed; never ask for it on S-stress, where ONE ``(E, D)``
+tensor is 25.6 GB.  Reported:
   * ``gradient_ms``: the per-layer edge gradients (``edge_gradients``: forward with leaf weights + ``autograd.grad``);
   * ``search_ms``: the beam search over all layers plus the path assembly (``visualize`` minus the gradient part);
   * ``peak_extra_bytes``: ``max_memory_allocated`` during one ``visualize`` above the allocation before it, and ``E * 64 * 4``, the
     size of ONE materialised (E, D) message tensor, beside it;
   * ``beam_kernel``: the ``ultra_beam_search_step_f32`` launch alone (device events around the C ABI call, median of ``--reps``
-    per layer, on that layer's real inputs) against its byte floor ``E (8 + 4 + 4K) + 4 (N + 1) + 12 N K``.
+    per layer, on that layer's real inputs) against its byte floor ``E (8 + 4 + 4K) + 4 (N + 1) + 12 N K``;
+  * ``weight_grad_kernel`` (rotate legs): the ``ultra_rspmm_rotate_backward_weight_f32`` launch alone (sum, F = 64, random
+    rows) against its byte floor: three rows of ``F`` floats (input, relation, output gradient), the three index words and the
+    ``d_weight`` word per edge, ``E (12 F + 16)``.
 Prints one JSON object; a workload that fails records the error instead of a result.
 """
 import argparse
@@ -26,7 +33,7 @@ import torch
 HBM_PEAK = 8.0e12      # bytes / s (MI355X_MICROARCH.md)
 
 
-def build(workload, dev, seed=1024):
+def build(workload, dev, message="distmult", seed=1024):
     from ultra_torchdrug_amd.data import SHAPES, synthetic_kg
     from ultra_torchdrug_amd.graph import Graph
     from ultra_torchdrug_amd.model import TransferNBFNet
@@ -38,7 +45,7 @@ def build(workload, dev, seed=1024):
     else:
         graph = synthetic_kg(workload, device=dev)
     torch.manual_seed(seed)
-    model = TransferNBFNet(input_dim=64, hidden_dims=[64] * 6, num_relation=graph.num_relation, message_func="distmult",
+    model = TransferNBFNet(input_dim=64, hidden_dims=[64] * 6, num_relation=graph.num_relation, message_func=message,
                            aggregate_func="sum", short_cut=True, layer_norm=True, project=True, mod=True).to(dev)
     rel = torch.randn(1, 2 * graph.num_relation, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(seed))
     return graph, model, rel
@@ -66,11 +73,36 @@ def kernel_ms(row_ptr, src, grad, beams, tail, reps):
     return times[len(times) // 2], out
 
 
-def run(workload, dev, reps, beams_k):
+def weight_grad_kernel_ms(csr, n_rel, dev, reps):
+    """The rotate d_weight launch alone on the graph's forward plan (F = block = 64, sum): median ms of ``reps`` launches."""
+    from ultra_torchdrug_amd import _lib
+    lib = _lib.load()
+    gen = torch.Generator(device=dev).manual_seed(7)
+    x, grad = (torch.randn(csr.shape[0], 64, device=dev, generator=gen) for _ in range(2))
+    relation = torch.randn(n_rel, 64, device=dev, generator=gen)
+    d_w = torch.empty(csr.n_edges, dtype=torch.float32, device=dev)
+    plan = csr.fwd
+    stream = torch.cuda.current_stream()
+    times = []
+    for _ in range(reps + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        _lib.check(lib.ultra_rspmm_rotate_backward_weight_f32(plan.pointer, relation.data_ptr(), x.data_ptr(), None, grad.data_ptr(),
+                                                              d_w.data_ptr(), n_rel, 64, 64, 0,
+                                                              ctypes.c_void_p(stream.cuda_stream)))
+        b.record(stream)
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    times = sorted(times[1:])
+    return times[len(times) // 2]
+
+
+def run(workload, dev, reps, beams_k, message="distmult", materialised=False):
     from ultra_torchdrug_amd import functional
-    rec = {"workload": workload, "B": 1, "num_beam": beams_k}
+    rec = {"workload": workload, "message": message, "route": "materialised" if materialised else "native", "B": 1,
+           "num_beam": beams_k}
     t0 = time.perf_counter()
-    graph, model, rel = build(workload, dev)
+    graph, model, rel = build(workload, dev, message)
     model.num_beam, model.path_topk = beams_k, 10
     und = model._undirected(graph)
     csr = und.relcsr
@@ -109,6 +141,13 @@ def run(workload, dev, reps, beams_k):
     rec["n_paths"] = len(paths)
     rec["top_path"] = [list(e) for e in paths[0]] if paths else None
     rec["top_weight"] = weights[0] if weights else None
+    if materialised:                 # the comparison leg: times and memory of the route, no kernel figures
+        return rec
+    if message == "rotate":
+        floor_w = E * (12 * 64 + 16)
+        ms = weight_grad_kernel_ms(csr, csr.shape[2], dev, max(reps, 5))
+        rec["weight_grad_kernel"] = {"byte_floor": floor_w, "ms": ms, "GB_per_s_of_floor": floor_w / ms / 1e6,
+                                     "fraction_of_hbm_peak": floor_w / (ms * 1e-3) / HBM_PEAK}
     # the beam kernel alone, per layer, on that layer's real inputs
     grads = model.edge_gradients(graph, [rel], [h], [t], [r])
     row_ptr, src, _, _ = csr.csr_arrays
@@ -130,6 +169,8 @@ def run(workload, dev, reps, beams_k):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="S-fb15k237,S-stress")
+    ap.add_argument("--messages", default="distmult", help="message functions, e.g. distmult,rotate")
+    ap.add_argument("--materialised", default="", help="workloads that also get a leg on the materialised route")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--beams", type=int, default=10)
     ap.add_argument("--json", default=None)
@@ -140,11 +181,19 @@ def main():
         raise SystemExit("explain_bench.py measures on an MI355X; no GPU is visible")
     dev = torch.device("cuda:0")
     out = {"device": torch.cuda.get_device_name(0), "results": []}
-    for workload in args.workloads.split(","):
+    from ultra_torchdrug_amd.layer import _RelationalConvBase
+    legs = [(w, m, False) for w in args.workloads.split(",") for m in args.messages.split(",")]
+    legs += [(w, m, True) for w in args.materialised.split(",") if w for m in args.messages.split(",")]
+    native_edge_grad = _RelationalConvBase.native_edge_grad
+    for workload, message, materialised in legs:
+        if materialised:            # every layer declines its native edge gradient: model._edge_grad_graph clones the graph
+            _RelationalConvBase.native_edge_grad = lambda self, *args: False
         try:
-            out["results"].append(run(workload, dev, args.reps, args.beams))
+            out["results"].append(run(workload, dev, args.reps, args.beams, message, materialised))
         except Exception as err:            # (out of memory on a smaller device, ...): recorded, not hidden
-            out["results"].append({"workload": workload, "error": "%s: %s" % (type(err).__name__, err)})
+            out["results"].append({"workload": workload, "message": message, "error": "%s: %s" % (type(err).__name__, err)})
+        finally:
+            _RelationalConvBase.native_edge_grad = native_edge_grad
         torch.cuda.empty_cache()
         print(json.dumps(out["results"][-1]), file=sys.stderr, flush=True)
     text = json.dumps(out, indent=1)

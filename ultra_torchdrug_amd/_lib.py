@@ -143,6 +143,7 @@ SIGNATURES = {
     "ultra_layer_score_forward_f32": (i32, [seg, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "ultra_rspmm_rotate_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]),
     "ultra_rspmm_rotate_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]),
+    "ultra_rspmm_rotate_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

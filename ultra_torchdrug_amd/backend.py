@@ -6,7 +6,7 @@ optional functions: a backend is an object with this complete interface
 
     accepts(tensor) -> bool            tensors this backend computes on (HIP library: ``tensor.is_cuda``)
     generalized_rspmm, rspmm_forward, rspmm_sum_plus, rspmm_frontier, frontier_supported, first_layer_forward, sum_layer,
-    remove_triples, rotate_rspmm, rotate_rspmm_forward
+    remove_triples, rotate_rspmm (with ``edge_weight=``, as generalized_rspmm), rotate_rspmm_forward, rotate_rspmm_backward_weight
     combine, linear_supported, linear_forward, relation_project, relation_project_train, score_all_entities
     filtered_rank, filtered_rank_keys, strict_negatives, statistics, bce_adversarial_loss, candidate_tiles, candidate_rows,
     score_candidates_supported, score_candidates

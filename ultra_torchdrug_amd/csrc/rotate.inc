@@ -12,6 +12,7 @@
 //   d_input     g = output_grad[dst], masked per component by (output == y) for min / max (every tied edge is fed):
 //               d_re = (g_re * r_re) + (g_im * r_im);   d_im = (g_im * r_re) - (g_re * r_im);   [d = w * d];   acc += d
 //   d_relation  the same with x for r:  d_re = (g_re * x_re) + (g_im * x_im);   d_im = (g_im * x_re) - (g_re * x_im)
+//   d_weight    y unweighted, g masked by (output == w * y):  acc += (g_re * y_re) + (g_im * y_im)   (rotate_weight_grad_kernel)
 //
 // Layout: one lane = one complex pair, one wave = 64 consecutive pairs (a pair tile: 128 columns, the re and im halves
 // each contiguous inside a query block).  Each gather is two fully used dword loads per wave.  The rows, chunks, pieces
@@ -333,4 +334,75 @@ int run_rotate_plan(const ultra_segments *seg, RotParams p, int64_t n_rel, int64
         HIP_TRY(hipGetLastError());
     }
     return ULTRA_OK;
+}
+
+// d_weight of the rotate forward, edges in forward-plan order (ultra_rspmm_rotate_backward_weight_f32):
+//     d_weight[e] = sum over the pairs of every query block of (g_re * y_re) + (g_im * y_im)
+// with y the UNWEIGHTED message of edge e = (u -> v, r, w) and g = output_grad[v], masked per component for min / max by
+// (output[v] == w * y) -- every tied edge is fed, as in the d_input / d_relation kernels above.
+// One lane = one pair, a wave walks an edge's pair tiles (two fully used dword loads per gathered row and tile), each lane
+// sums its tiles in tile order, then the __shfl_down tree.  TWO (n_pairs <= 32: the explain shape B = 1, D = 64 has 32 pairs):
+// a wave takes two consecutive edges, one per 32-lane half, so that no lane idles and a wave-instruction still moves two
+// whole 128-byte half rows; the tree then stops at offset 16.  Every d_weight entry is written.
+template <int SUM, bool UNIT_W, bool TWO>
+__global__ __launch_bounds__(256) void rotate_weight_grad_kernel(const int32_t *row, const int32_t *src, const int32_t *rel,
+                                                                 const float *weight, const float *relation,
+                                                                 const float *input, const float *output, const float *grad,
+                                                                 float *d_weight, long long F, int half, int n_pairs,
+                                                                 long long n_edges) {
+    constexpr int G = TWO ? 32 : 64;                 // lanes per edge
+    const int lane = threadIdx.x & 63;
+    const int sub = TWO ? (lane >> 5) : 0;
+    const int l = lane & (G - 1);
+    const long long waves_total = ((long long)gridDim.x * blockDim.x) >> 6;
+    const long long n_slots = TWO ? (n_edges + 1) / 2 : n_edges;
+    long long slot = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    for (; slot < n_slots; slot += waves_total) {
+        const long long e = TWO ? slot * 2 + sub : slot;
+        const bool live = e < n_edges;               // the odd last edge leaves the upper half of its wave without one
+        const long long ec = live ? e : n_edges - 1;
+        const long long v = row[ec], u = src[ec], r = rel[ec];
+        float wk = 1.0f;
+        if constexpr (!UNIT_W) wk = weight[ec];
+        float acc = 0.0f;
+        for (int pair = l; pair < n_pairs; pair += G) {
+            const int bq = pair / half;
+            const long long cre = (long long)bq * (2 * half) + (pair - bq * half);
+            const long long cim = cre + half;
+            float yr, yi;
+            rotate_message(input[u * F + cre], input[u * F + cim], relation[r * F + cre], relation[r * F + cim], yr, yi);
+            float gr = grad[v * F + cre], gi = grad[v * F + cim];
+            if constexpr (SUM != ULTRA_SUM_ADD) {
+                float mr = yr, mi = yi;
+                if constexpr (!UNIT_W) { mr = wk * yr; mi = wk * yi; }
+                gr = gr * ((output[v * F + cre] == mr) ? 1.0f : 0.0f);
+                gi = gi * ((output[v * F + cim] == mi) ? 1.0f : 0.0f);
+            }
+            const float a = gr * yr, b = gi * yi;
+            acc = acc + (a + b);
+        }
+#pragma unroll
+        for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if (l == 0 && live) d_weight[e] = acc;
+    }
+}
+
+template <int SUM>
+void launch_rotate_weight_grad(const ultra_segments *fwd, const float *relation, const float *input, const float *output,
+                               const float *grad, float *d_weight, long long F, int half, hipStream_t s) {
+    const int n_pairs = (int)(F / 2);
+    const bool two = n_pairs <= 32, unit = fwd->weight == nullptr;
+    const long long n_slots = two ? (fwd->n_edges + 1) / 2 : fwd->n_edges;
+    long long blocks = (n_slots + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+#define ULTRA_RWCASE(U, T)                                                                                                  \
+    if (unit == U && two == T)                                                                                              \
+        hipLaunchKernelGGL((rotate_weight_grad_kernel<SUM, U, T>), dim3((int)blocks), dim3(256), 0, s, fwd->row, fwd->node_a, \
+                           fwd->rel, fwd->weight, relation, input, output, grad, d_weight, F, half, n_pairs,               \
+                           (long long)fwd->n_edges);
+    ULTRA_RWCASE(true, true)
+    ULTRA_RWCASE(true, false)
+    ULTRA_RWCASE(false, true)
+    ULTRA_RWCASE(false, false)
+#undef ULTRA_RWCASE
 }

@@ -2107,6 +2107,27 @@ int ultra_rspmm_rotate_backward_f32(const ultra_segments *by_src, const ultra_se
     return ULTRA_OK;
 }
 
+int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd, const float *relation, const float *input,
+                                           const float *output, const float *output_grad, float *d_weight, int64_t n_rel,
+                                           int64_t F, int64_t block, int sum_op, void *stream) {
+    int rc = check_segments(fwd);
+    if (rc) return rc;
+    (void)n_rel;
+    if (F <= 0 || F > 0x7ffffffeLL || block <= 0 || block % 2 != 0 || F % block != 0) return ULTRA_ERR_BAD_SHAPE;
+    if (sum_op < 0 || sum_op > 2) return ULTRA_ERR_BAD_OP;
+    if (fwd->n_edges == 0) return ULTRA_OK;
+    if (relation == nullptr || input == nullptr || output_grad == nullptr || d_weight == nullptr)
+        return ULTRA_ERR_NULL_POINTER;
+    if (sum_op != ULTRA_SUM_ADD && output == nullptr) return ULTRA_ERR_NULL_POINTER;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int half = (int)(block / 2);
+    if (sum_op == ULTRA_SUM_ADD) launch_rotate_weight_grad<ULTRA_SUM_ADD>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
+    else if (sum_op == ULTRA_SUM_MIN) launch_rotate_weight_grad<ULTRA_SUM_MIN>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
+    else launch_rotate_weight_grad<ULTRA_SUM_MAX>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
 
 static int combine_launch(const CombineParams &p, void *stream) {
     int dev = 0;

@@ -766,6 +766,39 @@ std::tuple<Tensor, Tensor> rspmm_rotate_plan_bwd(const optional<Tensor> &by_src,
     return {d_input, d_relation};
 }
 
+// d(edge weights) of rspmm_rotate_plan_fwd: (n_edges,) in forward-plan order (ultra_rspmm_rotate_backward_weight_f32)
+Tensor rspmm_rotate_plan_bwd_weight(const Tensor &plan, const Tensor &relation, const Tensor &input, const optional<Tensor> &output,
+                                    const Tensor &output_grad, int64_t block, int64_t sum_op) {
+    const ultra_segments *seg = plan_of(plan, "plan");
+    TORCH_CHECK(seg != nullptr, "ultra_mi::rspmm_rotate_plan_bwd_weight: plan is required");
+    check_dense(input, "input", at::kFloat, input);
+    check_dense(relation, "relation", at::kFloat, input);
+    check_dense(output_grad, "output_grad", at::kFloat, input);
+    TORCH_CHECK(input.dim() == 2 && relation.dim() == 2 && input.size(1) == relation.size(1),
+                "ultra_mi::rspmm_rotate_plan_bwd_weight: relation (R, F) and input (n_src, F) expected");
+    const int64_t F = input.size(1), n_rel = relation.size(0);
+    check_rotate(F, block, sum_op);
+    TORCH_CHECK(output_grad.dim() == 2 && output_grad.size(0) == seg->n_rows && output_grad.size(1) == F,
+                "ultra_mi::rspmm_rotate_plan_bwd_weight: output_grad must be (", seg->n_rows, ", ", F, ")");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    Tensor rl = relation.contiguous(), x = input.contiguous(), g = output_grad.contiguous(), o;
+    if (output.has_value() && output->defined()) {
+        check_dense(*output, "output", at::kFloat, input);
+        TORCH_CHECK(output->sizes() == output_grad.sizes(),
+                    "ultra_mi::rspmm_rotate_plan_bwd_weight: output must have the shape of output_grad");
+        o = output->contiguous();
+    }
+    TORCH_CHECK(sum_op == 0 || o.defined(), "ultra_mi::rspmm_rotate_plan_bwd_weight: min / max aggregation needs the forward output");
+    Tensor d_weight = at::empty({seg->n_edges}, input.options());
+    if (seg->n_edges == 0) return d_weight;
+    check_status(ultra_rspmm_rotate_backward_weight_f32(seg, rl.data_ptr<float>(), x.data_ptr<float>(),
+                                                        o.defined() ? o.data_ptr<float>() : nullptr, g.data_ptr<float>(),
+                                                        d_weight.data_ptr<float>(), n_rel, F, block, (int)sum_op,
+                                                        current_stream(input)),
+                 "ultra_rspmm_rotate_backward_weight_f32");
+    return d_weight;
+}
+
 template <int SUM, bool HAS_W>
 void rotate_rows_cpu(const int *row_ptr, const int *src, const int *rel, const float *w, const float *relation, const float *x,
                      float *out, int64_t n_rows, int64_t F, int64_t half) {
@@ -1081,6 +1114,8 @@ TORCH_LIBRARY(ultra_mi, m) {
           "Tensor? boundary_value, int n_src, int block, int sum_op) -> Tensor");
     m.def("rspmm_rotate_plan_bwd(Tensor? by_src, Tensor? by_rel, Tensor relation, Tensor input, Tensor? output, "
           "Tensor output_grad, int n_src, int n_dst, int block, int sum_op) -> (Tensor, Tensor)");
+    m.def("rspmm_rotate_plan_bwd_weight(Tensor plan, Tensor relation, Tensor input, Tensor? output, Tensor output_grad, int block, "
+          "int sum_op) -> Tensor");
 }
 
 // rotate messages: the raw-CSR operators have a CPU kernel only (device tensors take the plan forms)
@@ -1092,6 +1127,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CPU, m) {
 TORCH_LIBRARY_IMPL(ultra_mi, CompositeExplicitAutograd, m) {
     m.impl("rspmm_rotate_plan_fwd", rspmm_rotate_plan_fwd);
     m.impl("rspmm_rotate_plan_bwd", rspmm_rotate_plan_bwd);
+    m.impl("rspmm_rotate_plan_bwd_weight", rspmm_rotate_plan_bwd_weight);
 }
 
 TORCH_LIBRARY_IMPL(ultra_mi, Autograd, m) {

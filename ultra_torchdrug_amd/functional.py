@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward","first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1547,11 +1547,33 @@ def rotate_rspmm_backward(csr, relation, input, output, output_grad, sum="add", 
     return d_input, d_relation
 
 
+def rotate_rspmm_backward_weight(csr, relation, input, output, output_grad, sum="add", block=64):
+    """d(weights) of the coalesced edges (forward-plan order) of :func:`rotate_rspmm_forward`
+    (``ultra_rspmm_rotate_backward_weight_f32``); ``output`` is the forward result without the epilogue (read for min / max only)."""
+    sum_op, block = _rotate_ops(csr, relation, input, sum, block, True)
+    relation, input, output_grad = relation.contiguous(), input.contiguous(), output_grad.contiguous()
+    output = output.contiguous() if output is not None else None
+    if _torch_ext.binding() == "torch":
+        return _torch_ext.load().rspmm_rotate_plan_bwd_weight(csr.fwd.plan_tensor, relation, input, output, output_grad, block,
+                                                              sum_op)
+    d_w = torch.empty(csr.n_edges, dtype=torch.float32, device=input.device)
+    if csr.n_edges == 0:
+        return d_w
+    _launch(input.device, "ultra_rspmm_rotate_backward_weight_f32", csr.fwd.pointer, relation, input, output, output_grad, d_w,
+            csr.shape[2], input.shape[1], block, sum_op)
+    return d_w
+
+
 class _RotateFunction(torch.autograd.Function):
-    """Autograd of :func:`rotate_rspmm` on device tensors; ``add_rows`` / ``(b_node, b_value)`` as in :class:`_RSPMMFunction`."""
+    """Autograd of :func:`rotate_rspmm` on device tensors; ``add_rows`` / ``(b_node, b_value)`` / ``edge_weight`` as in
+    :class:`_RSPMMFunction`."""
 
     @staticmethod
-    def forward(ctx, relation, input, csr, sum, block, add_rows=None, b_node=None, b_value=None):
+    def forward(ctx, relation, input, csr, sum, block, add_rows=None, b_node=None, b_value=None, edge_weight=None):
+        # edge_weight: fp32 (csr.n_edges,) weights of the COALESCED edges (forward-plan order) that replace csr's own; its
+        # gradient is rotate_rspmm_backward_weight's d_w
+        if edge_weight is not None:
+            csr = csr.with_coalesced_weights(edge_weight.detach())
         boundary = None if b_node is None else (b_node, b_value.detach())
         out = rotate_rspmm_forward(csr, relation, input, sum, block, add_rows=add_rows, boundary=boundary)
         ctx.csr, ctx.sum, ctx.block = csr, sum, block
@@ -1568,10 +1590,13 @@ class _RotateFunction(torch.autograd.Function):
         d_value = None
         if ctx.b_node is not None and ctx.needs_input_grad[7]:
             d_value = _boundary_value_grad(output_grad, ctx.b_node)
-        return d_relation, d_input, None, None, None, d_add, None, d_value
+        d_edge = None
+        if len(ctx.needs_input_grad) > 8 and ctx.needs_input_grad[8]:
+            d_edge = rotate_rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.block)
+        return d_relation, d_input, None, None, None, d_add, None, d_value, d_edge
 
 
-def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, boundary=None):
+def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, boundary=None, edge_weight=None):
     r"""Relational sparse-dense product with RotatE messages (the ``message_func="rotate"`` layers without an ``(E, F)`` tensor).
 
     .. math::  out_{v,:} = \bigoplus_{(v, u, r) \in sparse} w_{vur} \cdot (input_{u,:} \circledast relation_{r,:})
@@ -1582,7 +1607,9 @@ def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, bo
     differentiable in ``relation`` and ``input``, on CPU tensors (``torch.ops.ultra_mi.rspmm_rotate_fwd``, every row strictly
     sequentially) or MI355X tensors (the plan kernels of ``csrc/rotate.inc``).  The sparse values may not require grad.
     Extension (device tensors, ``sum="add"``): ``add_rows`` / ``boundary = (node, value)`` -- the epilogue ``+ boundary`` inside
-    the kernel, differentiable in ``add_rows`` / ``value`` (see :func:`rspmm_forward`)."""
+    the kernel, differentiable in ``add_rows`` / ``value`` (see :func:`rspmm_forward`).  ``edge_weight`` (MI355X only): fp32
+    ``(n_edges,)`` weights of the COALESCED edges in forward-plan order used instead of the adjacency's own, as in
+    :func:`generalized_rspmm`; differentiable -- its gradient is :func:`rotate_rspmm_backward_weight`."""
     if sum not in _lib.SUM_OPS:
         raise ValueError("Can't find a rotate rspmm operator for sum=`%s` (expected add, min or max)" % sum)
     csr, sparse_leaf = _as_relcsr(sparse)
@@ -1592,13 +1619,16 @@ def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, bo
     if (add_rows is not None or boundary is not None) and sum != "add":
         raise RuntimeError("rotate_rspmm: the fused boundary is for sum aggregation (max: torch.max after the call)")
     sum_op, block = _rotate_ops(csr, relation, input, sum, block, False)
+    _check_edge_weight(csr, sparse_leaf, edge_weight, input)
     if not input.is_cuda:
+        if edge_weight is not None:
+            raise RuntimeError("rotate_rspmm: edge_weight runs on an MI355X (HIP) device only")
         if add_rows is not None or boundary is not None:
             raise RuntimeError("rotate_rspmm: the fused boundary runs on an MI355X (HIP) device only")
         row_ptr, src, rel, w = csr.csr_arrays
         return _torch_ext.load().rspmm_rotate_fwd(row_ptr, src, rel, w, relation, input, block, sum_op)
     b_node, b_value = boundary if boundary is not None else (None, None)
-    return _RotateFunction.apply(relation, input, csr, sum, block, add_rows, b_node, b_value)
+    return _RotateFunction.apply(relation, input, csr, sum, block, add_rows, b_node, b_value, edge_weight)
 
 
 BEAM_MAX = 32        # beams per node the beam-search step takes (csrc/beam_search.hip: register top-K of at most 32)

@@ -186,12 +186,24 @@ class _RelationalConvBase(nn.Module):
                              relu=self.activation is F.relu, shortcut=shortcut, input_is_boundary=input_is_boundary,
                              grad_tiles=grad_tiles, grad_rows=grad_rows)
 
-    def native_edge_grad(self):
+    def native_edge_grad(self, graph=None, input=None):
         """Whether ``bellmanford(separate_grad="native")`` gives this layer a leaf weight per COALESCED edge on the rspmm route
-        (``functional.generalized_rspmm(edge_weight=...)``): summed or max-aggregated DistMult / TransE messages.  ``mean`` and
-        ``pna`` (their degree scaling reads the edge list) and ``rotate`` keep the materialised message route."""
+        (``functional.generalized_rspmm(edge_weight=...)`` / ``functional.rotate_rspmm(edge_weight=...)``): sum or max of
+        DistMult / TransE messages; sum or max of rotate messages of an even width in fp32 (``input``: the layers' input, the
+        conditions of :meth:`_rotate_aggregate`); and ``mean`` over any of the three on a graph whose coalesced weights are all
+        one (``graph.relcsr.unit_weight``) -- the native divisor ``degree_out + 1`` is then the COUNT the materialised
+        ``scatter(..., "mean")`` divides by, and it does not depend on the leaf.  ``mean`` on other graphs, ``pna`` (its degree
+        scaling reads the edge list) and everything else keep the materialised message route."""
         kind = self.aggregate_func[:-len("_nobound")] if self.aggregate_func.endswith("_nobound") else self.aggregate_func
-        return kind in ("sum", "max") and self.message_func in self.message2mul
+        if self.message_func == "rotate":
+            # (the rotate route has no _nobound forms)
+            if kind != self.aggregate_func or self.input_dim % 2 or (input is not None and input.dtype != torch.float32):
+                return False
+        elif self.message_func not in self.message2mul:
+            return False
+        if self.aggregate_func == "mean":
+            return graph is not None and bool(graph.relcsr.unit_weight)
+        return kind in ("sum", "max")
 
     def _no_grad(self, *tensors):
         return not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors if t is not None)
@@ -345,7 +357,7 @@ class _RelationalConvBase(nn.Module):
         """``aggregate(message(graph, input))`` for rotate messages with sum / mean / max through the native operator
         (``functional.rotate_rspmm``): no ``(E, B, D)`` tensor.  The same boundary handling as the DistMult branches above:
         fused in the kernel in inference, ``add_rows`` or the sparse form in training sums, ``torch.max`` after an unfused
-        max in training."""
+        max in training.  ``graph.native_edge_weight`` (:meth:`native_edge_grad`) is handed to the operator as ``edge_weight``."""
         batch_size, dim = len(graph.query), input.shape[-1]
         input = input.flatten(1)
         boundary = graph.boundary.flatten(1)
@@ -359,12 +371,16 @@ class _RelationalConvBase(nn.Module):
         reduce = "max" if self.aggregate_func == "max" else "add"
         sparse_bound = getattr(graph, "boundary_sparse", None)
         bound_args = dict(add_rows=boundary) if sparse_bound is None else dict(boundary=sparse_bound)
-        if ops.accepts(input) and self._no_grad(input, relation_input, boundary):
+        # bellmanford(separate_grad="native"): this layer's own leaf weight per coalesced edge -- the autograd route, never the
+        # forward-only entry
+        edge_weight = getattr(graph, "native_edge_weight", None)
+        ew = {} if edge_weight is None else dict(edge_weight=edge_weight)
+        if ops.accepts(input) and edge_weight is None and self._no_grad(input, relation_input, boundary):
             update = ops.rotate_rspmm_forward(adjacency, relation_input, input, reduce, dim, **bound_args)
         elif reduce == "max":
-            update = torch.max(ops.rotate_rspmm(adjacency, relation_input, input, "max", dim), boundary)
+            update = torch.max(ops.rotate_rspmm(adjacency, relation_input, input, "max", dim, **ew), boundary)
         elif ops.accepts(input):
-            update = ops.rotate_rspmm(adjacency, relation_input, input, "add", dim, **bound_args)
+            update = ops.rotate_rspmm(adjacency, relation_input, input, "add", dim, **bound_args, **ew)
         else:
             update = ops.rotate_rspmm(adjacency, relation_input, input, "add", dim) + boundary
         if self.aggregate_func == "mean":

@@ -198,13 +198,15 @@ class TransferNBFNet(nn.Module):
     @staticmethod
     def _edge_grad_graph(graph, conv, query, boundary):
         """The step graph of one layer under ``bellmanford(separate_grad="native")``.  On the device, for the layers that
-        have it (``conv.native_edge_grad()``: sum / max of DistMult / TransE messages), a shallow copy of ``graph`` whose
-        ``native_edge_weight`` -- a leaf copy of the COALESCED weights of ``graph.relcsr`` -- the layer hands to the rspmm
-        (``functional.generalized_rspmm(edge_weight=...)``): the non-fused epilogue, no fused layer, no sparse first-layer or
-        dense shortcut, no ``(E, D)`` message tensor.  Otherwise (``mean``, ``pna``, ``rotate``; CPU tensors) a clone on the
-        materialised message route (layer.py ``message`` / ``aggregate``) whose ``edge_weight`` is a leaf, one entry per
-        ORIGINAL edge.  ``edge_grad_leaf`` names the leaf, ``edge_grad_coalesced`` its order."""
-        if conv.native_edge_grad() and backend.get().accepts(boundary):
+        have it (``conv.native_edge_grad(graph, boundary)``: sum / max of DistMult / TransE / rotate messages, and their mean on
+        a unit-weight graph), a shallow copy of ``graph`` whose ``native_edge_weight`` -- a leaf copy of the COALESCED weights
+        of ``graph.relcsr`` -- the layer hands to the rspmm (``functional.generalized_rspmm(edge_weight=...)`` /
+        ``functional.rotate_rspmm(edge_weight=...)``): the non-fused epilogue, no fused layer, no sparse first-layer or dense
+        shortcut, no ``(E, D)`` message tensor.  Otherwise (``pna``; ``mean`` on a weighted graph; rotate of an odd width or
+        not in fp32; CPU tensors) a clone on the materialised message route (layer.py ``message`` / ``aggregate``) whose
+        ``edge_weight`` is a leaf, one entry per ORIGINAL edge.  ``edge_grad_leaf`` names the leaf, ``edge_grad_coalesced``
+        its order."""
+        if backend.get().accepts(boundary) and conv.native_edge_grad(graph, boundary):
             import copy
             step = copy.copy(graph)
             step.native_edge_weight = graph.relcsr.weight.detach().clone().requires_grad_()
@@ -251,9 +253,10 @@ class TransferNBFNet(nn.Module):
     def edge_gradients(self, graph, rel_query_list, h_index, t_index, r_index, with_ids=False):
         """The gradient of the score of ONE triple with respect to every layer's edge weights (model.py:394-409), one tensor
         per layer, one entry per COALESCED edge of ``graph``'s graph with inverse edges (``relcsr`` order: ``dst`` / ``src`` /
-        ``rel_id``).  ``bellmanford(separate_grad="native")``: on the device the sum / max layers of DistMult / TransE messages
-        take the rspmm route with a leaf weight vector per layer (no ``(E, D)`` message tensor); the other layers, and CPU
-        tensors, the materialised message route.  Only the edge-weight leaves are differentiated (``torch.autograd.grad``):
+        ``rel_id``).  ``bellmanford(separate_grad="native")``: on the device the sum / max layers of DistMult / TransE / rotate
+        messages, and mean layers on a unit-weight graph, take the rspmm route with a leaf weight vector per layer (no
+        ``(E, D)`` message tensor); the other layers (:meth:`_edge_grad_graph`), and CPU tensors, the materialised message
+        route.  Only the edge-weight leaves are differentiated (``torch.autograd.grad``):
         parameters' ``.grad`` stay as they are.  ``with_ids``: also return the host ids ``(h, t, r)``."""
         dev = self.device
         h_index, t_index, r_index = (torch.as_tensor(x, device=dev).reshape(-1).long() for x in (h_index, t_index, r_index))
