@@ -1214,9 +1214,9 @@ class _RSPMMFunction(torch.autograd.Function):
         ctx.has_add_rows = add_rows is not None
         ctx.b_node = b_node
         ctx.csr, ctx.sum, ctx.mul = csr, sum, mul
-        ctx.sparse_meta = None
+        ctx.sparse_shape = None
         if sparse is not None and sparse.requires_grad:
-            ctx.sparse_meta = (sparse._indices(), tuple(sparse.shape))
+            ctx.sparse_shape = tuple(sparse.shape)
         ctx.save_for_backward(relation, input, out if (sum != "add") else None)
         return out
 
@@ -1227,11 +1227,14 @@ class _RSPMMFunction(torch.autograd.Function):
         d_input, d_relation = rspmm_backward(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul,
                                              need_input=need_in, need_relation=need_rel)
         d_sparse = None
-        if ctx.sparse_meta is not None and ctx.needs_input_grad[0]:
+        if ctx.sparse_shape is not None and ctx.needs_input_grad[0]:
             d_w = rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul)
-            indices, shape = ctx.sparse_meta
-            # duplicates of one triple all receive its gradient
-            d_sparse = torch.sparse_coo_tensor(indices, d_w[ctx.csr.edge_of_input], shape)
+            # one entry per COALESCED edge ((dst, src, rel) order: a coalesced COO tensor), so that every duplicate of a triple
+            # receives its gradient once: autograd coalesces the gradient of a sparse constructor before it reads the values'
+            # share, and an entry per ORIGINAL edge would hand each duplicate the gradient times the triple's multiplicity
+            csr = ctx.csr
+            d_sparse = torch.sparse_coo_tensor(torch.stack([csr.dst, csr.src, csr.rel_id]), d_w, ctx.sparse_shape,
+                                               is_coalesced=True)
         d_add = output_grad if (ctx.has_add_rows and ctx.needs_input_grad[6]) else None
         d_value = None
         if ctx.b_node is not None and ctx.needs_input_grad[8]:
