@@ -625,7 +625,7 @@ int ultra_filtered_rank(const float *pred, int64_t n_query, int64_t n_cand, int6
 /*
  * Per-step index work from SORTED KEY ARRAYS instead of dense (B, N) masks (csrc/sampler.inc).  A graph keeps, per
  * direction, the sorted DISTINCT int64 keys  (anchor * n_rel + rel) * n_node + other  of its triples: for tail
- * prediction anchor = head, other = tail; for head prediction anchor = tail, other = head.  All three calls only
+ * prediction anchor = head, other = tail; for head prediction anchor = tail, other = head.  All these calls only
  * enqueue work: no allocation, no host synchronisation, capturable into a hipGraph.
  *
  * ultra_filtered_rank_keys: get_ranking (ultra/task.py:307-315) with the filter mask of ultra/task.py:65-100 looked up
@@ -643,6 +643,17 @@ int ultra_filtered_rank(const float *pred, int64_t n_query, int64_t n_cand, int6
  *   weights (1.0 when NULL, 1.0 in the slack) except 0.0 at every edge (h, t, r) / (t, h, r + n_base_rel) of the
  *   n_pattern triples that exists -- duplicates of a triple are one coalesced edge, so all of them go, as in the
  *   reference.  Triples that are not edges (the negatives of the batch) change nothing.
+ * ultra_filter_counts: n_free[q] = n_node - #{keys of (anchor_q, rel_q, ?)} = mask.sum(-1) of the filter mask of
+ *   ultra/task.py:65-100, the denominator of the sampled metrics hits@K_N (ultra/task.py:498).  anchor / rel are read at
+ *   [q * index_stride]; keys == NULL (unfiltered ranking): n_node.
+ * ultra_sampled_rank_keys: toy_eval of ultra/task.py:474-484 -- per query S_eff = min(n_sample, n_free) distinct entities
+ *   that do not complete (anchor_q, rel_q, ?), drawn WITHOUT replacement, and optimistic[q] = #{pos < pred[q, e]},
+ *   pessimistic[q] = #{pos <= pred[q, e]} over them.  The draw is defined by rand fp32 [n_query, n_sample] in [0, 1):
+ *   for j = 0 .. S_eff - 1 with m = n_free - j:  k = min((long long)(rand[q, j] * (float)m), m - 1)  (fp32 product,
+ *   truncated), then for every earlier chosen free-rank c in ascending order `if (c <= k) ++k`; k is the j-th chosen
+ *   free-rank and its entity the k-th entity (ascending) outside the completions.  samples (optional, NULL: not written):
+ *   int64 [n_query, n_sample] drawn entities in draw order, -1 in the unused slots.  pred / target / anchor / rel are
+ *   addressed as in ultra_filtered_rank_keys.  1 <= n_sample <= 64, ULTRA_ERR_BAD_SHAPE otherwise.
  */
 int ultra_filtered_rank_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t row_stride, const int64_t *target,
                              int64_t target_stride, const int64_t *keys, int64_t n_keys, const int64_t *anchor,
@@ -650,6 +661,12 @@ int ultra_filtered_rank_keys(const float *pred, int64_t n_query, int64_t n_cand,
                              void *stream);
 int ultra_strict_negative(const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel, int64_t n_query,
                           int64_t n_rel, int64_t n_node, const float *rand, int64_t n_sample, int64_t *out, void *stream);
+int ultra_filter_counts(const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel, int64_t index_stride,
+                        int64_t n_query, int64_t n_rel, int64_t n_node, int64_t *n_free, void *stream);
+int ultra_sampled_rank_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t row_stride, const int64_t *target,
+                            int64_t target_stride, const int64_t *keys, int64_t n_keys, const int64_t *anchor,
+                            const int64_t *rel, int64_t index_stride, int64_t n_rel, const float *rand, int64_t n_sample,
+                            int64_t *optimistic, int64_t *pessimistic, int64_t *samples, void *stream);
 int ultra_edge_removal_weights(const ultra_segments *fwd, const ultra_segments *by_src, const ultra_segments *by_rel,
                                const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_pattern,
                                int64_t n_base_rel, float *w_fwd, float *w_src, float *w_rel, int64_t slack, void *stream);

@@ -10,6 +10,7 @@ optional functions: a backend is an object with this complete interface
     combine, linear_supported, linear_forward, relation_project, relation_project_train, score_all_entities
     filtered_rank, filtered_rank_keys, strict_negatives, statistics, bce_adversarial_loss, candidate_tiles, candidate_rows,
     score_candidates_supported, score_candidates
+    filter_counts, sampled_rank_keys   (reached ONLY when the task has a sampled metric ``hits@K_N`` or ``toy_eval``)
 
 The parity tests install a second implementation of the same interface (``tests/oracle_ops.py``: the CPU oracle
 behind every operator) with :func:`use`, so that the SAME model code yields the oracle-side numbers; nothing under

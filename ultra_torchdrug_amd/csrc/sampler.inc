@@ -115,6 +115,97 @@ __global__ __launch_bounds__(256) void strict_negative_kernel(const int64_t *key
     out[i] = k + lo;
 }
 
+// n_free[q] = n_node - #{keys in [(anchor_q * n_rel + rel_q) * n_node, ... + n_node)}: `mask.sum(-1)` of the filter mask
+// (ultra/task.py:65-100; the keys are distinct), the denominator of the sampled metrics (ultra/task.py:498).  Two
+// binary searches per query, one thread each.
+__global__ __launch_bounds__(256) void filter_counts_kernel(const int64_t *keys, long long n_keys, const int64_t *anchor,
+                                                            const int64_t *rel, long long index_stride, long long n_query,
+                                                            long long n_rel, long long n_node, int64_t *n_free) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_query) return;
+    long long n_excl = 0;
+    if (keys != nullptr) {
+        const int64_t base = (anchor[q * index_stride] * n_rel + rel[q * index_stride]) * n_node;
+        n_excl = lower_bound_i64(keys, n_keys, base + n_node) - lower_bound_i64(keys, n_keys, base);
+    }
+    n_free[q] = n_node - n_excl;
+}
+
+constexpr int kSampledMax = 64;               // draws per query: one lane each
+constexpr int kSampledWaves = 4;              // queries per workgroup: one wave each
+
+// toy_eval of the reference (ultra/task.py:474-484): S_eff = min(S, n_free) DISTINCT entities that do not complete
+// (anchor_q, rel_q, ?), drawn without replacement, and the positive ranked among their scores:
+//     optimistic[q] = #{pos < pred[q, e]},  pessimistic[q] = #{pos <= pred[q, e]}.
+// The draw is defined by the uniform numbers rand[q, 0..S) (torch.multinomial's stream cannot be restated):
+//     for j = 0 .. S_eff - 1, m = n_free - j:   k = min((long long)(rand[q, j] * (float)m), m - 1)       fp32 product, truncated
+//         for every earlier chosen free-rank c in ASCENDING order: if (c <= k) ++k                     k-th of those left
+//     k is the j-th chosen free-rank; its entity is the k-th missing number of the sorted completion list (as above).
+// One wave per query: lane 0 runs the dependent draw steps over a sorted list in LDS (at most 64 * 64 / 2 steps), then
+// lane j maps rank j, gathers one score and compares; the counts are a shuffle tree; plain stores, no atomics.
+__global__ __launch_bounds__(64 * kSampledWaves) void sampled_rank_keys_kernel(
+        const float *pred, long long row_stride, long long n_cand, long long n_query, const int64_t *target,
+        long long target_stride, const int64_t *keys, long long n_keys, const int64_t *anchor, const int64_t *rel,
+        long long index_stride, long long n_rel, const float *rand, int n_sample, int64_t *optimistic, int64_t *pessimistic,
+        int64_t *samples) {
+    __shared__ long long sorted[kSampledWaves][kSampledMax];       // chosen free-ranks, ascending
+    __shared__ long long chosen[kSampledWaves][kSampledMax];       // ... in draw order
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long q = (long long)blockIdx.x * kSampledWaves + wave;
+    const bool live = q < n_query;
+    int64_t base = 0;
+    long long first = 0, n_excl = 0;
+    if (live && keys != nullptr) {
+        base = (anchor[q * index_stride] * n_rel + rel[q * index_stride]) * n_cand;
+        first = lower_bound_i64(keys, n_keys, base);
+        n_excl = lower_bound_i64(keys, n_keys, base + n_cand) - first;
+    }
+    const long long n_free = n_cand - n_excl;
+    const int s_eff = !live ? 0 : (n_free < (long long)n_sample ? (int)(n_free < 0 ? 0 : n_free) : n_sample);
+    if (lane == 0) {
+        for (int j = 0; j < s_eff; ++j) {
+            const long long m = n_free - j;
+            long long k = (long long)(rand[q * n_sample + j] * (float)m);
+            if (k > m - 1) k = m - 1;
+            if (k < 0) k = 0;
+            int at = 0;                                            // (the list ascends and k only grows: the first c > k ends it)
+            while (at < j && sorted[wave][at] <= k) { ++k; ++at; }
+            for (int i = j; i > at; --i) sorted[wave][i] = sorted[wave][i - 1];
+            sorted[wave][at] = k;
+            chosen[wave][j] = k;
+        }
+    }
+    __syncthreads();                                               // (every wave of the workgroup arrives: no early return above)
+    if (!live) return;
+    int opt = 0, pess = 0;
+    long long entity = -1;
+    if (lane < s_eff) {
+        const long long k = chosen[wave][lane];
+        long long lo = 0, hi = n_excl;      // smallest j in [0, n_excl] with L[j] - j > k   (L[n_excl] = +infinity)
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if ((keys[first + mid] - base) - mid > k) hi = mid; else lo = mid + 1;
+        }
+        entity = k + lo;
+        if (entity >= n_cand) entity = n_cand - 1;                 // (keys of another graph: a wrong answer, not a wild read)
+        const float *row = pred + q * row_stride;
+        const float pos = row[target[q * target_stride]];
+        const float neg = row[entity];
+        opt = pos < neg ? 1 : 0;
+        pess = pos <= neg ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        opt += __shfl_down(opt, off, 64);
+        pess += __shfl_down(pess, off, 64);
+    }
+    if (lane == 0) {
+        optimistic[q] = opt;
+        pessimistic[q] = pess;
+    }
+    if (samples != nullptr && lane < n_sample) samples[q * n_sample + lane] = entity;       // unused slots: -1
+}
+
 // Lexicographic lower bound over three sorted int32 columns.
 __device__ __forceinline__ long long lower_bound_3(const int32_t *a, const int32_t *b, const int32_t *c, long long n,
                                                    int va, int vb, int vc) {
@@ -225,6 +316,40 @@ int ultra_strict_negative(const int64_t *keys, int64_t n_keys, const int64_t *an
     hipLaunchKernelGGL(strict_negative_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), keys, (long long)n_keys, anchor, rel, (long long)n_query,
                        (long long)n_rel, (long long)n_node, rand, (long long)n_sample, out);
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+int ultra_filter_counts(const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel, int64_t index_stride,
+                        int64_t n_query, int64_t n_rel, int64_t n_node, int64_t *n_free, void *stream) {
+    if (n_query < 0 || n_keys < 0 || n_node <= 0 || index_stride < 0) return ULTRA_ERR_BAD_SHAPE;
+    if (n_query == 0) return ULTRA_OK;
+    if (n_free == nullptr) return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && (anchor == nullptr || rel == nullptr)) return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && n_rel <= 0) return ULTRA_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(filter_counts_kernel, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), keys, (long long)n_keys, anchor, rel, (long long)index_stride,
+                       (long long)n_query, (long long)n_rel, (long long)n_node, n_free);
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+int ultra_sampled_rank_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t row_stride, const int64_t *target,
+                            int64_t target_stride, const int64_t *keys, int64_t n_keys, const int64_t *anchor,
+                            const int64_t *rel, int64_t index_stride, int64_t n_rel, const float *rand, int64_t n_sample,
+                            int64_t *optimistic, int64_t *pessimistic, int64_t *samples, void *stream) {
+    if (n_query < 0 || n_cand <= 0 || row_stride < n_cand || n_keys < 0 || target_stride < 0 || index_stride < 0)
+        return ULTRA_ERR_BAD_SHAPE;
+    if (n_sample < 1 || n_sample > kSampledMax) return ULTRA_ERR_BAD_SHAPE;
+    if (n_query == 0) return ULTRA_OK;
+    if (pred == nullptr || target == nullptr || rand == nullptr || optimistic == nullptr || pessimistic == nullptr)
+        return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && (anchor == nullptr || rel == nullptr)) return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && n_rel <= 0) return ULTRA_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(sampled_rank_keys_kernel, dim3((unsigned)((n_query + kSampledWaves - 1) / kSampledWaves)),
+                       dim3(64 * kSampledWaves), 0, static_cast<hipStream_t>(stream), pred, (long long)row_stride,
+                       (long long)n_cand, (long long)n_query, target, (long long)target_stride, keys, (long long)n_keys, anchor,
+                       rel, (long long)index_stride, (long long)n_rel, rand, (int)n_sample, optimistic, pessimistic, samples);
     HIP_TRY(hipGetLastError());
     return ULTRA_OK;
 }

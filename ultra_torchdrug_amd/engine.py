@@ -168,6 +168,18 @@ class GraphedPredict:
         self.graph.replay()
         return self.static_ranks.clone()
 
+    def statistics(self, batch, rand=None):
+        """``task.rank_statistics`` ``(B, 2, 4)`` int64 of ``batch`` (``with_ranks=True``): the captured predict + ranks are
+        replayed, then the count and sampling kernels run eagerly on the static scores -- nothing more is captured and no
+        random-number call sits inside the graph.  ``rand``: the batch's ``(B, 2, 50)`` uniform numbers under ``toy_eval``."""
+        if self.static_ranks is None or batch.shape != self.static_batch.shape:
+            with torch.no_grad():
+                return self.task.rank_statistics(batch, rand=rand)
+        self.static_batch.copy_(batch)
+        self.graph.replay()
+        with torch.no_grad():
+            return self.task._device_statistics(self.static_batch, self.static_pred, self.static_ranks, rand)
+
 
 class GraphedTrainStep:
     """One fine-tuning step (``ultra/engine.py:62-92``) for a fixed batch size as hipGraph replays: strict negative
@@ -572,12 +584,14 @@ class GraphedScores:
         return self.static_pred
 
 
-def _ranks_of_unique_queries(task, local, batch_size, graphed):
+def _ranks_of_unique_queries(task, local, batch_size, graphed, statistics=False, rand=None):
     """``(n, 2)`` filtered ranks of the triples ``local`` with every DISTINCT query scored once.  A test set asks
     ``(h, r, ?)`` and ``(?, r, t)`` for each triple; triples that share the head and the relation share the tail query
     (and popular tails share head queries), and a query's scores do not depend on its batch mates, so the Bellman-Ford
     runs over the distinct queries only, ``2 * batch_size`` at a time, and every triple ranks its own target in the
-    scores of its query.  ``None`` when the model has no fused all-entity score path (the caller keeps the triple loop)."""
+    scores of its query.  ``None`` when the model has no fused all-entity score path (the caller keeps the triple loop).
+    ``statistics``: ``(n, 2, 4)`` ``task.rank_statistics`` instead -- the counts and, under ``toy_eval``, the sampled ranks of
+    every entry from ITS OWN row of ``rand`` ``(n, 2, 50)``, whichever entries share its query."""
     from . import backend
     ops = backend.get()
     n = len(local)
@@ -595,6 +609,9 @@ def _ranks_of_unique_queries(task, local, batch_size, graphed):
     keys = (graph.completion_keys(0), graph.completion_keys(1)) if task.filtered_ranking else (None, None)
     rank_rel = max(graph.num_relation, 1)
     ranks = torch.empty(2 * n, dtype=torch.long, device=local.device)
+    extra = torch.zeros(2 * n, 3, dtype=torch.long, device=local.device) if statistics else None     # count, optimistic, pessimistic
+    if statistics and task.toy_eval:
+        rand = torch.cat([rand[:, 0], rand[:, 1]])                              # (2n, 50): entry e < n = the tail query of triple e
     scorer = None
     bounds = first.tolist()
     for c in range(0, len(uniq), chunk):
@@ -614,6 +631,14 @@ def _ranks_of_unique_queries(task, local, batch_size, graphed):
             if len(e):
                 ranks[e] = ops.filtered_rank_keys(rows[pick], target[e], keys[side], anchor[e], base[e], rank_rel,
                                                   graph.num_node)
+                if statistics:
+                    extra[e, 0] = ops.filter_counts(keys[side], anchor[e], base[e], rank_rel, graph.num_node)
+                    if task.toy_eval:
+                        extra[e, 1], extra[e, 2] = ops.sampled_rank_keys(rows[pick], target[e], keys[side], anchor[e], base[e],
+                                                                         rank_rel, rand[e], graph.num_node)
+    if statistics:
+        both = torch.cat([ranks[:, None], extra], dim=1)                        # (2n, 4)
+        return torch.stack([both[:n], both[n:]], dim=1)
     return torch.stack([ranks[:n], ranks[n:]], dim=1)
 
 
@@ -622,7 +647,7 @@ UNIQUE_QUERY_GAIN = 0.9
 
 
 @torch.no_grad()
-def evaluate(task, triples, batch_size=16, graphed=None, cache_relations=None, unique_queries=None):
+def evaluate(task, triples, batch_size=16, graphed=None, cache_relations=None, unique_queries=None, generator=None):
     """Filtered ranking of ``triples`` ((n, 3) rows of (h, t, r)) sharded over ranks; every rank returns the
     metrics of the WHOLE set.  Only int64 ranks cross ranks.  ``graphed`` (default: on a GPU, when the shard holds at
     least two full batches): ``predict`` is captured once and replayed as a hipGraph for every full batch.
@@ -632,10 +657,24 @@ def evaluate(task, triples, batch_size=16, graphed=None, cache_relations=None, u
     per-batch path.  The cache is dropped before returning.  ``unique_queries`` (default: in eval mode on a GPU with
     full-batch evaluation, when at most ``UNIQUE_QUERY_GAIN`` of the shard's 2n queries are distinct): every distinct query
     of the shard is scored once (:func:`_ranks_of_unique_queries`) -- same ranks, fewer Bellman-Ford passes on test sets
-    whose triples share heads or tails; on sets that repeat few queries the triple loop is the faster one and stays."""
+    whose triples share heads or tails; on sets that repeat few queries the triple loop is the faster one and stays.
+    A task with a sampled metric ``hits@K_N`` or ``toy_eval`` (``task.needs_statistics``) gathers the int64 ``(n, 2, 4)``
+    ``task.rank_statistics`` instead of the ranks, through the same gather.  Under ``toy_eval`` the uniform numbers that define
+    the draws come ONCE for the whole triple set, ``(len(triples), 2, 50)`` from ``generator`` (a ``torch.Generator`` of the
+    task's device; in a process group rank 0's numbers are broadcast) and every triple uses its own row: the metrics do not depend on
+    ``batch_size``, ``graphed``, ``unique_queries`` or the shard boundaries.  Returns ``(metrics, ranking)``; the ranking is
+    the float ``0.5 * (optimistic + pessimistic) + 1`` under ``toy_eval``."""
     device = task.device
     mine = shard_indices(len(triples))
     local = validate_triples(task, triples[mine].to(device))
+    statistics = task.needs_statistics
+    rand = None
+    if statistics and task.toy_eval:
+        from .task import TOY_EVAL_SAMPLES
+        rand = torch.rand(len(triples), 2, TOY_EVAL_SAMPLES, generator=generator, device=device)
+        if get_world_size() > 1:
+            dist.broadcast(rand, 0)         # ranks are seeded apart (seed + rank): every rank uses rank 0's numbers
+        rand = rand[mine.to(device)]
     if graphed is None:
         graphed = device.type == "cuda" and len(local) >= 2 * batch_size and not task.training
     if cache_relations is None:
@@ -654,18 +693,32 @@ def evaluate(task, triples, batch_size=16, graphed=None, cache_relations=None, u
             keys = torch.cat([h * (2 * n_rel) + r, t * (2 * n_rel) + r + n_rel])
             unique_queries = int(torch.unique(keys).numel()) <= UNIQUE_QUERY_GAIN * keys.numel()
     try:
-        ranks = _ranks_of_unique_queries(task, local, batch_size, graphed) if unique_queries and len(local) else None
+        ranks = (_ranks_of_unique_queries(task, local, batch_size, graphed, statistics, rand)
+                 if unique_queries and len(local) else None)
         if ranks is None:
             # predict AND the filtered ranking of a batch as one replay (only the (B, 2) ranks are copied out per batch)
             replay = GraphedPredict(task, local[:batch_size], with_ranks=True) if graphed and len(local) >= batch_size else None
             ranks = []
             for i in range(0, len(local), batch_size):
                 batch = local[i:i + batch_size]
-                ranks.append(replay.ranks(batch) if replay is not None else task.rank_batch(batch))
-            ranks = torch.cat(ranks) if ranks else torch.zeros(0, 2, dtype=torch.long, device=device)
+                if statistics:
+                    batch_rand = None if rand is None else rand[i:i + batch_size]
+                    ranks.append(replay.statistics(batch, batch_rand) if replay is not None
+                                 else task.rank_statistics(batch, rand=batch_rand))
+                else:
+                    ranks.append(replay.ranks(batch) if replay is not None else task.rank_batch(batch))
+            ranks = torch.cat(ranks) if ranks else torch.zeros((0, 2, 4) if statistics else (0, 2), dtype=torch.long, device=device)
     finally:
         if cache_relations:
             task.clear_relation_cache()
+    if statistics:
+        # (n, 2, 4) int64 through the one gather, beside the relation column when the metrics are grouped by it
+        flat = ranks.reshape(len(ranks), 8)
+        both = gather_variable(torch.cat([flat, local[:, 2:3]], dim=1) if task.metric_per_rel else flat)
+        stats = both[:, :8].reshape(-1, 2, 4)
+        ranking = task.toy_ranking(stats) if task.toy_eval else stats[..., 0].contiguous()
+        rel = both[:, 8].contiguous() if task.metric_per_rel else None
+        return task.evaluate(ranking, rel=rel, num_candidates=stats[..., 1].contiguous()), ranking
     if task.metric_per_rel:
         # the reference's target() returns the relation of every ranked triple beside the masks (task.py:290-292) and
         # evaluate() groups by it; one more column through the same gather
@@ -684,7 +737,7 @@ def evaluate_all(task, test_sets, batch_size=16, **kwargs):
     the reference gathers each graph's score tensors) and the metrics are AVERAGED over the graphs with equal weight, as
     the reference does (``:154-157``).  Contexts are visited in sorted name order, so all ranks issue the same sequence
     of collectives.  Returns ``(mean metrics as floats, {graph: metrics}, {graph: ranking})``; the active context is
-    restored afterwards."""
+    restored afterwards.  ``generator`` (``toy_eval``) goes to every :func:`evaluate` in turn."""
     if not test_sets:
         raise ValueError("evaluate_all: no test sets")
     saved = task.split

@@ -1078,6 +1078,81 @@ def strict_negatives(keys, anchor, rel, n_rel, n_node, rand):
     return out
 
 
+def _index_pair(name, anchor, rel, rows, device):
+    """``anchor`` / ``rel`` int64 ``(rows,)`` on ``device`` and the element stride both are read with: views that share a
+    stride (the columns of a ``(B, 3)`` batch) go to the kernel as they are, anything else as contiguous copies."""
+    for what, t in (("anchor", anchor), ("rel", rel)):
+        if t.dtype != torch.int64 or t.shape != (rows,) or t.device != device:
+            raise RuntimeError("%s: %s must be int64 (%d,) on %s" % (name, what, rows, device))
+    if rows > 1 and (anchor.stride(0) != rel.stride(0) or anchor.stride(0) < 1):
+        anchor, rel = anchor.contiguous(), rel.contiguous()
+    return anchor, rel, (anchor.stride(0) if rows > 1 else 1)
+
+
+def filter_counts(keys, anchor, rel, n_rel, n_node):
+    """``mask.sum(-1)`` of the filter mask (``ultra/task.py:65-100``) without the mask: per query the number of entities
+    that do NOT complete ``(anchor[q], rel[q], ?)`` in the graph whose sorted distinct completion keys ``keys`` are
+    (``None``: unfiltered ranking, every count is ``n_node``) -- the denominator of the sampled metrics ``hits@K_N``
+    (``ultra/task.py:498``).  ``anchor`` / ``rel``: int64 ``(B,)``, strided views are fine.  Returns int64 ``(B,)``.  No host
+    synchronisation."""
+    if not anchor.is_cuda:
+        raise RuntimeError("filter_counts: anchor must be int64 (B,) on the HIP device")
+    rows = anchor.shape[0] if anchor.dim() == 1 else -1
+    anchor, rel, stride = _index_pair("filter_counts", anchor, rel, rows, anchor.device)
+    if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous()
+                             or keys.device != anchor.device):
+        raise RuntimeError("filter_counts: keys must be a contiguous int64 vector on %s" % anchor.device)
+    if int(n_node) <= 0 or int(n_rel) <= 0:
+        raise RuntimeError("filter_counts: n_rel and n_node must be positive, got %d and %d" % (int(n_rel), int(n_node)))
+    out = torch.empty(rows, dtype=torch.int64, device=anchor.device)
+    if rows == 0:
+        return out
+    _launch(anchor.device, "ultra_filter_counts", keys, keys.numel() if keys is not None else 0, anchor, rel, stride, rows,
+            int(n_rel), int(n_node), out)
+    return out
+
+
+SAMPLED_RANK_MAX = 64           # draws per query of ultra_sampled_rank_keys (one lane each)
+
+
+def sampled_rank_keys(pred, target, keys, anchor, rel, n_rel, rand, n_node=None, return_samples=False):
+    """The sampled ranking protocol ``toy_eval`` of the reference (``ultra/task.py:474-484``) on one prediction side, from
+    the graph's sorted completion keys: per row ``min(S, n_free)`` distinct entities outside the completions of
+    ``(anchor[q], rel[q], ?)`` are drawn without replacement -- the draw is DEFINED by the uniform numbers ``rand`` fp32
+    ``(B, S)``, ``S <= 64`` (``include/ultra_rspmm.h``; ``task.sampled_free_ranks`` restates it) -- and the positive is ranked
+    among their scores.  ``pred`` / ``target`` / ``keys`` / ``anchor`` / ``rel`` / ``n_node`` as in
+    :func:`filtered_rank_keys`.  Returns ``(optimistic, pessimistic)`` int64 ``(B,)`` = ``#{pos < neg}``, ``#{pos <= neg}``,
+    and with ``return_samples`` also the drawn entities int64 ``(B, S)`` in draw order (``-1`` in unused slots)."""
+    if pred.dim() != 2 or pred.dtype != torch.float32 or pred.stride(1) != 1 or not pred.is_cuda:
+        raise RuntimeError("sampled_rank_keys: pred must be fp32 (B, N) with contiguous rows on the HIP device")
+    rows, n_cand = pred.shape
+    if n_node is not None and int(n_node) != n_cand:
+        raise RuntimeError("sampled_rank_keys: the scores list %d candidates but the completion keys were built over "
+                           "%d nodes (filter graph and fact graph must share the entity set)" % (n_cand, int(n_node)))
+    if target.dtype != torch.int64 or target.shape != (rows,) or target.device != pred.device:
+        raise RuntimeError("sampled_rank_keys: target must be int64 (%d,) on %s" % (rows, pred.device))
+    anchor, rel, stride = _index_pair("sampled_rank_keys", anchor, rel, rows, pred.device)
+    if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous()
+                             or keys.device != pred.device):
+        raise RuntimeError("sampled_rank_keys: keys must be a contiguous int64 vector on %s" % pred.device)
+    if rand.dim() != 2 or rand.shape[0] != rows or rand.dtype != torch.float32 or rand.device != pred.device:
+        raise RuntimeError("sampled_rank_keys: rand must be fp32 (%d, S) on %s" % (rows, pred.device))
+    n_sample = rand.shape[1]
+    if not 1 <= n_sample <= SAMPLED_RANK_MAX:
+        raise RuntimeError("sampled_rank_keys: 1 to %d samples per query, got %d" % (SAMPLED_RANK_MAX, n_sample))
+    if rows and pred.stride(0) < n_cand:
+        raise RuntimeError("sampled_rank_keys: the rows of pred overlap")
+    rand = rand.contiguous()
+    optimistic = torch.empty(rows, dtype=torch.int64, device=pred.device)
+    pessimistic = torch.empty(rows, dtype=torch.int64, device=pred.device)
+    samples = torch.empty(rows, n_sample, dtype=torch.int64, device=pred.device) if return_samples else None
+    if rows:
+        _launch(pred.device, "ultra_sampled_rank_keys", pred, rows, n_cand, pred.stride(0), target, target.stride(0), keys,
+                keys.numel() if keys is not None else 0, anchor, rel, stride, int(n_rel), rand, n_sample, optimistic,
+                pessimistic, samples)
+    return (optimistic, pessimistic, samples) if return_samples else (optimistic, pessimistic)
+
+
 # Training, opt-in (ULTRA_KEEP_PRE_NORM=1): the fused epilogue's forward keeps z = Linear(cat[input, update]) (one more
 # (N, B, 64) tensor per layer) and the fused backward loads it instead of recomputing it -- a third of that kernel's matrix
 # work, identical gradients.  Measured on an MI355X it only moves the backward kernel 380 -> 365 us at 655 k rows (the kernel

@@ -14,6 +14,8 @@ checkpoint holds after ``util.clean_save`` (``ultra/util.py:278-325``); scores a
 only the int64 ranks leave it (the reference moves ``(B, 2, N)`` scores and masks to the host per batch,
 ``task.py:263,295``).
 """
+import math
+
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -31,14 +33,71 @@ def variadic_sample(candidates, sizes, num_sample):
     return candidates[index]
 
 
+TOY_EVAL_SAMPLES = 50          # negatives per query and side of the sampled protocol (the reference asserts it, task.py:500)
+
+
+def parse_hits(name):
+    """``hits@K`` -> ``(K, None)``; ``hits@K_N`` -> ``(K, N)``, the reference's sampled estimate over N negatives
+    (``values = _metric[5:].split("_")``, task.py:493-496)."""
+    values = name[5:].split("_")
+    if len(values) > 2:
+        raise ValueError("Unknown metric `%s`" % name)
+    return int(values[0]), (int(values[1]) if len(values) > 1 else None)
+
+
+def sampled_free_ranks(n_free, rand):
+    """The without-replacement draw of the sampled protocol, DEFINED by uniform numbers (``csrc/sampler.inc``,
+    ``sampled_rank_keys_kernel``; ``torch.multinomial``'s stream, task.py:477, cannot be restated): for row ``q`` with
+    ``n_free[q]`` candidates and ``j = 0 .. min(S, n_free) - 1``, ``m = n_free - j``:
+    ``k = min(trunc(rand[q, j] * float32(m)), m - 1)`` (an fp32 product), then ``k += 1`` for every earlier chosen rank
+    ``c <= k`` in ascending order -- the ``k``-th candidate still undrawn.  Returns int64 ``(rows, S)`` ranks among the row's
+    candidates in draw order, ``-1`` in the slots past ``n_free``."""
+    if rand.dtype != torch.float32 or rand.dim() != 2:
+        raise ValueError("sampled_free_ranks: rand must be fp32 (rows, S)")
+    rows, n_sample = rand.shape
+    n_free = n_free.to(torch.int64)
+    out = torch.full((rows, n_sample), -1, dtype=torch.int64, device=rand.device)
+    never = torch.full((rows,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=rand.device)
+    ordered = never[:, None][:, :0]                                   # the chosen ranks, ascending (exhausted rows: `never`)
+    for j in range(n_sample):
+        m = n_free - j
+        active = m > 0
+        k = (rand[:, j] * m.to(torch.float32)).long()
+        k = torch.minimum(k, m - 1).clamp(min=0)
+        for c in range(j):
+            k = k + (ordered[:, c] <= k).long()
+        out[:, j] = torch.where(active, k, out[:, j])
+        ordered = torch.sort(torch.cat([ordered, torch.where(active, k, never)[:, None]], dim=1), dim=1).values
+    return out
+
+
+def dense_sampled_ranks(pred, target, mask, rand):
+    """The sampled protocol (task.py:474-484) from a dense filter mask -- the CPU counterpart of
+    ``functional.sampled_rank_keys``: ``pred`` fp32 ``(rows, N)``, ``target`` int64 ``(rows,)``, ``mask`` bool ``(rows, N)``
+    (True = unfiltered), ``rand`` fp32 ``(rows, S)``.  Returns ``(optimistic, pessimistic, samples)``: ``#{pos < neg}`` and
+    ``#{pos <= neg}`` over the entities drawn by :func:`sampled_free_ranks`, and those entities int64 ``(rows, S)`` in draw
+    order (``-1`` in unused slots)."""
+    n = mask.shape[-1]
+    free_rank = sampled_free_ranks(mask.sum(dim=-1), rand)
+    drawn = free_rank >= 0
+    # a free-rank's entity: the first position where the running count of unfiltered entities reaches rank + 1
+    entity = torch.searchsorted(mask.cumsum(dim=-1), free_rank.clamp(min=0) + 1).clamp(max=n - 1)
+    pos_pred = pred.gather(-1, target.unsqueeze(-1))
+    neg_pred = pred.gather(-1, entity)
+    optimistic = ((pos_pred < neg_pred) & drawn).sum(dim=-1)
+    pessimistic = ((pos_pred <= neg_pred) & drawn).sum(dim=-1)
+    return optimistic, pessimistic, torch.where(drawn, entity, free_rank)
+
+
 class KnowledgeGraphCompletion(nn.Module):
     """``tasks.KnowledgeGraphCompletionAdapted`` with the configuration surface of
-    ``config/transductive/inference.yaml:8-39``."""
+    ``config/transductive/inference.yaml:8-39``; with ``toy_eval`` and the sampled metric names ``hits@K_N`` it is also the
+    evaluation of ``tasks.InductiveKnowledgeGraphCompletionAdapted`` (``ultra/task.py:463-523``)."""
 
     def __init__(self, model, rel_models, criterion="bce",
                  metric=("mr", "mrr", "hits@1", "hits@3", "hits@10", "mrr-tail", "hits@1-tail", "hits@10-tail"),
                  num_negative=128, margin=6, adversarial_temperature=0, strict_negative=True, filtered_ranking=True,
-                 fact_ratio=None, sample_weight=False, metric_per_rel=False, full_batch_eval=False):
+                 fact_ratio=None, sample_weight=False, metric_per_rel=False, full_batch_eval=False, toy_eval=False):
         super().__init__()
         assert strict_negative                                   # task.py:27
         self._relation_cache = {}                                # graph context -> per relation model (R, 2R, 64) tables
@@ -55,6 +114,7 @@ class KnowledgeGraphCompletion(nn.Module):
         self.sample_weight = sample_weight
         self.metric_per_rel = metric_per_rel
         self.full_batch_eval = full_batch_eval
+        self.toy_eval = bool(toy_eval)                          # task.py:474-484: rank among 50 sampled unfiltered negatives
         # full-batch evaluation scores tails and heads in ONE Bellman-Ford over 2B queries instead of two over B
         # (task.py:249-259 issues two model calls).  Queries are independent columns of every kernel on the path, so
         # every score is bit-identical to the two-call form (tests/test_model_gpu.py); False = the literal two calls.
@@ -404,34 +464,140 @@ class KnowledgeGraphCompletion(nn.Module):
             return torch.stack([t_rank, h_rank], dim=1)
         return self.get_ranking(pred, self.target(batch))
 
-    def evaluate(self, ranking, rel=None):
-        """task.py:317-351 on an int64 ``(n, 2)`` ranking tensor (column 0 = tail, 1 = head).  With
-        ``metric_per_rel`` and ``rel`` (``(n,)`` relation of every ranked triple) every undirected metric is also
-        reported per relation (task.py:290-292,512-517: tails under ``r``, heads under ``r + num_relation``)."""
+    # ------------------------------------------------------------------ sampled metrics (task.py:463-523)
+    @property
+    def needs_statistics(self):
+        """True when ``evaluate`` needs more than the filtered ranks: a sampled metric ``hits@K_N`` divides by the number of
+        unfiltered candidates of every query (task.py:498), ``toy_eval`` ranks among sampled negatives (task.py:474-484)."""
+        return self.toy_eval or any(name.startswith("hits@") and "_" in name.split("-")[0] for name in self.metric)
+
+    def _toy_rand(self, rows, device, rand):
+        """The uniform numbers of one batch, fp32 ``(B, 2, 50)``: given, or drawn tails first, then heads."""
+        if rand is None:
+            rand = torch.stack([torch.rand(rows, TOY_EVAL_SAMPLES, device=device),
+                                torch.rand(rows, TOY_EVAL_SAMPLES, device=device)], dim=1)
+        if rand.shape != (rows, 2, TOY_EVAL_SAMPLES) or rand.dtype != torch.float32:
+            raise ValueError("toy_eval: rand must be fp32 (%d, 2, %d), got %s %s"
+                             % (rows, TOY_EVAL_SAMPLES, rand.dtype, tuple(rand.shape)))
+        return rand.to(device)
+
+    def _device_statistics(self, batch, pred, ranks, rand=None):
+        """``rank_statistics`` behind scores and filtered ranks that exist already (a replayed hipGraph's): the counts and
+        the sampled ranks from the FILTER graph's sorted completion keys -- no ``(B, 2, N)`` mask, no host synchronisation."""
+        ops = backend.get()
+        pos_h_index, pos_t_index, pos_r_index = batch.t()
+        graph = self.graph
+        n_rel = max(graph.num_relation, 1)
+        keys = (graph.completion_keys(0), graph.completion_keys(1)) if self.filtered_ranking else (None, None)
+        count = torch.stack([ops.filter_counts(keys[0], pos_h_index, pos_r_index, n_rel, graph.num_node),
+                             ops.filter_counts(keys[1], pos_t_index, pos_r_index, n_rel, graph.num_node)], dim=1)
+        if not self.toy_eval:
+            zero = torch.zeros_like(count)
+            return torch.stack([ranks, count, zero, zero], dim=-1)
+        rand = self._toy_rand(len(batch), pred.device, rand)
+        t_opt, t_pess = ops.sampled_rank_keys(pred[:, 0], pos_t_index, keys[0], pos_h_index, pos_r_index, n_rel, rand[:, 0],
+                                              graph.num_node)
+        h_opt, h_pess = ops.sampled_rank_keys(pred[:, 1], pos_h_index, keys[1], pos_t_index, pos_r_index, n_rel, rand[:, 1],
+                                              graph.num_node)
+        return torch.stack([ranks, count, torch.stack([t_opt, h_opt], dim=1), torch.stack([t_pess, h_pess], dim=1)], dim=-1)
+
+    @torch.no_grad()
+    def rank_statistics(self, batch, pred=None, rand=None):
+        """What the sampled metrics need beside the ranks, int64 ``(B, 2, 4)``: filtered rank (``rank_batch``),
+        ``num_candidates`` = ``mask.sum(-1)`` (task.py:498), and -- zero unless ``toy_eval`` -- ``optimistic`` /
+        ``pessimistic`` = ``#{pos < neg}`` / ``#{pos <= neg}`` over 50 unfiltered negatives drawn without replacement
+        (task.py:474-484).  ``rand``: fp32 ``(B, 2, 50)`` uniform numbers that define the draw (:func:`sampled_free_ranks`;
+        drawn with ``torch.rand``, tails then heads, when not given).  On the device everything comes from the filter
+        graph's sorted completion keys (``ultra_filter_counts``, ``ultra_sampled_rank_keys``); CPU tensors take the dense
+        masks of ``target``."""
+        if pred is None:
+            pred = self.predict(batch)
+        if backend.get().accepts(pred):
+            ranks = self.rank_batch(batch, pred=pred)
+            return self._device_statistics(self._select(batch), pred, ranks, rand)
+        batch = self._select(batch)
+        mask, target = self.target(batch)
+        if not self.filtered_ranking:
+            mask = torch.ones_like(mask)
+        ranks = self.get_ranking(pred, (mask, target))
+        count = mask.sum(dim=-1)
+        if not self.toy_eval:
+            zero = torch.zeros_like(count)
+            return torch.stack([ranks, count, zero, zero], dim=-1)
+        rand = self._toy_rand(len(batch), pred.device, rand)
+        rows, n = 2 * len(batch), mask.shape[-1]
+        optimistic, pessimistic, _ = dense_sampled_ranks(pred.reshape(rows, n), target.reshape(rows), mask.reshape(rows, n),
+                                                         rand.reshape(rows, TOY_EVAL_SAMPLES))
+        optimistic, pessimistic = optimistic.view(-1, 2), pessimistic.view(-1, 2)
+        return torch.stack([ranks, count, optimistic, pessimistic], dim=-1)
+
+    def _query_scores(self, name, ranking, num_candidates, full_name=None):
+        """The per-query value of the undirected metric ``name`` (task.py:488-511), same shape as ``ranking``;
+        ``full_name``: the configured name, with its direction, for the error message."""
+        if name == "mr":
+            return ranking.float()
+        if name == "mrr":
+            return 1 / ranking.float()
+        if not name.startswith("hits@"):
+            raise ValueError("Unknown metric `%s`" % (full_name or name))
+        threshold, num_sample = parse_hits(name)
+        if num_sample is None:
+            return (ranking <= threshold).float()
+        # the chance that fewer than `threshold` of `num_sample` uniformly drawn unfiltered negatives outrank the positive
+        # (task.py:497-506, "unbiased estimation"), in fp32 as the reference evaluates it
+        if num_candidates is None:
+            raise ValueError("metric `%s` needs the number of unfiltered candidates of every query: "
+                             "evaluate(ranking, num_candidates=...) (task.rank_statistics)" % name)
+        if self.toy_eval:
+            if num_sample != TOY_EVAL_SAMPLES:
+                raise ValueError("toy_eval ranks among %d negatives: `%s` must name %d samples"
+                                 % (TOY_EVAL_SAMPLES, name, TOY_EVAL_SAMPLES))
+            fp_rate = (ranking - 1).float() / (TOY_EVAL_SAMPLES + 1)
+        else:
+            fp_rate = (ranking - 1).float() / num_candidates.to(ranking.device)
+        score = torch.zeros_like(fp_rate)
+        for i in range(threshold):
+            score = score + float(math.comb(num_sample, i)) * (fp_rate ** i) * ((1 - fp_rate) ** (num_sample - i))
+        return score
+
+    def toy_ranking(self, statistics):
+        """task.py:484: the float ranking ``0.5 * (optimistic + pessimistic) + 1`` of ``rank_statistics`` columns."""
+        return 0.5 * (statistics[..., 2] + statistics[..., 3]) + 1
+
+    def evaluate(self, ranking, rel=None, num_candidates=None):
+        """task.py:317-351 / 463-523 on an ``(n, 2)`` ranking tensor (column 0 = tail, 1 = head): int64 filtered ranks,
+        or under ``toy_eval`` the float :meth:`toy_ranking`.  With ``metric_per_rel`` and ``rel`` (``(n,)`` relation of
+        every ranked triple) every undirected metric is also reported per relation (task.py:290-292,512-517: tails under
+        ``r``, heads under ``r + num_relation``).  ``num_candidates`` (``(n, 2)``, ``rank_statistics`` column 1): needed by
+        the sampled metrics ``hits@K_N`` and by ``toy_eval``, whose draw of 50 needs at least 50 candidates per query (the
+        reference's ``multinomial`` raises there, and so does this)."""
         metric = {}
         if self.metric_per_rel and rel is None:
             raise ValueError("metric_per_rel needs the relation of every ranked triple: evaluate(ranking, rel)")
+        if self.toy_eval:
+            if num_candidates is None:
+                raise ValueError("toy_eval needs the number of unfiltered candidates of every query: "
+                                 "evaluate(ranking, num_candidates=...)")
+            if num_candidates.numel() and int(num_candidates.min()) < TOY_EVAL_SAMPLES:
+                raise ValueError("toy_eval draws %d unfiltered negatives per query without replacement, but a query has "
+                                 "only %d" % (TOY_EVAL_SAMPLES, int(num_candidates.min())))
         for name in self.metric:
-            _ranking, _name = ranking, name
+            _name, column = name, None
             if "-" in name:
                 _name, direction = name.split("-")
                 if direction not in ("head", "tail"):
                     raise ValueError("Unknown direction `%s`" % direction)
-                _ranking = ranking.select(1, 1 if direction == "head" else 0)
-            if _name == "mr":
-                score = _ranking.float().mean()
-            elif _name == "mrr":
-                score = (1 / _ranking.float()).mean()
-            elif _name.startswith("hits@"):
-                score = (_ranking <= int(_name[5:])).float().mean()
+                column = 1 if direction == "head" else 0
+            if column is None:
+                value = self._query_scores(_name, ranking, num_candidates, name)
             else:
-                raise ValueError("Unknown metric `%s`" % name)
-            metric[name] = score
+                value = self._query_scores(_name, ranking.select(1, column),
+                                           None if num_candidates is None else num_candidates.select(1, column), name)
+            metric[name] = value.mean()
             if self.metric_per_rel and "-" not in name:
                 n_rel = self.num_relation
                 rel2 = torch.stack([rel, rel + n_rel], dim=1).reshape(-1).to(ranking.device)
-                value = ranking.reshape(-1).float()
-                value = value if _name == "mr" else (1 / value if _name == "mrr" else (value <= int(_name[5:])).float())
+                value = value.reshape(-1)
                 total = torch.zeros(2 * n_rel, device=ranking.device).index_add_(0, rel2, value)
                 count = torch.zeros(2 * n_rel, device=ranking.device).index_add_(0, rel2, torch.ones_like(value))
                 for ridx in range(2 * n_rel):
