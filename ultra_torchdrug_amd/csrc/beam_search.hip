@@ -21,21 +21,9 @@
 #include <cmath>
 #include <cstdint>
 
-#include "ultra_rspmm.h"
-
-extern thread_local int ultra_detail_last_hip_error;
+#include "host_common.h"
 
 namespace {
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) {                         \
-            ultra_detail_last_hip_error = (int)_e;      \
-            (void)hipGetLastError();                    \
-            return ULTRA_ERR_HIP;                       \
-        }                                               \
-    } while (0)
 
 constexpr int kThreads = 256;
 constexpr unsigned long long kNoKey = ~0ull;

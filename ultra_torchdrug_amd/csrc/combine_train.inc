@@ -402,14 +402,8 @@ int ultra_combine_backward_f32(const float *input, const float *update, const fl
     p.grad_out = grad_out; p.d_z = d_z; p.d_gamma_partial = d_ln_weight_partial; p.d_beta_partial = d_ln_bias_partial;
     p.rows = rows; p.eps = ln_eps; p.relu = relu;
     const size_t lds = (size_t)(kCbWaves * kCbTileFloats + 128) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_backward_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(combine_backward_kernel, dim3(ln_waves / kCbWaves), dim3(kCbWaves * 64), lds, s, p);
-    HIP_TRY(hipGetLastError());
+    rc = launch_with_lds(combine_backward_kernel, p, ln_waves / kCbWaves, lds, s, kCbWaves * 64, (int)lds);
+    if (rc) return rc;
 
     WGradParams w;
     w.d_z = d_z; w.input = input; w.update = update; w.partial = d_weight_partial; w.bias_partial = d_bias_partial;
@@ -427,26 +421,16 @@ int ultra_combine_dxdu_f32(const float *d_z, const float *weight, const float *g
     if (dim != 64 || rows < 0) return ULTRA_ERR_BAD_SHAPE;
     if (rows == 0) return ULTRA_OK;
     if (d_z == nullptr || weight == nullptr || d_input == nullptr || d_update == nullptr) return ULTRA_ERR_NULL_POINTER;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     DxDuParams p;
     p.d_z = d_z; p.weight = weight; p.grad_out = grad_out; p.d_input = d_input; p.d_update = d_update; p.rows = rows;
     const size_t lds = (size_t)(128 * 68 + kCbWaves * 32 * 132) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dxdu_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        attr_set[dev] = true;
-    }
     const long long n_tiles = (rows + 31) / 32;
     long long blocks = (n_tiles + kCbWaves - 1) / kCbWaves;
     if (blocks > di->n_cu) blocks = di->n_cu;
-    hipLaunchKernelGGL(dxdu_kernel, dim3((unsigned)blocks), dim3(kCbWaves * 64), lds, static_cast<hipStream_t>(stream), p);
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return launch_with_lds(dxdu_kernel, p, (int)blocks, lds, static_cast<hipStream_t>(stream), kCbWaves * 64, (int)lds);
 }
 
 }  // extern "C"

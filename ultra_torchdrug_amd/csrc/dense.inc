@@ -274,20 +274,10 @@ template <int K>
 int launch_linear(const LinearParams &p, int n_cu, hipStream_t stream) {
     constexpr int kStride = K + 4;
     const size_t lds = (size_t)(K * kStride + kCbWaves * 32 * kStride) * sizeof(float);
-    static bool attr_set[16] = {false};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(linear_kernel<K, K>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
     const long long n_tiles = (p.rows + 31) / 32;
     long long blocks = (n_tiles + kCbWaves - 1) / kCbWaves;
     if (blocks > n_cu) blocks = n_cu;
-    hipLaunchKernelGGL((linear_kernel<K, K>), dim3((unsigned)blocks), dim3(kCbWaves * 64), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return launch_with_lds(linear_kernel<K, K>, p, (int)blocks, lds, stream, kCbWaves * 64, (int)lds);
 }
 
 }  // namespace
@@ -446,10 +436,8 @@ int ultra_linear_forward_f32(const float *input, const float *weight, const floa
     if (rows == 0) return ULTRA_OK;
     if (input == nullptr || weight == nullptr || bias == nullptr || out == nullptr) return ULTRA_ERR_NULL_POINTER;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     if (out_dim == 1 && in_dim % 4 == 0) {          // the 128 -> 1 score head (no activation after the last layer)
         if (relu) return ULTRA_ERR_BAD_SHAPE;
@@ -475,28 +463,19 @@ int ultra_score_forward_f32(const float *hidden, const float *query, const float
     if (hidden == nullptr || query == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr ||
         query_bias == nullptr || out == nullptr)
         return ULTRA_ERR_NULL_POINTER;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     ScoreParams p;
     p.hidden = hidden; p.query = query; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.qbias = query_bias; p.out = out;
     p.n_node = n_node; p.batch = (int)batch;
     const size_t lds = (size_t)(128 * 68 + 128 + kScoreLdsBatch * kScoreCStride + kCbWaves * 32 * 132) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(score_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(score_query_bias_kernel, dim3((unsigned)batch), dim3(128), 0, static_cast<hipStream_t>(stream), p);
     const long long n_tiles = (n_node * batch + 31) / 32;
     long long blocks = (n_tiles + kCbWaves - 1) / kCbWaves;
     if (blocks > di->n_cu) blocks = di->n_cu;
-    hipLaunchKernelGGL(score_kernel, dim3((unsigned)blocks), dim3(kCbWaves * 64), lds, static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return launch_with_lds(score_kernel, p, (int)blocks, lds, static_cast<hipStream_t>(stream), kCbWaves * 64, (int)lds);
 }
 
 int ultra_relation_project_f32(const float *relation, int64_t stride_b, int64_t stride_r, const float *const *w1,
@@ -508,18 +487,10 @@ int ultra_relation_project_f32(const float *relation, int64_t stride_b, int64_t 
     if (n_layers == 0 || batch == 0 || n_rel == 0) return ULTRA_OK;
     if (relation == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr || out == nullptr)
         return ULTRA_ERR_NULL_POINTER;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     const size_t lds = (size_t)(2 * 64 * 68 + kCbWaves * 32 * 68) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(project_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        attr_set[dev] = true;
-    }
     for (int64_t first = 0; first < n_layers; first += kProjMaxLayers) {
         const int count = (int)((n_layers - first) < kProjMaxLayers ? (n_layers - first) : kProjMaxLayers);
         ProjectParams p{};
@@ -539,9 +510,8 @@ int ultra_relation_project_f32(const float *relation, int64_t stride_b, int64_t 
         if (per_layer > cap) per_layer = cap;
         if (per_layer < 1) per_layer = 1;
         p.blocks_per_layer = (int)per_layer;
-        hipLaunchKernelGGL(project_kernel, dim3((unsigned)(per_layer * count)), dim3(kCbWaves * 64), lds,
-                           static_cast<hipStream_t>(stream), p);
-        HIP_TRY(hipGetLastError());
+        rc = launch_with_lds(project_kernel, p, (int)(per_layer * count), lds, static_cast<hipStream_t>(stream), kCbWaves * 64, (int)lds);
+        if (rc) return rc;
     }
     return ULTRA_OK;
 }

@@ -27,22 +27,11 @@
 #include <cstdint>
 #include <cstring>
 
-#include "relgraph_dense.h"
-#include "ultra_rspmm.h"
-
-extern thread_local int ultra_detail_last_hip_error;
+#include "host_common.h"
 
 namespace {
 
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) {                         \
-            ultra_detail_last_hip_error = (int)_e;      \
-            (void)hipGetLastError();                    \
-            return ULTRA_ERR_HIP;                       \
-        }                                               \
-    } while (0)
+using namespace ultra_detail;
 
 typedef float qf4 __attribute__((ext_vector_type(4)));
 typedef float qf2 __attribute__((ext_vector_type(2)));
@@ -62,8 +51,6 @@ __device__ __forceinline__ void lds_write4(uint32_t byte_addr, qf4 v) { *(lds_qf
 __device__ __forceinline__ void lds_write2(uint32_t byte_addr, qf2 v) { *(lds_qf2_wptr)byte_addr = v; }
 __device__ __forceinline__ void lds_write1(uint32_t byte_addr, float v) { *(lds_f_wptr)byte_addr = v; }
 
-constexpr int kXcd = 8;
-constexpr int kMaxLdsBytes = 156 * 1024;
 constexpr int kLfBlock = 512;                    // 8 waves per CU, as rowgroup_kernel
 constexpr int kLfWaves = kLfBlock / 64;
 // a staged epilogue row: in[even columns] 32 | in[odd] 32 | up[even] 32 | up[odd] 32 | pad 4 floats -- lane group k of the
@@ -78,7 +65,7 @@ constexpr uint32_t kOffTiles = kOffBias + 256;
 constexpr uint32_t kOffRel = kOffTiles + kLfWaves * kLfTileBytes;        // relation rows held in LDS (if any)
 static_assert(kOffRel % 16 == 0, "16-byte aligned LDS tables");
 
-constexpr int kRelL2 = 0, kRelLds = 1, kRelPart = 2;
+constexpr int kRelL2 = REL_L2, kRelLds = REL_LDS, kRelPart = REL_PART;
 
 struct LayerParams {
     const int32_t *row_ptr;     // [n_rows + 1]
@@ -549,21 +536,7 @@ __global__ __launch_bounds__(128) void score_qbias_kernel(const float *query, co
 
 template <int G, bool SCORE = false>
 int launch_layer_g(const LayerParams &p, bool unit_w, int rel, int grid, size_t lds, hipStream_t stream) {
-#define ULTRA_LF(UW, RL)                                                                                          \
-    do {                                                                                                          \
-        auto kern = rowgroup_layer_kernel<UW, RL, G, SCORE>;                                                      \
-        static bool attr_set[16] = {};                                                                            \
-        int dev = 0;                                                                                              \
-        HIP_TRY(hipGetDevice(&dev));                                                                              \
-        if (dev >= 0 && dev < 16 && !attr_set[dev]) {                                                             \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        kMaxLdsBytes));                                                           \
-            attr_set[dev] = true;                                                                                 \
-        }                                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kLfBlock), lds, stream, p);                                     \
-        HIP_TRY(hipGetLastError());                                                                               \
-        return ULTRA_OK;                                                                                          \
-    } while (0)
+#define ULTRA_LF(UW, RL) return launch_with_lds(rowgroup_layer_kernel<UW, RL, G, SCORE>, p, grid, lds, stream, kLfBlock)
     if constexpr (!SCORE) {
         if (unit_w) {
             if (rel == kRelLds) ULTRA_LF(true, kRelLds);
@@ -578,21 +551,12 @@ int launch_layer_g(const LayerParams &p, bool unit_w, int rel, int grid, size_t 
 #undef ULTRA_LF
 }
 
-int gcd_int(int a, int b) {
-    while (b) { const int t = a % b; a = b; b = t; }
-    return a;
-}
-
-bool abi_ok(const ultra_segments *s) {
-    return s->struct_bytes == (uint32_t)sizeof(ultra_segments) && s->abi_version == (uint32_t)ULTRA_RSPMM_ABI_VERSION;
-}
-
 }  // namespace
 
 extern "C" {
 
 int ultra_layer_forward_supported(const ultra_segments *fwd, int64_t n_query, int64_t n_rel) {
-    if (fwd == nullptr || !abi_ok(fwd)) return 0;
+    if (fwd == nullptr || !segments_abi_ok(fwd)) return 0;
     if (fwd->row_ptr == nullptr || fwd->n_pieces != 0 || fwd->n_rows <= 0 || fwd->n_rows > 0x7fffffffLL) return 0;
     if (n_query <= 0 || n_rel <= 0 || n_query * 64 >= (1LL << 30)) return 0;
     return 1;
@@ -601,52 +565,35 @@ int ultra_layer_forward_supported(const ultra_segments *fwd, int64_t n_query, in
 // shared by the two entries: tiling, LDS budget, launch.  `score` != NULL: the last layer with the score head inside.
 static int layer_launch(const ultra_segments *fwd, LayerParams &q, int64_t n_query, int64_t n_rel, bool score, hipStream_t s,
                         const int32_t *col_override = nullptr) {
-    int n_cu = 0;
-    int rc = ultra_detail::persistent_cus(&n_cu);
+    DeviceInfo *di = nullptr;
+    int rc = current_device_info(&di);
     if (rc) return rc;
     const long long F = n_query * 64;
     q.row_ptr = fwd->row_ptr; q.col = col_override != nullptr ? col_override : fwd->node_a; q.rel = fwd->rel; q.weight = fwd->weight;
     q.F = F; q.n_rows = (int)fwd->n_rows; q.n_rel = (int)n_rel; q.n_query = (int)n_query;
-    // groups as wide as the row allows when the gathered matrix lives in DRAM (launch_rowgroup's rule), a whole number of tiles
-    const bool dram = ultra_detail::wide_groups_forced() || (double)fwd->n_rows * (double)F * 4.0 > 256.0 * 1024 * 1024;
-    const int group = (dram && F % 256 == 0) ? 64 : ((dram && F % 128 == 0) ? 32 : 16);
-    const int width = 4 * group;
-    q.n_tiles = (int)(F / width);
-    q.split = kXcd / gcd_int(q.n_tiles, kXcd);
-    while (((long long)q.n_rows + q.split - 1) / q.split * F * 4 >= (1LL << 32) - 65536 && q.split < (1 << 20)) q.split *= 2;
-    q.n_slots = q.n_tiles * q.split;
-    q.blocks_per_label = (n_cu + kXcd - 1) / kXcd;
-    const int grid = q.blocks_per_label * kXcd;
+    // rowgroup_kernel's tiling (F is a whole number of tiles of every group width it can choose) with the relation rows in the
+    // LDS the epilogue leaves; the score form keeps that LDS for the head's weights
+    const RowGroupTiling t = rowgroup_tiling(F, fwd->n_rows, fwd->n_rows, score ? 0 : n_rel, di->n_cu, g_knobs.wide_groups, kOffRel,
+                                             (size_t)kMaxLdsBytes - kOffRel);
+    q.n_tiles = t.geo.n_tiles; q.split = t.geo.split; q.n_slots = t.geo.n_slots; q.blocks_per_label = t.geo.blocks_per_label;
+    q.n_rel_lds = t.n_rel_lds;
     const bool unit_w = fwd->weight == nullptr;
     if (score) {
         const size_t lds = kOffSC + (size_t)n_query * 128 * sizeof(float);
-        q.n_rel_lds = 0;
-        if (group == 64) return launch_layer_g<64, true>(q, unit_w, kRelL2, grid, lds, s);
-        if (group == 32) return launch_layer_g<32, true>(q, unit_w, kRelL2, grid, lds, s);
-        return launch_layer_g<16, true>(q, unit_w, kRelL2, grid, lds, s);
+        if (t.group == 64) return launch_layer_g<64, true>(q, unit_w, kRelL2, t.geo.grid, lds, s);
+        if (t.group == 32) return launch_layer_g<32, true>(q, unit_w, kRelL2, t.geo.grid, lds, s);
+        return launch_layer_g<16, true>(q, unit_w, kRelL2, t.geo.grid, lds, s);
     }
-    // relation rows in the LDS the epilogue leaves: all of them, or the first ones when that is at least a quarter of the table
-    const size_t room = (size_t)kMaxLdsBytes - kOffRel;
-    const size_t lds_need = (size_t)n_rel * width * sizeof(float);
-    int rel = kRelL2;
-    q.n_rel_lds = 0;
-    size_t lds = kOffRel;
-    if (lds_need <= room) {
-        rel = kRelLds; q.n_rel_lds = (int)n_rel; lds += lds_need;
-    } else {
-        const int part_rows = (int)(room / ((size_t)width * sizeof(float)));
-        if ((long long)part_rows * 4 >= n_rel) { rel = kRelPart; q.n_rel_lds = part_rows; lds += (size_t)part_rows * width * sizeof(float); }
-    }
-    if (group == 64) return launch_layer_g<64>(q, unit_w, rel, grid, lds, s);
-    if (group == 32) return launch_layer_g<32>(q, unit_w, rel, grid, lds, s);
-    return launch_layer_g<16>(q, unit_w, rel, grid, lds, s);
+    if (t.group == 64) return launch_layer_g<64>(q, unit_w, t.rel_mode, t.geo.grid, t.lds, s);
+    if (t.group == 32) return launch_layer_g<32>(q, unit_w, t.rel_mode, t.geo.grid, t.lds, s);
+    return launch_layer_g<16>(q, unit_w, t.rel_mode, t.geo.grid, t.lds, s);
 }
 
 static int layer_args_ok(const ultra_segments *fwd, const float *relation, const float *input, const int32_t *boundary_node,
                          const float *boundary_value, int64_t n_query, const float *weight, const float *bias,
                          const float *ln_weight, const float *ln_bias, int64_t n_rel) {
     if (fwd == nullptr) return ULTRA_ERR_NULL_POINTER;
-    if (!abi_ok(fwd)) return ULTRA_ERR_ABI;
+    if (!segments_abi_ok(fwd)) return ULTRA_ERR_ABI;
     if (!ultra_layer_forward_supported(fwd, n_query, n_rel)) return ULTRA_ERR_BAD_SHAPE;
     if (relation == nullptr || input == nullptr || weight == nullptr || bias == nullptr) return ULTRA_ERR_NULL_POINTER;
     if ((boundary_node == nullptr) != (boundary_value == nullptr)) return ULTRA_ERR_NULL_POINTER;

@@ -291,14 +291,8 @@ int ultra_relation_project_backward_f32(const float *relation, const float *cons
     q.blocks_per_layer = (int)per_layer;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds = (size_t)(2 * 64 * 68 + kPbWaves * 3 * 32 * 68) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(project_bwd_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(project_bwd_kernel, dim3((unsigned)(per_layer * n_layers)), dim3(kPbWaves * 64), lds, s, p);
-    HIP_TRY(hipGetLastError());
+    rc = launch_with_lds(project_bwd_kernel, p, (int)(per_layer * n_layers), lds, s, kPbWaves * 64, (int)lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(project_bwd_reduce_kernel, dim3((kPbSlab + 255) / 256, (unsigned)n_layers), dim3(256), 0, s, q);
     HIP_TRY(hipGetLastError());
     return ULTRA_OK;

@@ -62,7 +62,7 @@ __device__ __forceinline__ uint32_t lds_read1(uint32_t byte_addr) { return *(lds
 // the FIRST layer: the source whose input row is non-zero).  An inactive edge's gathers are issued past the end of their buffer
 // descriptors -- they return 0.0 without touching memory -- and its contribution is the same (+-0) the full computation adds:
 // identical bits, a fraction of the traffic.  One bitmap word read from LDS, a shift, a select and an OR per edge.  (ACT = 1 is
-// kept as a template value but not dispatched: d_input is not bound by its gathers, see launch_quad_w.)
+// kept as a template value but not dispatched: d_input is not bound by its gathers, see plan_path.h.)
 // DEAD (round 5; sum aggregation with mul = mul, unit weights): the words are the plan's `packed_dead` copy -- bit 31 marks an edge the
 // training step removed (weight 0 among weights of 1, ultra_edge_removal_marks).  A marked edge issues its gathers past the buffer
 // descriptors: they return 0.0, the message is relation * 0 (forward), 0 * relation (d_input), 0 * 0 (d_relation) = (+-0), which is

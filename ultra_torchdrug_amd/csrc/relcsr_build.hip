@@ -13,21 +13,9 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "ultra_rspmm.h"
-
-extern thread_local int ultra_detail_last_hip_error;
+#include "host_common.h"
 
 namespace {
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) {                         \
-            ultra_detail_last_hip_error = (int)_e;      \
-            (void)hipGetLastError();                    \
-            return ULTRA_ERR_HIP;                       \
-        }                                               \
-    } while (0)
 
 constexpr int kThreads = 256;
 inline unsigned grid_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads > 0 ? (n + kThreads - 1) / kThreads : 1); }

@@ -1,5 +1,5 @@
 // relgraph_dense.hip -- sum aggregation over a DENSE relation graph on the exact-f32 matrix cores (third translation unit of
-// libultra_rspmm.so; rspmm_kernels.hip's run_plan reaches it through csrc/relgraph_dense.h).
+// libultra_rspmm.so; rspmm_kernels.hip's run_plan reaches it through dense_launch, csrc/host_common.h).
 //
 // construct_relation_graph (/root/reference/ultra/rel_model.py:99-143) multiplies incidence matrices: the graph of relations
 // has 2R nodes, 4 edge types, unit weights, and is dense by nature (the FB15k237-shaped one is COMPLETE: 474 x 474 x 4 =
@@ -25,27 +25,16 @@
 
 #include <cstdint>
 
-#include "relgraph_dense.h"
-#include "ultra_rspmm.h"
-
-extern thread_local int ultra_detail_last_hip_error;
+#include "host_common.h"
 
 namespace {
 
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) {                         \
-            ultra_detail_last_hip_error = (int)_e;      \
-            (void)hipGetLastError();                    \
-            return ULTRA_ERR_HIP;                       \
-        }                                               \
-    } while (0)
-
-constexpr int kXcd = 8;
+using ultra_detail::kXcd;
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 using ultra_detail::DenseCall;
-constexpr int KIND_FWD = 0, KIND_DX = 1, KIND_DREL = 2;       // rspmm_kernels.hip's enum Kind
+using ultra_detail::KIND_FWD;
+using ultra_detail::KIND_DX;
+using ultra_detail::KIND_DREL;
 
 typedef float dn4 __attribute__((ext_vector_type(4)));
 constexpr int kDnU = 8;          // forward / d_input: sources per block = 2 matrix words (4 sources each) + 2 loads of gathered rows
@@ -442,23 +431,6 @@ inline long long dense_slack_bytes(int kind) { return kind == 0 ? 2 * kDnU * 64 
 
 namespace ultra_detail {
 
-// Is the plan's dense form usable for this call?  (what the header lists as preconditions; the caller has looked at the knobs)
-bool dense_applies(const DenseCall &c) {
-    const ultra_segments *seg = c.seg;
-    if (seg->dense == nullptr || seg->weight != nullptr || c.sum_op != ULTRA_SUM_ADD || c.n_rel != 4) return false;
-    if (c.F % 16 != 0 || c.F * 4 >= (1LL << 24)) return false;
-    if (seg->dense_cols != c.gather_rows || c.gather_rows * c.F * 4 >= (1LL << 31)) return false;
-    if (c.kind == KIND_DREL) {
-        if (c.mul_op != ULTRA_MUL_MUL || seg->n_rows != 4 || seg->dense_rows != c.gather2_rows) return false;
-        const long long n_vt = (seg->dense_rows + 15) / 16;
-        if (c.workspace == nullptr || c.workspace_bytes < (size_t)(n_vt * 4 * c.F) * sizeof(float)) return false;
-    } else {
-        if (seg->dense_rows != seg->n_rows) return false;
-        if (c.kind == KIND_FWD && c.add_rows == nullptr && c.bnode != nullptr && c.bdim <= 0) return false;
-    }
-    return true;
-}
-
 int dense_launch(const DenseCall &c, hipStream_t stream) {
     const ultra_segments *seg = c.seg;
     const long long F = c.F;
@@ -549,7 +521,7 @@ size_t ultra_relcsr_dense_bytes(int64_t n_rows, int64_t n_cols, int kind) {
 
 int ultra_relcsr_dense(const ultra_segments *plan, int64_t n_rows, int64_t n_cols, int kind, uint32_t *dense, void *stream) {
     if (plan == nullptr) return ULTRA_ERR_NULL_POINTER;
-    if (plan->struct_bytes != (uint32_t)sizeof(ultra_segments) || plan->abi_version != (uint32_t)ULTRA_RSPMM_ABI_VERSION) return ULTRA_ERR_ABI;
+    if (!ultra_detail::segments_abi_ok(plan)) return ULTRA_ERR_ABI;
     if (plan->n_edges < 0 || plan->n_edges > 0x7fffffffLL) return ULTRA_ERR_BAD_SHAPE;
     if (plan->n_edges > 0 && (plan->row == nullptr || plan->node_a == nullptr || plan->rel == nullptr)) return ULTRA_ERR_NULL_POINTER;
     const size_t bytes = ultra_relcsr_dense_bytes(n_rows, n_cols, kind);
@@ -572,7 +544,7 @@ int ultra_relcsr_dense(const ultra_segments *plan, int64_t n_rows, int64_t n_col
 }
 
 int ultra_dense_layer_supported(const ultra_segments *fwd, int64_t n_query) {
-    if (fwd == nullptr || fwd->struct_bytes != (uint32_t)sizeof(ultra_segments) || fwd->abi_version != (uint32_t)ULTRA_RSPMM_ABI_VERSION) return 0;
+    if (fwd == nullptr || !ultra_detail::segments_abi_ok(fwd)) return 0;
     if (fwd->dense == nullptr || fwd->weight != nullptr || n_query <= 0) return 0;
     if (fwd->dense_rows != fwd->n_rows || fwd->dense_rows != fwd->dense_cols) return 0;        // a layer maps the nodes onto themselves
     const long long F = n_query * 64;
@@ -583,7 +555,7 @@ int ultra_dense_layer_forward_f32(const ultra_segments *fwd, const float *relati
                                   const int32_t *boundary_node, const float *boundary_value, int64_t n_query, const float *weight,
                                   const float *bias, const float *ln_weight, const float *ln_bias, float ln_eps, int relu,
                                   int shortcut, float *out, void *stream) {
-    if (fwd != nullptr && (fwd->struct_bytes != (uint32_t)sizeof(ultra_segments) || fwd->abi_version != (uint32_t)ULTRA_RSPMM_ABI_VERSION))
+    if (fwd != nullptr && (!ultra_detail::segments_abi_ok(fwd)))
         return ULTRA_ERR_ABI;
     if (!ultra_dense_layer_supported(fwd, n_query)) return ULTRA_ERR_BAD_SHAPE;
     if (relation == nullptr || input == nullptr || boundary_node == nullptr || boundary_value == nullptr || weight == nullptr ||

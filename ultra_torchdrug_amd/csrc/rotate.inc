@@ -254,12 +254,13 @@ __global__ __launch_bounds__(kBlock) void rotate_segment_kernel(const RotParams 
 
 template <int KIND, int SUM>
 int launch_rotate_w(const RotParams &p, bool unit_w, bool rel_lds, int grid, size_t lds, hipStream_t stream) {
-    if (unit_w) {
-        if (rel_lds) return launch_with_lds(rotate_segment_kernel<KIND, SUM, true, true>, p, grid, lds, stream);
-        return launch_with_lds(rotate_segment_kernel<KIND, SUM, true, false>, p, grid, lds, stream);
-    }
-    if (rel_lds) return launch_with_lds(rotate_segment_kernel<KIND, SUM, false, true>, p, grid, lds, stream);
-    return launch_with_lds(rotate_segment_kernel<KIND, SUM, false, false>, p, grid, lds, stream);
+    return with_bool(unit_w, [&](auto uw) {
+        return with_bool(rel_lds, [&](auto rl) {
+            constexpr bool UW = decltype(uw)::value, RL = decltype(rl)::value;
+            if constexpr (RL && KIND == KIND_DREL) return (int)ULTRA_ERR_BAD_OP;      // rows are relations: no LDS table
+            else return launch_with_lds(rotate_segment_kernel<KIND, SUM, UW, RL>, p, grid, lds, stream, kBlock);
+        });
+    });
 }
 
 // One plan with rotate messages: the checks of run_plan, rotate_segment_kernel over the chunk schedule, then fixup_kernel
@@ -276,18 +277,14 @@ int run_rotate_plan(const ultra_segments *seg, RotParams p, int64_t n_rel, int64
     if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return ULTRA_ERR_WORKSPACE;
     if (seg->n_rows == 0) return ULTRA_OK;
 
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    rc = device_info(dev, &di);
+    rc = current_device_info(&di);
     if (rc) return rc;
 
     const int n_pairs = (int)(F / 2);
-    const int n_tiles = (n_pairs + kTile - 1) / kTile;
-    const int split = kXcd / gcd_int(n_tiles, kXcd);
+    const TileGeometry geo = tile_geometry(n_pairs, kTile, di->n_cu);      // a lane is a (re, im) pair
     const size_t lds_need = (size_t)n_rel * 2 * kTile * sizeof(float);
     const bool rel_lds = KIND != KIND_DREL && n_rel > 0 && lds_need <= (size_t)kMaxLdsBytes;
-    const int blocks_per_label = (di->n_cu + kXcd - 1) / kXcd;
 
     p.row = seg->row;
     p.node_a = seg->node_a;
@@ -301,16 +298,14 @@ int run_rotate_plan(const ultra_segments *seg, RotParams p, int64_t n_rel, int64
     p.n_pairs = n_pairs;
     p.n_chunks = (int)seg->n_chunks;
     p.n_rel = (int)n_rel;
-    p.n_tiles = n_tiles;
-    p.split = split;
-    p.n_slots = n_tiles * split;
-    p.blocks_per_label = blocks_per_label;
-    const int grid = blocks_per_label * kXcd;
+    p.n_tiles = geo.n_tiles;
+    p.split = geo.split;
+    p.n_slots = geo.n_slots;
+    p.blocks_per_label = geo.blocks_per_label;
     const size_t lds = kLdsHeader + (rel_lds ? lds_need : 0);
-    const bool unit_w = seg->weight == nullptr;
-    if (sum_op == ULTRA_SUM_ADD) rc = launch_rotate_w<KIND, ULTRA_SUM_ADD>(p, unit_w, rel_lds, grid, lds, stream);
-    else if (sum_op == ULTRA_SUM_MIN) rc = launch_rotate_w<KIND, ULTRA_SUM_MIN>(p, unit_w, rel_lds, grid, lds, stream);
-    else rc = launch_rotate_w<KIND, ULTRA_SUM_MAX>(p, unit_w, rel_lds, grid, lds, stream);
+    rc = with_sum(sum_op, [&](auto sum) {
+        return launch_rotate_w<KIND, decltype(sum)::value>(p, seg->weight == nullptr, rel_lds, geo.grid, lds, stream);
+    });
     if (rc) return rc;
 
     if (seg->n_long_rows > 0) {
@@ -327,11 +322,7 @@ int run_rotate_plan(const ultra_segments *seg, RotParams p, int64_t n_rel, int64
         fp.n_tiles = (int)((F + kTile - 1) / kTile);        // the fix-up walks plain 64-column tiles
         const long long waves = (long long)fp.n_long * fp.n_tiles;
         const int fgrid = (int)((waves + 3) / 4);
-        const int red = (KIND == KIND_FWD) ? sum_op : ULTRA_SUM_ADD;
-        if (red == ULTRA_SUM_ADD) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_ADD>, dim3(fgrid), dim3(256), 0, stream, fp);
-        else if (red == ULTRA_SUM_MIN) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MIN>, dim3(fgrid), dim3(256), 0, stream, fp);
-        else hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MAX>, dim3(fgrid), dim3(256), 0, stream, fp);
-        HIP_TRY(hipGetLastError());
+        return launch_fixup(fp, (KIND == KIND_FWD) ? sum_op : ULTRA_SUM_ADD, false, fgrid, stream);
     }
     return ULTRA_OK;
 }
@@ -388,21 +379,20 @@ __global__ __launch_bounds__(256) void rotate_weight_grad_kernel(const int32_t *
 }
 
 template <int SUM>
-void launch_rotate_weight_grad(const ultra_segments *fwd, const float *relation, const float *input, const float *output,
-                               const float *grad, float *d_weight, long long F, int half, hipStream_t s) {
+int launch_rotate_weight_grad(const ultra_segments *fwd, const float *relation, const float *input, const float *output,
+                              const float *grad, float *d_weight, long long F, int half, hipStream_t s) {
     const int n_pairs = (int)(F / 2);
     const bool two = n_pairs <= 32, unit = fwd->weight == nullptr;
     const long long n_slots = two ? (fwd->n_edges + 1) / 2 : fwd->n_edges;
     long long blocks = (n_slots + 3) / 4;
     if (blocks > 8192) blocks = 8192;
-#define ULTRA_RWCASE(U, T)                                                                                                  \
-    if (unit == U && two == T)                                                                                              \
-        hipLaunchKernelGGL((rotate_weight_grad_kernel<SUM, U, T>), dim3((int)blocks), dim3(256), 0, s, fwd->row, fwd->node_a, \
-                           fwd->rel, fwd->weight, relation, input, output, grad, d_weight, F, half, n_pairs,               \
-                           (long long)fwd->n_edges);
-    ULTRA_RWCASE(true, true)
-    ULTRA_RWCASE(true, false)
-    ULTRA_RWCASE(false, true)
-    ULTRA_RWCASE(false, false)
-#undef ULTRA_RWCASE
+    return with_bool(unit, [&](auto uw) {
+        return with_bool(two, [&](auto tw) -> int {
+            hipLaunchKernelGGL((rotate_weight_grad_kernel<SUM, decltype(uw)::value, decltype(tw)::value>), dim3((int)blocks), dim3(256),
+                               0, s, fwd->row, fwd->node_a, fwd->rel, fwd->weight, relation, input, output, grad, d_weight, F, half,
+                               n_pairs, (long long)fwd->n_edges);
+            HIP_TRY(hipGetLastError());
+            return ULTRA_OK;
+        });
+    });
 }

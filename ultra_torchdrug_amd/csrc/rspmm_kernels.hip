@@ -28,16 +28,16 @@
 #include <cstring>
 #include <mutex>
 
-#include "relgraph_dense.h"
-#include "ultra_rspmm.h"
+#include "host_common.h"
 
-// hipError_t of the last failing HIP call on this thread; shared with relcsr_build.hip (hidden: -fvisibility=hidden, the
-// library exports exactly what include/ultra_rspmm.h declares)
+// hipError_t of the last failing HIP call on this thread (host_common.h; hidden: -fvisibility=hidden, the library exports
+// exactly what include/ultra_rspmm.h declares)
 thread_local int ultra_detail_last_hip_error = 0;
 
 namespace {
 
-constexpr int kTile = 64;            // columns per tile == wave width
+using namespace ultra_detail;        // kTile, kXcd, kMaxLdsBytes, kLdsHeader, Kind (plan_path.h) and the host helpers
+
 #ifndef ULTRA_BLOCK
 #define ULTRA_BLOCK 1024
 #endif
@@ -54,12 +54,7 @@ constexpr int kUnroll = ULTRA_UNROLL;   // gathers in flight per wave
 #define ULTRA_BIG_GATHER_AUX 0
 #endif
 constexpr int kUnrollBig = ULTRA_UNROLL_BIG;   // ... for the big-graph variants of packed_kernel (DRAM gathers; 16 measured 3 % slower); <= PACK_SLACK
-constexpr int kXcd = 8;
 constexpr int kFixUnroll = 16;
-constexpr int kMaxLdsBytes = 156 * 1024;   // leave a little of the 160 KiB
-constexpr int kLdsHeader = 16;             // bytes in front of the tables: the workgroup's chunk ticket counter
-
-enum Kind { KIND_FWD = 0, KIND_DX = 1, KIND_DREL = 2 };
 
 struct KParams {
     const int32_t *row;
@@ -954,15 +949,12 @@ __global__ __launch_bounds__(kCbWaves * 64, PF ? 1 : 2) void combine_kernel(cons
 
 // ------------------------------------------------------------------------------------------------ host side
 
+static_assert(kBlock == kPlanBlock && kRgBlock == kPlanRgBlock, "plan_path.h states the workgroup sizes of its families");
+static_assert(kRelL2 == REL_L2 && kRelLds == REL_LDS && kRelPart == REL_PART, "plan_path.h's RelMode is rowgroup.inc's REL");
+
 // one-shot profiling events (ultra_rspmm_profile_next): bracket the next plan's segment kernel on its stream
 thread_local hipEvent_t g_prof_start = nullptr;
 thread_local hipEvent_t g_prof_stop = nullptr;
-// test/bench knob (ultra_rspmm_force_general_path): run the general kernel even where the packed one applies
-bool g_force_general = false;
-bool g_no_x_lds = false;
-bool g_no_quad = false;
-bool g_wide_groups = false;
-bool g_no_dead_words = false;
 #ifndef ULTRA_QUAD_U
 #define ULTRA_QUAD_U 8
 #endif
@@ -976,25 +968,329 @@ constexpr int kQuadUW = ULTRA_QUAD_UW;   // ... with per-edge weights: 8 would s
 #endif
 constexpr int kQuadUX = ULTRA_QUAD_UX;   // ... with the gathered matrix in LDS
 
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) {                         \
-            ultra_detail_last_hip_error = (int)_e;                 \
-            (void)hipGetLastError();                    \
-            return ULTRA_ERR_HIP;                       \
-        }                                               \
-    } while (0)
+// The launchers below take the variant from plan_path()'s decision and instantiate exactly the kernels a call can reach.
 
-struct DeviceInfo {
-    bool valid = false;
-    int n_cu = 0;            // compute units the persistent grids are sized for (= n_cu_total - ultra_rspmm_reserve_cus)
-    int n_cu_total = 0;
-    int lds_bytes = 0;
-    char arch[64] = {0};
-};
+template <int KIND, int SUM, int MUL>
+int launch_general(const KParams &p, const PlanPath &path, hipStream_t stream) {
+    return with_bool(path.unit_w, [&](auto uw) {
+        return with_bool(path.rel_lds, [&](auto rl) {
+            constexpr bool UW = decltype(uw)::value, RL = decltype(rl)::value;
+            // no LDS table where no per-edge relation operand is read: d_relation (rows are relations), d_input of add / add
+            if constexpr (RL && (KIND == KIND_DREL || (KIND == KIND_DX && SUM == ULTRA_SUM_ADD && MUL == ULTRA_MUL_ADD)))
+                return (int)ULTRA_ERR_BAD_OP;
+            else
+                return launch_with_lds(segment_kernel<KIND, SUM, MUL, UW, RL>, p, path.grid, path.lds, stream, kBlock);
+        });
+    });
+}
+
+template <int KIND, int SUM, int MUL>
+int launch_packed(const PParams &p, const PlanPath &path, hipStream_t stream) {
+    return with_bool(path.unit_w, [&](auto uw) {
+        auto go = [&](auto var) {
+            constexpr int V = decltype(var)::value;
+            constexpr int UN = (V == 2 || V == 3) ? kUnrollBig : kUnroll;
+            return launch_with_lds(packed_kernel<KIND, SUM, MUL, decltype(uw)::value, V, UN>, p, path.grid, path.lds, stream, kBlock);
+        };
+        if constexpr (KIND == KIND_DREL) return go(std::integral_constant<int, 0>{});      // the plain form only
+        else return with_int<0, 1, 2, 3, 4>(path.var, go);
+    });
+}
+
+template <int KIND, int SUM, int MUL>
+int launch_quad(const PParams &p, const PlanPath &path, hipStream_t stream) {
+#define ULTRA_Q(UW, XL, U, ACT, DEAD) \
+    return launch_with_lds(quad_kernel<KIND, SUM, MUL, UW, XL, U, ACT, DEAD>, p, path.grid, path.lds, stream, kBlock)
+    if constexpr (SUM == ULTRA_SUM_ADD && MUL == ULTRA_MUL_MUL) {       // the plan's marked word copy (quad.inc DEAD)
+        if (path.dead) {
+            if constexpr (KIND == KIND_DREL) {
+                if (path.act == ACT_BITS) ULTRA_Q(true, false, kQuadU, 2, true);
+            }
+            ULTRA_Q(true, false, kQuadU, 0, true);
+        }
+    }
+    if constexpr (KIND == KIND_DREL) {                                  // activity masks (quad.inc ACT)
+        if (path.act == ACT_BITS) {
+            if (path.unit_w) ULTRA_Q(true, false, kQuadU, 2, false);
+            ULTRA_Q(false, false, kQuadUW, 2, false);
+        }
+        if constexpr (MUL == ULTRA_MUL_MUL) {                           // (mul = add does not depend on the input rows)
+            if (path.act == ACT_NODE) {
+                if (path.unit_w) ULTRA_Q(true, false, kQuadU, 3, false);
+                ULTRA_Q(false, false, kQuadUW, 3, false);
+            }
+        }
+    }
+    if constexpr (KIND != KIND_DREL || MUL == ULTRA_MUL_MUL) {          // d_relation of mul = add reads no `input` row
+        if (path.x_lds) {
+            if (path.unit_w) ULTRA_Q(true, true, kQuadUX, 0, false);
+            ULTRA_Q(false, true, kQuadUW, 0, false);
+        }
+    }
+    if (path.unit_w) ULTRA_Q(true, false, kQuadU, 0, false);
+    ULTRA_Q(false, false, kQuadUW, 0, false);
+#undef ULTRA_Q
+}
+
+// rowgroup_kernel.  BACKWARD: the d_input contribution order (sum-aggregation only), where a relation operand exists only
+// for mul = mul; the forward always has one.
+template <int SUM, int MUL, bool BACKWARD>
+int launch_rowgroup(const RowGroupParams &p, const PlanPath &path, hipStream_t stream) {
+    constexpr bool NEEDS_REL = !BACKWARD || MUL == ULTRA_MUL_MUL;
+    return with_int<16, 32, 64>(path.group, [&](auto g) {
+        return with_bool(path.unit_w, [&](auto uw) {
+            return with_int<kRelL2, kRelLds, kRelPart>(path.rel_mode, [&](auto rel) {
+                constexpr int REL = decltype(rel)::value;
+                if constexpr (!NEEDS_REL && REL != kRelL2) return (int)ULTRA_ERR_BAD_OP;
+                else
+                    return launch_with_lds(rowgroup_kernel<SUM, MUL, decltype(uw)::value, REL, NEEDS_REL, BACKWARD, decltype(g)::value>,
+                                           p, path.grid, path.lds, stream, kRgBlock);
+            });
+        });
+    });
+}
+
+void fill_tiling(RowGroupParams &q, const PlanPath &path) {
+    q.n_tiles = path.geo.n_tiles;
+    q.split = path.geo.split;
+    q.n_slots = path.geo.n_slots;
+    q.blocks_per_label = path.geo.blocks_per_label;
+    q.n_rel_lds = path.n_rel_lds;
+}
+
+// the kernels behind the rowgroup, quad and packed families: every operator pair forward, sum-aggregation backward
+template <int KIND, typename Fn>
+int with_fast_ops(int sum_op, int mul_op, Fn &&fn) {
+    if constexpr (KIND == KIND_FWD) return with_sum_mul(sum_op, mul_op, fn);
+    else return with_mul(mul_op, [&](auto mul) { return fn(std::integral_constant<int, ULTRA_SUM_ADD>{}, mul); });
+}
+
+inline bool aligned16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+
+// packed_kernel / quad_kernel over the plan's packed words
+template <int KIND>
+int launch_words(const ultra_segments *seg, const KParams &p, const PlanPath &path, int64_t gather_rows, int64_t gather2_rows,
+                 int64_t n_rel, int64_t F, int sum_op, int mul_op, hipStream_t stream) {
+    const bool big = seg->packed_src_shift >= 32;          // node ids live in node_a, not in the packed word
+    const bool quad = path.family == FAM_QUAD;
+    const unsigned long long relation_bytes = (unsigned long long)n_rel * (unsigned long long)F * 4ull;
+    const unsigned long long meta_bytes = ((unsigned long long)seg->n_edges + 16ull) * 4ull;   // PACK_SLACK words follow
+    const unsigned long long out_bytes = (unsigned long long)seg->n_rows * (unsigned long long)F * 4ull;
+    PParams q{};
+    q.meta = path.dead ? seg->packed_dead : seg->packed;
+    q.meta2 = reinterpret_cast<const uint32_t *>(big ? seg->node_a : seg->node_b);
+    q.weight = path.dead ? nullptr : seg->weight;
+    q.chunks = p.chunks;
+    q.relation = p.relation;
+    q.gather = (KIND == KIND_DX) ? p.grad : p.input;
+    q.gather2 = p.grad;
+    q.add_rows = p.add_rows;
+    q.bnode = p.bnode;
+    q.bvec = p.bvec;
+    q.bdim = p.bdim;
+    q.out = p.out;
+    q.partial = p.partial;
+    q.F = F;
+    q.gather_bytes = (uint32_t)((unsigned long long)gather_rows * (unsigned long long)F * 4ull);
+    q.gather2_bytes = (uint32_t)((unsigned long long)gather2_rows * (unsigned long long)F * 4ull);
+    q.relation_bytes = (uint32_t)(relation_bytes < 0xffff0000ull ? relation_bytes : 0);
+    q.meta_bytes = (uint32_t)(meta_bytes < 0xffff0000ull ? meta_bytes : 0);
+    q.meta2_bytes = (uint32_t)((unsigned long long)seg->n_edges * 4ull);
+    q.out_bytes = (uint32_t)(out_bytes < 0xffff0000ull ? out_bytes : 0);
+    q.row_bytes = (uint32_t)(F * 4);
+    q.src_shift = (uint32_t)seg->packed_src_shift;
+    q.rel_mask = big ? 0xffffff00u : ((1u << (seg->packed_src_shift - 8)) - 1u) << 8;
+    q.n_gather_rows = (int)gather_rows;
+    if (!big && seg->n_hot > 0) {
+        q.hot_nodes = seg->hot_nodes;
+        q.n_hot = (int)seg->n_hot;
+    }
+    q.n_chunks = p.n_chunks;
+    q.n_rel = p.n_rel;
+    q.n_tiles = p.n_tiles;
+    q.split = p.split;
+    q.n_slots = p.n_slots;
+    q.blocks_per_label = p.blocks_per_label;
+    if (quad) {
+        q.concurrent = path.concurrent;
+        if (path.act == ACT_BITS) {
+            q.act_bits = p.act_bits;
+            q.act_words = p.act_words;
+        } else if (path.act == ACT_NODE) {
+            q.act_node = p.act_node;
+        }
+    }
+    return with_fast_ops<KIND>(sum_op, mul_op, [&](auto sum, auto mul) {
+        constexpr int S = decltype(sum)::value, M = decltype(mul)::value;
+        return quad ? launch_quad<KIND, S, M>(q, path, stream) : launch_packed<KIND, S, M>(q, path, stream);
+    });
+}
+
+// fixup_kernel over the split rows: pieces added in piece order
+int launch_fixup(const FixParams &fp, int red, bool many_pieces, int grid, hipStream_t stream) {
+    if (red == ULTRA_SUM_ADD && many_pieces) hipLaunchKernelGGL((fixup_kernel<ULTRA_SUM_ADD, 64>), dim3(grid), dim3(256), 0, stream, fp);
+    else if (red == ULTRA_SUM_ADD) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_ADD>, dim3(grid), dim3(256), 0, stream, fp);
+    else if (red == ULTRA_SUM_MIN) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MIN>, dim3(grid), dim3(256), 0, stream, fp);
+    else hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MAX>, dim3(grid), dim3(256), 0, stream, fp);
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+// Runs one plan: validate, decide (plan_path.h), fill the parameters of the chosen family, launch, then fixup_kernel over the
+// split rows.
+template <int KIND>
+int run_plan(const ultra_segments *seg, KParams p, int64_t gather_rows, int64_t gather2_rows, int64_t n_rel, int64_t F,
+             int sum_op, int mul_op, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+    int rc = check_segments(seg);
+    if (rc) return rc;
+    if (F <= 0 || n_rel < 0 || n_rel > 0x7fffffffLL) return ULTRA_ERR_BAD_SHAPE;
+    if (sum_op < 0 || sum_op > 2 || mul_op < 0 || mul_op > 1) return ULTRA_ERR_BAD_OP;
+    const size_t need = ultra_rspmm_workspace_bytes(seg, F);
+    if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return ULTRA_ERR_WORKSPACE;
+    if (seg->n_rows == 0) return ULTRA_OK;
+
+    DeviceInfo *di = nullptr;
+    rc = current_device_info(&di);
+    if (rc) return rc;
+
+    p.partial = static_cast<float *>(workspace);
+    PlanInput in;
+    in.kind = KIND; in.sum_op = sum_op; in.mul_op = mul_op;
+    in.F = F; in.n_rel = n_rel; in.gather_rows = gather_rows; in.gather2_rows = gather2_rows;
+    in.has_weight = seg->weight != nullptr; in.has_node_b = seg->node_b != nullptr; in.has_row_ptr = seg->row_ptr != nullptr;
+    in.has_packed = seg->packed != nullptr; in.has_packed_dead = seg->packed_dead != nullptr; in.has_dense = seg->dense != nullptr;
+    in.packed_src_shift = seg->packed_src_shift; in.n_rows = seg->n_rows; in.n_edges = seg->n_edges;
+    in.n_long_rows = seg->n_long_rows; in.n_pieces = seg->n_pieces; in.n_hot = seg->n_hot;
+    in.dense_rows = seg->dense_rows; in.dense_cols = seg->dense_cols;
+    in.has_add_rows = p.add_rows != nullptr; in.has_bnode = p.bnode != nullptr; in.bdim = p.bdim;
+    in.has_act_bits = p.act_bits != nullptr; in.has_act_node = p.act_node != nullptr; in.act_words = p.act_words;
+    in.has_workspace = workspace != nullptr; in.workspace_bytes = workspace_bytes;
+    in.aligned = (aligned16(p.input) ? AL_INPUT : 0) | (aligned16(p.grad) ? AL_GRAD : 0) | (aligned16(p.out) ? AL_OUT : 0) |
+                 (aligned16(p.relation) ? AL_RELATION : 0) | (aligned16(p.add_rows) ? AL_ADD_ROWS : 0) |
+                 (aligned16(p.partial) ? AL_PARTIAL : 0) | (aligned16(p.bvec) ? AL_BVEC : 0);
+    in.knobs = g_knobs;
+    in.n_cu = di->n_cu;
+    in.gfx950 = std::strncmp(di->arch, "gfx950", 6) == 0;
+    PlanPath path = plan_path(in);
+    if (path.family == FAM_QUAD) {
+        if (const char *force = getenv("ULTRA_CONC")) {      // experiments (tools/conc_ab.sh)
+            const char *min_rows = getenv("ULTRA_CONC_MIN_ROWS");
+            force_concurrent(path, atoi(force), min_rows != nullptr, min_rows != nullptr ? atoll(min_rows) : 0, gather_rows);
+        }
+    }
+
+    hipEvent_t ev_start = g_prof_start, ev_stop = g_prof_stop;
+    g_prof_start = g_prof_stop = nullptr;
+    // (not while the stream is being captured: the ROCm 7.0 runtime bundled with PyTorch rejects external
+    // event-record nodes, so the hook is simply ignored inside a hipGraph capture)
+    if (ev_start != nullptr || ev_stop != nullptr) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing(stream, &cs));
+        if (cs != hipStreamCaptureStatusNone) ev_start = ev_stop = nullptr;
+    }
+    if (ev_start != nullptr) HIP_TRY(hipEventRecord(ev_start, stream));
+    if (path.status) return path.status;
+
+    p.row = seg->row;
+    p.node_a = seg->node_a;
+    p.node_b = seg->node_b;
+    p.rel = seg->rel;
+    p.weight = seg->weight;
+    p.chunks = reinterpret_cast<const int4 *>(seg->chunks);
+    p.F = F;
+    p.n_chunks = (int)seg->n_chunks;
+    p.n_rel = (int)n_rel;
+    p.n_tiles = path.geo.n_tiles;
+    p.split = path.geo.split;
+    p.n_slots = path.geo.n_slots;
+    p.blocks_per_label = path.geo.blocks_per_label;
+    switch (path.family) {
+        case FAM_DENSE: {
+            const DenseCall call{seg, KIND, mul_op, p.relation, p.input, p.grad, p.add_rows, p.bnode, p.bvec, p.bdim, p.out, workspace, F};
+            rc = dense_launch(call, stream);
+            break;
+        }
+        case FAM_ROWGROUP:
+            if constexpr (KIND != KIND_DREL) {
+                RowGroupParams q{};
+                q.row_ptr = seg->row_ptr;
+                q.col = seg->node_a;
+                q.rel = seg->rel;
+                q.weight = seg->weight;
+                q.relation = p.relation;
+                q.gather = (KIND == KIND_DX) ? p.grad : p.input;
+                q.add_rows = p.add_rows;
+                q.bnode = p.bnode;
+                q.bvec = p.bvec;
+                q.bdim = p.bdim;
+                q.out = p.out;
+                q.F = F;
+                q.n_rows = (int)seg->n_rows;
+                q.n_rel = (int)n_rel;
+                fill_tiling(q, path);
+                rc = with_fast_ops<KIND>(sum_op, mul_op, [&](auto sum, auto mul) {
+                    return launch_rowgroup<decltype(sum)::value, decltype(mul)::value, KIND == KIND_DX>(q, path, stream);
+                });
+            }
+            break;
+        case FAM_QUAD:
+        case FAM_PACKED:
+            rc = launch_words<KIND>(seg, p, path, gather_rows, gather2_rows, n_rel, F, sum_op, mul_op, stream);
+            break;
+        default:
+            rc = with_sum_mul(sum_op, mul_op, [&](auto sum, auto mul) {
+                return launch_general<KIND, decltype(sum)::value, decltype(mul)::value>(p, path, stream);
+            });
+    }
+    if (rc) return rc;
+    if (ev_stop != nullptr) HIP_TRY(hipEventRecord(ev_stop, stream));
+
+    if (path.fixup != FIX_NONE) {
+        FixParams fp;
+        fp.long_rows = seg->long_rows;
+        fp.partial = p.partial;
+        fp.add_rows = p.add_rows;
+        fp.bnode = p.bnode;
+        fp.bvec = p.bvec;
+        fp.bdim = p.bdim;
+        fp.out = p.out;
+        fp.F = F;
+        fp.n_long = (int)seg->n_long_rows;
+        fp.n_tiles = path.geo.n_tiles;
+        return launch_fixup(fp, (KIND == KIND_FWD) ? sum_op : ULTRA_SUM_ADD, path.fixup == FIX_MANY, path.fixup_grid, stream);
+    }
+    return ULTRA_OK;
+}
+
+#include "rotate.inc"
+
+}  // namespace
+
+namespace ultra_detail {
+
+Knobs g_knobs;
+
+namespace {
 DeviceInfo g_dev[16];
 int g_reserve_cus = 0;       // ultra_rspmm_reserve_cus
+
+struct LdsAttrTable {
+    static constexpr int kSlots = 512;
+    const void *kern[kSlots];
+    int dev[kSlots];
+    int n = 0;
+    bool seen(const void *k, int d) const {
+        for (int i = 0; i < n; ++i)
+            if (kern[i] == k && dev[i] == d) return true;
+        return false;
+    }
+    void add(const void *k, int d) {
+        if (n < kSlots) { kern[n] = k; dev[n] = d; ++n; }     // table full: the attribute is simply set again next time
+    }
+};
+LdsAttrTable g_lds_attr;
+std::mutex g_lds_attr_mutex;
+}  // namespace
 
 int device_info(int device, DeviceInfo **out) {
     if (device < 0 || device >= 16) return ULTRA_ERR_NO_DEVICE;
@@ -1012,556 +1308,23 @@ int device_info(int device, DeviceInfo **out) {
     return ULTRA_OK;
 }
 
-int gcd_int(int a, int b) {
-    while (b) {
-        int t = a % b;
-        a = b;
-        b = t;
-    }
-    return a;
+int current_device_info(DeviceInfo **out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    return device_info(dev, out);
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a property of ONE kernel function.  Every packed_kernel / quad_kernel
-// instance has the same pointer type void (*)(PParams), so a function-local static would be shared by all of them:
-// the "already set" table is keyed on the kernel's address (per device).
-struct LdsAttrTable {
-    static constexpr int kSlots = 512;
-    const void *kern[kSlots];
-    int dev[kSlots];
-    int n = 0;
-    bool seen(const void *k, int d) const {
-        for (int i = 0; i < n; ++i)
-            if (kern[i] == k && dev[i] == d) return true;
-        return false;
-    }
-    void add(const void *k, int d) {
-        if (n < kSlots) { kern[n] = k; dev[n] = d; ++n; }     // table full: the attribute is simply set again next time
-    }
-};
-LdsAttrTable g_lds_attr;
-std::mutex g_lds_attr_mutex;
-
-int ensure_lds_attribute(const void *kern, size_t lds) {
+int ensure_lds_attribute(const void *kern, size_t lds, int max_bytes) {
     if (lds <= 48 * 1024) return ULTRA_OK;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_lds_attr_mutex);
     if (g_lds_attr.seen(kern, dev)) return ULTRA_OK;
-    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes));
+    HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes));
     g_lds_attr.add(kern, dev);
     return ULTRA_OK;
 }
 
-template <typename Kern, typename Params>
-int launch_with_lds(Kern kern, const Params &p, int grid, size_t lds, hipStream_t stream, int block = kBlock) {
-    const int rc = ensure_lds_attribute(reinterpret_cast<const void *>(kern), lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
-}
-
-template <int KIND, int SUM, int MUL, bool UNIT_W, bool REL_LDS>
-int launch_instance(const KParams &p, int grid, size_t lds, hipStream_t stream) {
-    return launch_with_lds(segment_kernel<KIND, SUM, MUL, UNIT_W, REL_LDS>, p, grid, lds, stream);
-}
-
-template <int KIND, int SUM, int MUL>
-int launch_wl(const KParams &p, bool unit_w, bool rel_lds, int grid, size_t lds, hipStream_t stream) {
-    if constexpr (KIND == KIND_DREL) {   // rows are relations: no per-edge relation operand, no LDS table
-        if (unit_w) return launch_instance<KIND, SUM, MUL, true, false>(p, grid, kLdsHeader, stream);
-        return launch_instance<KIND, SUM, MUL, false, false>(p, grid, kLdsHeader, stream);
-    } else {
-        if (unit_w) {
-            if (rel_lds) return launch_instance<KIND, SUM, MUL, true, true>(p, grid, lds, stream);
-            return launch_instance<KIND, SUM, MUL, true, false>(p, grid, lds, stream);
-        }
-        if (rel_lds) return launch_instance<KIND, SUM, MUL, false, true>(p, grid, lds, stream);
-        return launch_instance<KIND, SUM, MUL, false, false>(p, grid, lds, stream);
-    }
-}
-
-template <int KIND>
-int launch_ops(const KParams &p, int sum_op, int mul_op, bool unit_w, bool rel_lds, int grid, size_t lds,
-               hipStream_t stream) {
-#define ULTRA_CASE(S, M)                                                    \
-    if (sum_op == S && mul_op == M) return launch_wl<KIND, S, M>(p, unit_w, rel_lds, grid, lds, stream);
-    ULTRA_CASE(ULTRA_SUM_ADD, ULTRA_MUL_MUL)
-    ULTRA_CASE(ULTRA_SUM_ADD, ULTRA_MUL_ADD)
-    ULTRA_CASE(ULTRA_SUM_MIN, ULTRA_MUL_MUL)
-    ULTRA_CASE(ULTRA_SUM_MIN, ULTRA_MUL_ADD)
-    ULTRA_CASE(ULTRA_SUM_MAX, ULTRA_MUL_MUL)
-    ULTRA_CASE(ULTRA_SUM_MAX, ULTRA_MUL_ADD)
-#undef ULTRA_CASE
-    return ULTRA_ERR_BAD_OP;
-}
-
-// The fence of the boundary (ABI 8): the caller's struct must be THIS header's, field for field.  Only the two leading
-// fields are read before that is known.
-inline bool segments_abi_ok(const ultra_segments *s) {
-    return s->struct_bytes == (uint32_t)sizeof(ultra_segments) && s->abi_version == (uint32_t)ULTRA_RSPMM_ABI_VERSION;
-}
-
-int check_segments(const ultra_segments *s) {
-    if (s == nullptr) return ULTRA_ERR_NULL_POINTER;
-    if (!segments_abi_ok(s)) return ULTRA_ERR_ABI;
-    if (s->n_rows < 0 || s->n_edges < 0 || s->n_chunks < 0 || s->n_pieces < 0 || s->n_long_rows < 0)
-        return ULTRA_ERR_BAD_SHAPE;
-    if (s->n_rows > 0x7fffffffLL || s->n_edges > 0x7fffffffLL || s->n_chunks > 0x7fffffffLL) return ULTRA_ERR_BAD_SHAPE;
-    if (s->n_edges > 0 && (s->row == nullptr || s->node_a == nullptr || s->rel == nullptr)) return ULTRA_ERR_NULL_POINTER;
-    if (s->n_chunks > 0 && s->chunks == nullptr) return ULTRA_ERR_NULL_POINTER;
-    if (s->n_long_rows > 0 && s->long_rows == nullptr) return ULTRA_ERR_NULL_POINTER;
-    return ULTRA_OK;
-}
-
-template <int KIND, int SUM, int MUL>
-int launch_packed_w(const PParams &p, bool unit_w, int var, int grid, size_t lds, hipStream_t stream) {
-#define ULTRA_VAR(V)                                                                                                  \
-    if (var == V) {                                                                                                   \
-        constexpr int UN = (V == 2 || V == 3) ? kUnrollBig : kUnroll;                                                 \
-        if (unit_w) return launch_with_lds(packed_kernel<KIND, SUM, MUL, true, V, UN>, p, grid, lds, stream);        \
-        return launch_with_lds(packed_kernel<KIND, SUM, MUL, false, V, UN>, p, grid, lds, stream);                   \
-    }
-    if constexpr (KIND != KIND_DREL) {
-        ULTRA_VAR(1)
-        ULTRA_VAR(2)
-        ULTRA_VAR(3)
-        ULTRA_VAR(4)
-    }
-    ULTRA_VAR(0)
-#undef ULTRA_VAR
-    return ULTRA_ERR_BAD_OP;
-}
-
-template <int KIND>
-int launch_packed(const PParams &p, int sum_op, int mul_op, bool unit_w, int var, int grid, size_t lds,
-                  hipStream_t stream) {
-    if constexpr (KIND == KIND_FWD) {
-#define ULTRA_PCASE(S, M) \
-    if (sum_op == S && mul_op == M) return launch_packed_w<KIND_FWD, S, M>(p, unit_w, var, grid, lds, stream);
-        ULTRA_PCASE(ULTRA_SUM_ADD, ULTRA_MUL_MUL)
-        ULTRA_PCASE(ULTRA_SUM_ADD, ULTRA_MUL_ADD)
-        ULTRA_PCASE(ULTRA_SUM_MIN, ULTRA_MUL_MUL)
-        ULTRA_PCASE(ULTRA_SUM_MIN, ULTRA_MUL_ADD)
-        ULTRA_PCASE(ULTRA_SUM_MAX, ULTRA_MUL_MUL)
-        ULTRA_PCASE(ULTRA_SUM_MAX, ULTRA_MUL_ADD)
-#undef ULTRA_PCASE
-    } else if constexpr (KIND == KIND_DX) {
-        if (mul_op == ULTRA_MUL_MUL) return launch_packed_w<KIND_DX, ULTRA_SUM_ADD, ULTRA_MUL_MUL>(p, unit_w, var, grid, lds, stream);
-        return launch_packed_w<KIND_DX, ULTRA_SUM_ADD, ULTRA_MUL_ADD>(p, unit_w, var, grid, lds, stream);
-    } else {
-        if (mul_op == ULTRA_MUL_MUL) return launch_packed_w<KIND_DREL, ULTRA_SUM_ADD, ULTRA_MUL_MUL>(p, unit_w, 0, grid, kLdsHeader, stream);
-        return launch_packed_w<KIND_DREL, ULTRA_SUM_ADD, ULTRA_MUL_ADD>(p, unit_w, 0, grid, kLdsHeader, stream);
-    }
-    return ULTRA_ERR_BAD_OP;
-}
-
-template <int KIND, int SUM, int MUL>
-int launch_quad_w(const PParams &p, bool unit_w, bool x_lds, int grid, size_t lds, hipStream_t stream, bool dead = false) {
-    // the plan's marked word copy (quad.inc DEAD): removed edges by bit 31, every other weight 1 -- run_plan decides
-    if constexpr (SUM == ULTRA_SUM_ADD && MUL == ULTRA_MUL_MUL) {
-        if (dead && !x_lds && p.act_node == nullptr) {
-            if constexpr (KIND == KIND_DREL) {
-                if (p.act_bits != nullptr)
-                    return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, false, kQuadU, 2, true>, p, grid, lds, stream);
-            }
-            return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, false, kQuadU, 0, true>, p, grid, lds, stream);
-        }
-    }
-    // activity masks (see quad.inc ACT): d_relation only.  The d_input form (ACT = 1) was built and measured: that kernel is
-    // bound by its per-row epilogue (read-modify-write of the gradient it accumulates into) and per-edge issue, not by its
-    // gathers -- 137 vs 138 us on the FB15k237-shaped graph, 156 vs 148 us on the WN18RR-shaped one with the mask -- so it is
-    // not dispatched; d_relation (two gathers per edge) gains 30-45 %.
-    if constexpr (KIND == KIND_DREL) {
-        if (p.act_bits != nullptr && !x_lds) {
-            if (unit_w) return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, false, kQuadU, 2>, p, grid, lds, stream);
-            return launch_with_lds(quad_kernel<KIND, SUM, MUL, false, false, kQuadUW, 2>, p, grid, lds, stream);
-        }
-        if (p.act_node != nullptr && !x_lds) {
-            if (unit_w) return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, false, kQuadU, 3>, p, grid, lds, stream);
-            return launch_with_lds(quad_kernel<KIND, SUM, MUL, false, false, kQuadUW, 3>, p, grid, lds, stream);
-        }
-    }
-    if constexpr (KIND != KIND_DREL || MUL == ULTRA_MUL_MUL) {       // d_relation of mul = add reads no `input` row
-        if (x_lds) {
-            if (unit_w) return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, true, kQuadUX>, p, grid, lds, stream);
-            return launch_with_lds(quad_kernel<KIND, SUM, MUL, false, true, kQuadUW>, p, grid, lds, stream);
-        }
-    }
-    if (unit_w) return launch_with_lds(quad_kernel<KIND, SUM, MUL, true, false, kQuadU>, p, grid, lds, stream);
-    return launch_with_lds(quad_kernel<KIND, SUM, MUL, false, false, kQuadUW>, p, grid, lds, stream);
-}
-
-template <int KIND>
-int launch_quad(const PParams &p, int sum_op, int mul_op, bool unit_w, bool x_lds, int grid, size_t lds,
-                hipStream_t stream, bool dead = false) {
-    if constexpr (KIND == KIND_FWD) {
-#define ULTRA_QCASE(S, M) \
-    if (sum_op == S && mul_op == M) return launch_quad_w<KIND_FWD, S, M>(p, unit_w, x_lds, grid, lds, stream, dead);
-        ULTRA_QCASE(ULTRA_SUM_ADD, ULTRA_MUL_MUL)
-        ULTRA_QCASE(ULTRA_SUM_ADD, ULTRA_MUL_ADD)
-        ULTRA_QCASE(ULTRA_SUM_MIN, ULTRA_MUL_MUL)
-        ULTRA_QCASE(ULTRA_SUM_MIN, ULTRA_MUL_ADD)
-        ULTRA_QCASE(ULTRA_SUM_MAX, ULTRA_MUL_MUL)
-        ULTRA_QCASE(ULTRA_SUM_MAX, ULTRA_MUL_ADD)
-#undef ULTRA_QCASE
-    } else if constexpr (KIND == KIND_DX) {
-        if (mul_op == ULTRA_MUL_MUL) return launch_quad_w<KIND_DX, ULTRA_SUM_ADD, ULTRA_MUL_MUL>(p, unit_w, x_lds, grid, lds, stream, dead);
-        return launch_quad_w<KIND_DX, ULTRA_SUM_ADD, ULTRA_MUL_ADD>(p, unit_w, x_lds, grid, lds, stream);
-    } else {
-        if (mul_op == ULTRA_MUL_MUL) return launch_quad_w<KIND_DREL, ULTRA_SUM_ADD, ULTRA_MUL_MUL>(p, unit_w, x_lds, grid, lds, stream, dead);
-        return launch_quad_w<KIND_DREL, ULTRA_SUM_ADD, ULTRA_MUL_ADD>(p, unit_w, false, grid, p.act_bits != nullptr ? lds : (size_t)kLdsHeader, stream);
-    }
-    return ULTRA_ERR_BAD_OP;
-}
-
-// rowgroup_kernel dispatch.  backward: the d_input contribution order; needs_rel: a relation operand exists; group:
-// lanes per row (16 / 32 / 64 -> column tiles of 64 / 128 / 256).
-template <int SUM, int MUL, bool BACKWARD, int G>
-int launch_rowgroup_w(const RowGroupParams &p, bool unit_w, int rel, bool needs_rel, int grid, size_t lds,
-                      hipStream_t stream) {
-#define ULTRA_RG(UW, RL, NR) return launch_with_lds(rowgroup_kernel<SUM, MUL, UW, RL, NR, BACKWARD, G>, p, grid, lds, stream, kRgBlock)
-    if (!needs_rel) {
-        if (unit_w) ULTRA_RG(true, kRelL2, false);
-        ULTRA_RG(false, kRelL2, false);
-    }
-    if (unit_w) {
-        if (rel == kRelLds) ULTRA_RG(true, kRelLds, true);
-        if (rel == kRelPart) ULTRA_RG(true, kRelPart, true);
-        ULTRA_RG(true, kRelL2, true);
-    }
-    if (rel == kRelLds) ULTRA_RG(false, kRelLds, true);
-    if (rel == kRelPart) ULTRA_RG(false, kRelPart, true);
-    ULTRA_RG(false, kRelL2, true);
-#undef ULTRA_RG
-}
-
-template <int G>
-int launch_rowgroup_g(const RowGroupParams &p, bool backward, int sum_op, int mul_op, bool unit_w, int rel, int grid,
-                      size_t lds, hipStream_t stream) {
-    if (backward) {       // d_input of sum-aggregation: the relation operand exists only for mul = mul
-        if (mul_op == ULTRA_MUL_MUL)
-            return launch_rowgroup_w<ULTRA_SUM_ADD, ULTRA_MUL_MUL, true, G>(p, unit_w, rel, true, grid, lds, stream);
-        return launch_rowgroup_w<ULTRA_SUM_ADD, ULTRA_MUL_ADD, true, G>(p, unit_w, kRelL2, false, grid, kLdsHeader, stream);
-    }
-#define ULTRA_RCASE(S, M) \
-    if (sum_op == S && mul_op == M) return launch_rowgroup_w<S, M, false, G>(p, unit_w, rel, true, grid, lds, stream);
-    ULTRA_RCASE(ULTRA_SUM_ADD, ULTRA_MUL_MUL)
-    ULTRA_RCASE(ULTRA_SUM_ADD, ULTRA_MUL_ADD)
-    ULTRA_RCASE(ULTRA_SUM_MIN, ULTRA_MUL_MUL)
-    ULTRA_RCASE(ULTRA_SUM_MIN, ULTRA_MUL_ADD)
-    ULTRA_RCASE(ULTRA_SUM_MAX, ULTRA_MUL_MUL)
-    ULTRA_RCASE(ULTRA_SUM_MAX, ULTRA_MUL_ADD)
-#undef ULTRA_RCASE
-    return ULTRA_ERR_BAD_OP;
-}
-
-// Fills the tiling fields of `q` and launches.  Wide groups only where the gathered matrix cannot be cache-resident
-// (beyond the 256 MB Infinity Cache): there one contiguous fetch per edge beats L2 locality of 64-column tiles.
-int launch_rowgroup(RowGroupParams &q, bool backward, int sum_op, int mul_op, bool unit_w, long long gather_rows, int n_cu,
-                    hipStream_t stream) {
-    const long long F = q.F;
-    if (F >= (1LL << 30)) return ULTRA_ERR_BAD_SHAPE;         // row bytes are a 32-bit factor of the address arithmetic
-    const bool dram = g_wide_groups || (double)gather_rows * (double)F * 4.0 > 256.0 * 1024 * 1024;
-    const int group = (dram && F % 256 == 0) ? 64 : ((dram && F % 128 == 0) ? 32 : 16);
-    const int width = 4 * group;
-    q.n_tiles = (int)((F + width - 1) / width);
-    q.split = kXcd / gcd_int(q.n_tiles, kXcd);
-    // a part's rows are stored through one buffer descriptor with 32-bit offsets: keep rows_per_part * row bytes < 4 GiB
-    while (((long long)q.n_rows + q.split - 1) / q.split * F * 4 >= (1LL << 32) - 65536 && q.split < (1 << 20)) q.split *= 2;
-    q.n_slots = q.n_tiles * q.split;
-    q.blocks_per_label = (n_cu + kXcd - 1) / kXcd;
-    const size_t lds_need = (size_t)q.n_rel * width * sizeof(float);
-    const bool rel_fits = q.n_rel > 0 && lds_need <= (size_t)kMaxLdsBytes;
-    const int grid = q.blocks_per_label * kXcd;
-    // Relation rows: from LDS when the tile's table fits; else the first rows of the table from LDS and the rest through
-    // L2, when that is at least a quarter of the rows (every row served from LDS is one gather less through the
-    // texture path the input rows need; measured on S-stress, 1 000 relations: 624 rows of a 64-column tile in LDS
-    // 5.96 -> 5.67 ms, 312 rows of a 128-column tile 11.9 -> 11.1 ms, 156 rows of a 256-column tile 23.8 -> 24.1 ms).
-    int rel = rel_fits ? kRelLds : kRelL2;
-    q.n_rel_lds = rel_fits ? q.n_rel : 0;
-    size_t lds = kLdsHeader + (rel_fits ? lds_need : 0);
-    const int part_rows = (int)((size_t)kMaxLdsBytes / ((size_t)width * sizeof(float)));
-    if (!rel_fits && q.n_rel > 0 && (long long)part_rows * 4 >= q.n_rel) {
-        rel = kRelPart;
-        q.n_rel_lds = part_rows;
-        lds = kLdsHeader + (size_t)part_rows * width * sizeof(float);
-    }
-    if (group == 64) return launch_rowgroup_g<64>(q, backward, sum_op, mul_op, unit_w, rel, grid, lds, stream);
-    if (group == 32) return launch_rowgroup_g<32>(q, backward, sum_op, mul_op, unit_w, rel, grid, lds, stream);
-    return launch_rowgroup_g<16>(q, backward, sum_op, mul_op, unit_w, rel, grid, lds, stream);
-}
-
-bool g_no_rowgroup = false;
-bool g_no_concurrent_tiles = false;
-bool g_no_dense = false;
-
-
-// Runs one plan: segment_kernel over the chunk schedule, then fixup_kernel over the split rows.
-template <int KIND>
-int run_plan(const ultra_segments *seg, KParams p, int64_t gather_rows, int64_t gather2_rows, int64_t n_rel, int64_t F,
-             int sum_op, int mul_op, bool wants_rel_lds, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-    int rc = check_segments(seg);
-    if (rc) return rc;
-    if (F <= 0 || n_rel < 0 || n_rel > 0x7fffffffLL) return ULTRA_ERR_BAD_SHAPE;
-    if (sum_op < 0 || sum_op > 2 || mul_op < 0 || mul_op > 1) return ULTRA_ERR_BAD_OP;
-    const size_t need = ultra_rspmm_workspace_bytes(seg, F);
-    if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return ULTRA_ERR_WORKSPACE;
-    if (seg->n_rows == 0) return ULTRA_OK;
-
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    DeviceInfo *di = nullptr;
-    rc = device_info(dev, &di);
-    if (rc) return rc;
-
-    const int n_tiles = (int)((F + kTile - 1) / kTile);
-    const int split = kXcd / gcd_int(n_tiles, kXcd);
-    const size_t lds_need = (size_t)n_rel * kTile * sizeof(float);
-    const bool rel_lds = wants_rel_lds && n_rel > 0 && lds_need <= (size_t)kMaxLdsBytes;
-    const int blocks_per_label = (di->n_cu + kXcd - 1) / kXcd;
-
-    p.row = seg->row;
-    p.node_a = seg->node_a;
-    p.node_b = seg->node_b;
-    p.rel = seg->rel;
-    p.weight = seg->weight;
-    p.chunks = reinterpret_cast<const int4 *>(seg->chunks);
-    p.partial = static_cast<float *>(workspace);
-    p.F = F;
-    p.n_chunks = (int)seg->n_chunks;
-    p.n_rel = (int)n_rel;
-    p.n_tiles = n_tiles;
-    p.split = split;
-    p.n_slots = n_tiles * split;
-    p.blocks_per_label = blocks_per_label;
-
-    const int grid = blocks_per_label * kXcd;
-    hipEvent_t ev_start = g_prof_start, ev_stop = g_prof_stop;
-    g_prof_start = g_prof_stop = nullptr;
-    // (not while the stream is being captured: the ROCm 7.0 runtime bundled with PyTorch rejects external
-    // event-record nodes, so the hook is simply ignored inside a hipGraph capture)
-    if (ev_start != nullptr || ev_stop != nullptr) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing(stream, &cs));
-        if (cs != hipStreamCaptureStatusNone) ev_start = ev_stop = nullptr;
-    }
-    auto stamp = [&](hipEvent_t ev) -> hipError_t { return hipEventRecord(ev, stream); };
-    if (ev_start != nullptr) HIP_TRY(stamp(ev_start));
-    // dense relation graphs: the sum as a product with the plan's 0/1 matrix on the exact-f32 matrix cores -- the reference
-    // order for every row, no pieces, no fix-up pass (relgraph_dense.hip)
-    // (only on the architecture the instruction's summation order was probed on -- tools/ubench/mfma_order.hip, MI355X: a build
-    // with ARCH=gfx942 walks the edge list -- and for finite operands only: fmaf(0, y, acc) == acc needs a finite y, so ONE
-    // non-finite activation turns every row of a dense launch into NaN where the edge walk and the reference touch that node's
-    // neighbours only; the eager callers test their relation tables as the frontier path does)
-    if (seg->dense != nullptr && !g_no_dense && !g_force_general && !g_no_quad && !g_no_x_lds &&
-        std::strncmp(di->arch, "gfx950", 6) == 0) {
-        ultra_detail::DenseCall call{seg, KIND, sum_op, mul_op, p.relation, p.input, p.grad, p.add_rows, p.bnode, p.bvec, p.bdim,
-                                     p.out, workspace, workspace_bytes, gather_rows, gather2_rows, n_rel, F};
-        if (ultra_detail::dense_applies(call)) {
-            rc = ultra_detail::dense_launch(call, stream);
-            if (rc) return rc;
-            if (ev_stop != nullptr) HIP_TRY(stamp(ev_stop));
-            return ULTRA_OK;
-        }
-    }
-    // big graphs of short rows (node ids outside the packed word, no split rows, row pointers present): one row per
-    // 16-lane group (rowgroup.inc); same sequential order per row as every other kernel, so the same bits
-    bool use_rowgroup = false;
-    if constexpr (KIND != KIND_DREL) {
-        auto aligned16 = [](const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; };
-        const float *gather = (KIND == KIND_DX) ? p.grad : p.input;
-        use_rowgroup = !g_force_general && !g_no_rowgroup && seg->row_ptr != nullptr && seg->packed_src_shift >= 32 &&
-                       seg->n_long_rows == 0 && (F % 4) == 0 && (KIND == KIND_FWD || sum_op == ULTRA_SUM_ADD) &&
-                       aligned16(gather) && aligned16(p.out) && aligned16(p.relation) && aligned16(p.add_rows) &&
-                       aligned16(p.bvec) && (p.bnode == nullptr || p.bdim % 4 == 0);
-        if (use_rowgroup) {
-            RowGroupParams q{};
-            q.row_ptr = seg->row_ptr;
-            q.col = seg->node_a;
-            q.rel = seg->rel;
-            q.weight = seg->weight;
-            q.relation = p.relation;
-            q.gather = gather;
-            q.add_rows = p.add_rows;
-            q.bnode = p.bnode;
-            q.bvec = p.bvec;
-            q.bdim = p.bdim;
-            q.out = p.out;
-            q.F = F;
-            q.n_rows = (int)seg->n_rows;
-            q.n_rel = (int)n_rel;
-            rc = launch_rowgroup(q, KIND == KIND_DX, sum_op, mul_op, seg->weight == nullptr, gather_rows, di->n_cu, stream);
-            if (rc) return rc;
-        }
-    }
-    // packed fast path: forward and sum-backward d_input, when the plan carries packed words, the relation
-    // tile fits LDS and the gathered matrix is addressable with a 32-bit byte offset
-    bool use_packed = false;
-    if (!use_rowgroup) {
-        // forward gathers `input`; d_input gathers `output_grad`; d_relation gathers both (grad by node_b, input by node_a)
-        const float *gather = (KIND == KIND_DX) ? p.grad : p.input;
-        const unsigned long long gather_bytes = (unsigned long long)gather_rows * (unsigned long long)F * 4ull;
-        const unsigned long long gather2_bytes = (unsigned long long)gather2_rows * (unsigned long long)F * 4ull;
-        const bool big = seg->packed_src_shift >= 32;          // node ids live in node_a, not in the packed word
-        const bool rel_fits = lds_need <= (size_t)kMaxLdsBytes && n_rel > 0;
-        const unsigned long long relation_bytes = (unsigned long long)n_rel * (unsigned long long)F * 4ull;
-        const bool lds_ok = (KIND == KIND_DREL) || rel_fits || (big && relation_bytes < 0xffff0000ull && n_rel > 0);
-        use_packed = !g_force_general && seg->packed != nullptr && (KIND == KIND_FWD || sum_op == ULTRA_SUM_ADD) &&
-                     lds_ok && gather_bytes < 0xffff0000ull && gather2_bytes < 0xffff0000ull &&
-                     (unsigned long long)F * 4ull < 0x7fffffffull && (KIND != KIND_DREL || (seg->node_b != nullptr && !big));
-        if (use_packed) {
-            PParams q{};
-            q.meta = seg->packed;
-            q.meta2 = reinterpret_cast<const uint32_t *>(big ? seg->node_a : seg->node_b);
-            q.weight = seg->weight;
-            q.chunks = p.chunks;
-            q.relation = p.relation;
-            q.gather = gather;
-            q.gather2 = p.grad;
-            q.add_rows = p.add_rows;
-            q.bnode = p.bnode;
-            q.bvec = p.bvec;
-            q.bdim = p.bdim;
-            q.out = p.out;
-            q.partial = p.partial;
-            q.F = F;
-            q.gather_bytes = (uint32_t)gather_bytes;
-            q.gather2_bytes = (uint32_t)gather2_bytes;
-            q.relation_bytes = (uint32_t)(relation_bytes < 0xffff0000ull ? relation_bytes : 0);
-            q.row_bytes = (uint32_t)(F * 4);
-            q.src_shift = (uint32_t)seg->packed_src_shift;
-            q.rel_mask = big ? 0xffffff00u : ((1u << (seg->packed_src_shift - 8)) - 1u) << 8;
-            q.n_chunks = p.n_chunks;
-            q.n_rel = p.n_rel;
-            q.n_tiles = n_tiles;
-            q.split = split;
-            q.n_slots = p.n_slots;
-            q.blocks_per_label = blocks_per_label;
-            const bool needs_rel = (KIND == KIND_FWD) || (KIND == KIND_DX && mul_op == ULTRA_MUL_MUL);
-            // small gathered matrix (relation graphs: 2R nodes): stage its tile in LDS next to the relation tile
-            const size_t lds_x_bytes = (size_t)gather_rows * kTile * sizeof(float);
-            int var = 0;
-            size_t lds_bytes = needs_rel ? lds_need : 0;
-            if (big) {
-                var = (needs_rel && !rel_fits) ? 2 : 3;
-                if (var == 2) lds_bytes = 0;
-            } else if (seg->n_hot > 0) {
-                // the plan's words address a hot-row cache: its rows must fit next to the relation tile
-                const size_t hot_bytes = (size_t)seg->n_hot * kTile * sizeof(float);
-                if (lds_bytes + hot_bytes > (size_t)kMaxLdsBytes) return ULTRA_ERR_BAD_SHAPE;
-                var = 4;
-                lds_bytes += hot_bytes;
-                q.hot_nodes = seg->hot_nodes;
-                q.n_hot = (int)seg->n_hot;
-            } else if ((KIND != KIND_DREL || mul_op == ULTRA_MUL_MUL) && !g_no_x_lds && gather_rows > 0 &&
-                       lds_bytes + lds_x_bytes <= (size_t)kMaxLdsBytes) {
-                var = 1;       // d_relation: the `input` rows (picked by source node) from LDS, output_grad stays a gather
-                lds_bytes += lds_x_bytes;
-            }
-            q.n_gather_rows = (int)gather_rows;
-            // four chunks per wave, four columns per lane (quad.inc): needs 16-byte rows and pointers
-            auto aligned16 = [](const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; };
-            const unsigned long long meta_bytes = ((unsigned long long)seg->n_edges + 16ull) * 4ull;   // PACK_SLACK words follow
-            q.meta_bytes = (uint32_t)(meta_bytes < 0xffff0000ull ? meta_bytes : 0);
-            q.meta2_bytes = (uint32_t)((unsigned long long)seg->n_edges * 4ull);
-            const unsigned long long out_bytes = (unsigned long long)seg->n_rows * (unsigned long long)F * 4ull;
-            q.out_bytes = (uint32_t)(out_bytes < 0xffff0000ull ? out_bytes : 0);
-            const bool quad = !g_no_quad && (var == 0 || var == 1) && (F % 4) == 0 && q.out_bytes != 0 &&
-                              q.meta_bytes != 0 && (unsigned long long)F * 4ull < (1ull << 24) &&
-                              (KIND != KIND_DREL || gather2_rows < (1ll << 24)) && aligned16(gather) && aligned16(p.grad) &&
-                              aligned16(p.out) && aligned16(p.add_rows) && aligned16(p.partial) && aligned16(p.bvec) &&
-                              (p.bnode == nullptr || p.bdim % 4 == 0);
-            if (quad) {
-                // tiles of one label side by side (quad.inc): as many as the label has, while every team keeps >= 4
-                // workgroups.  Measured on every shape tried (rocprofv3, F = 1 024 / 2 048): S-codexs 28.8 -> 19.7 us,
-                // S-wn18rr 64.5 -> 60.6 / 172 -> 154 us, S-codexm 84.4 -> 80.8 us, S-fb15k237 246 -> 219 us -- also where
-                // the tiles' slices of the gathered matrix together exceed the XCD's 4 MB L2 (S-fb15k237: 4 x 3.7 MB): what
-                // the sequential walk gains in L2 hits it loses in per-tile start-up and tails; the Infinity Cache backs
-                // the gathers either way.
-                const int slots_per_label = (q.n_slots + kXcd - 1) / kXcd;
-                int conc = 1;
-                while (!g_no_concurrent_tiles && conc * 2 <= slots_per_label && blocks_per_label % (conc * 2) == 0 &&
-                       blocks_per_label / (conc * 2) >= 4)
-                    conc *= 2;
-                if (const char *force = getenv("ULTRA_CONC")) {      // experiments: force the number of concurrent tiles
-                    const int want = atoi(force);                    // (ULTRA_CONC_MIN_ROWS: only for gathered matrices of at
-                    const char *min_rows = getenv("ULTRA_CONC_MIN_ROWS");    // least that many rows, i.e. not the relation graphs)
-                    if (want >= 1 && blocks_per_label % want == 0 && (min_rows == nullptr || gather_rows >= atoll(min_rows)))
-                        conc = want;
-                }
-                q.concurrent = conc;
-                // activity masks of the backward (quad.inc ACT): only where the gathered matrix is not staged in LDS, the
-                // bitmap fits behind the tables and a column tile is a query block
-                size_t act_bytes = 0;
-                if (KIND == KIND_DREL && var == 0 && F % kTile == 0) {
-                    if (p.act_bits != nullptr && p.act_words > 0 && lds_bytes + (size_t)p.act_words * 4 <= (size_t)kMaxLdsBytes) {
-                        q.act_bits = p.act_bits;
-                        q.act_words = p.act_words;
-                        act_bytes = (size_t)p.act_words * 4;
-                    } else if (KIND == KIND_DREL && p.act_node != nullptr && mul_op == ULTRA_MUL_MUL) {
-                        q.act_node = p.act_node;      // (mul = add: d_relation does not depend on the input rows)
-                    }
-                }
-                // removed edges marked in a copy of the words (ultra_segments.packed_dead): the unit-weight kernel on those words
-                const bool dead = seg->packed_dead != nullptr && !g_no_dead_words && var == 0 && q.act_node == nullptr &&
-                                  sum_op == ULTRA_SUM_ADD && mul_op == ULTRA_MUL_MUL;
-                if (dead) { q.meta = seg->packed_dead; q.weight = nullptr; }
-                rc = launch_quad<KIND>(q, sum_op, mul_op, dead || seg->weight == nullptr, var == 1, grid,
-                                       kLdsHeader + lds_bytes + act_bytes, stream, dead);
-            }
-            if (!quad) rc = launch_packed<KIND>(q, sum_op, mul_op, seg->weight == nullptr, var, grid, kLdsHeader + lds_bytes, stream);
-            if (rc) return rc;
-        }
-    }
-    if (!use_packed && !use_rowgroup) {
-        rc = launch_ops<KIND>(p, sum_op, mul_op, seg->weight == nullptr, rel_lds, grid,
-                              kLdsHeader + (rel_lds ? lds_need : 0), stream);
-        if (rc) return rc;
-    }
-    if (ev_stop != nullptr) HIP_TRY(stamp(ev_stop));
-
-    if (seg->n_long_rows > 0) {
-        FixParams fp;
-        fp.long_rows = seg->long_rows;
-        fp.partial = p.partial;
-        fp.add_rows = p.add_rows;
-        fp.bnode = p.bnode;
-        fp.bvec = p.bvec;
-        fp.bdim = p.bdim;
-        fp.out = p.out;
-        fp.F = F;
-        fp.n_long = (int)seg->n_long_rows;
-        fp.n_tiles = n_tiles;
-        const long long waves = (long long)fp.n_long * n_tiles;
-        const int fgrid = (int)((waves + 3) / 4);
-        const int red = (KIND == KIND_FWD) ? sum_op : ULTRA_SUM_ADD;
-        const bool many_pieces = seg->n_pieces >= 128 * seg->n_long_rows;       // on average >= 128 pieces per split row
-        if (red == ULTRA_SUM_ADD && many_pieces)
-            hipLaunchKernelGGL((fixup_kernel<ULTRA_SUM_ADD, 64>), dim3(fgrid), dim3(256), 0, stream, fp);
-        else if (red == ULTRA_SUM_ADD) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_ADD>, dim3(fgrid), dim3(256), 0, stream, fp);
-        else if (red == ULTRA_SUM_MIN) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MIN>, dim3(fgrid), dim3(256), 0, stream, fp);
-        else hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MAX>, dim3(fgrid), dim3(256), 0, stream, fp);
-        HIP_TRY(hipGetLastError());
-    }
-    return ULTRA_OK;
-}
-
-#include "rotate.inc"
-
-}  // namespace
-
-namespace ultra_detail {
-int persistent_cus(int *n_cu) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    DeviceInfo *di = nullptr;
-    const int rc = device_info(dev, &di);
-    if (rc) return rc;
-    *n_cu = di->n_cu;
-    return ULTRA_OK;
-}
-bool wide_groups_forced() { return g_wide_groups; }
 }  // namespace ultra_detail
 
 extern "C" {
@@ -1608,14 +1371,7 @@ int ultra_rspmm_device_info(int device, int *n_cu, int *lds_bytes, char *arch_ho
 }
 
 int ultra_rspmm_force_general_path(int on) {
-    g_force_general = (on & 1) != 0;      // bit 0: general kernel instead of the packed one
-    g_no_x_lds = (on & 2) != 0;           // bit 1: packed kernel without staging the gathered matrix in LDS
-    g_no_quad = (on & 4) != 0;            // bit 2: one chunk per wave (packed_kernel) instead of four (quad_kernel)
-    g_no_rowgroup = (on & 8) != 0;        // bit 3: chunked kernels where one row per group (rowgroup_kernel) would run
-    g_wide_groups = (on & 16) != 0;       // bit 4: rowgroup_kernel with 32 / 64 lanes per row even for cache-sized inputs
-    g_no_concurrent_tiles = (on & 32) != 0;   // bit 5: quad_kernel walks a label's column tiles one after the other
-    g_no_dead_words = (on & 128) != 0;    // bit 7: the weighted kernels even where a plan carries marked words (packed_dead)
-    g_no_dense = (on & 64) != 0;          // bit 6: the edge list of a plan that carries a dense form (relgraph_dense.hip)
+    g_knobs = decode_knobs(on);
     return ULTRA_OK;
 }
 
@@ -1665,7 +1421,7 @@ int ultra_rspmm_forward_f32(const ultra_segments *fwd, const float *relation, co
     p.input = input;
     p.add_rows = add_rows;
     p.out = out;
-    return run_plan<KIND_FWD>(fwd, p, n_src, 0, n_rel, F, sum_op, mul_op, true, workspace, workspace_bytes,
+    return run_plan<KIND_FWD>(fwd, p, n_src, 0, n_rel, F, sum_op, mul_op, workspace, workspace_bytes,
                               static_cast<hipStream_t>(stream));
 }
 
@@ -1679,10 +1435,9 @@ int ultra_rspmm_fwd_f32(const int32_t *row_ptr, const int32_t *src, const int32_
     if (E > 0 && (src == nullptr || rel == nullptr || relation == nullptr || x == nullptr)) return ULTRA_ERR_NULL_POINTER;
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(relation)) & 15u)
         return ULTRA_ERR_BAD_SHAPE;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
+    if (F >= (1LL << 30)) return ULTRA_ERR_BAD_SHAPE;         // row bytes are a 32-bit factor of the address arithmetic
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     RowGroupParams q{};
     q.row_ptr = row_ptr;
@@ -1696,7 +1451,13 @@ int ultra_rspmm_fwd_f32(const int32_t *row_ptr, const int32_t *src, const int32_
     q.n_rows = (int)N;
     q.n_rel = (int)R;
     // (the rows of x are not part of this signature; N stands in for them in the cache-residency heuristic)
-    return launch_rowgroup(q, false, sum_op, mul_op, w == nullptr, N, di->n_cu, static_cast<hipStream_t>(stream));
+    PlanPath path;
+    path.unit_w = w == nullptr;
+    set_rowgroup(path, rowgroup_tiling(F, N, N, R, di->n_cu, g_knobs.wide_groups, kLdsHeader, kMaxLdsBytes));
+    fill_tiling(q, path);
+    return with_sum_mul(sum_op, mul_op, [&](auto sum, auto mul) {
+        return launch_rowgroup<decltype(sum)::value, decltype(mul)::value, false>(q, path, static_cast<hipStream_t>(stream));
+    });
 }
 
 int ultra_rspmm_forward_boundary_f32(const ultra_segments *fwd, const float *relation, const float *input,
@@ -1716,7 +1477,7 @@ int ultra_rspmm_forward_boundary_f32(const ultra_segments *fwd, const float *rel
     p.bvec = boundary_value;
     p.bdim = (int)block;
     p.out = out;
-    return run_plan<KIND_FWD>(fwd, p, n_src, 0, n_rel, F, sum_op, mul_op, true, workspace, workspace_bytes,
+    return run_plan<KIND_FWD>(fwd, p, n_src, 0, n_rel, F, sum_op, mul_op, workspace, workspace_bytes,
                               static_cast<hipStream_t>(stream));
 }
 
@@ -1773,7 +1534,7 @@ int ultra_rspmm_frontier_f32(const ultra_segments *by_src, const int32_t *src_pt
     for (int sh = 0; sh < 31; ++sh)
         if ((1LL << sh) == by_src->piece_len) p.piece_shift = sh;
     const size_t msg_bytes = (size_t)n_rel * kTile * sizeof(float);
-    if (!g_force_general && n_rel > 0 && msg_bytes <= (size_t)kMaxLdsBytes) {
+    if (!g_knobs.force_general && n_rel > 0 && msg_bytes <= (size_t)kMaxLdsBytes) {
         // the query's R messages in LDS, ids 16 at a time (frontier_lds_kernel): one workgroup of 64 groups per slice
         p.slices = kFrontierLdsSlices;
         const int grid = (int)(F / 64) * p.slices;
@@ -1826,10 +1587,8 @@ static int first_layer_sparse_impl(const ultra_segments *by_src, const int32_t *
          reinterpret_cast<uintptr_t>(boundary_value)) & 15u)
         return ULTRA_ERR_BAD_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    rc = device_info(dev, &di);
+    rc = current_device_info(&di);
     if (rc) return rc;
     CombineParams cp{};
     cp.weight = weight; cp.bias = bias; cp.gamma = ln_weight; cp.beta = ln_bias;
@@ -1858,7 +1617,7 @@ static int first_layer_sparse_impl(const ultra_segments *by_src, const int32_t *
         if ((1LL << sh) == by_src->piece_len) p.piece_shift = sh;
     p.run_prefix = run_prefix; p.row_list = row_list; p.list_offset = list_offset; p.list_len = (int)row_list_len;
     const size_t msg_bytes = (size_t)n_rel * kTile * sizeof(float);
-    if (!g_force_general && msg_bytes <= (size_t)kMaxLdsBytes) {
+    if (!g_knobs.force_general && msg_bytes <= (size_t)kMaxLdsBytes) {
         p.slices = kFrontierLdsSlices;
         const int fgrid = (int)n_query * p.slices;
         rc = by_src->weight == nullptr ? launch_with_lds(frontier_lds_kernel<true>, p, fgrid, msg_bytes, s, kFrontierLdsThreads)
@@ -1936,6 +1695,40 @@ int ultra_rspmm_backward_boundary_rows_f32(const ultra_segments *by_src, const i
     return ULTRA_OK;
 }
 
+// d_input over the by_src plan and d_relation over the by_rel plan, each where its output is asked for; the activity
+// arguments are ultra_rspmm_backward_active_f32's (NULL: none)
+static int backward_plans(const ultra_segments *by_src, const ultra_segments *by_rel, const float *relation, const float *input,
+                          const float *output, const float *output_grad, const float *d_input_add, float *d_input,
+                          float *d_relation, void *workspace, size_t workspace_bytes, int64_t n_src, int64_t n_dst,
+                          int64_t n_rel, int64_t F, int sum_op, int mul_op, const uint32_t *dst_active_bits,
+                          int64_t active_words, const int32_t *src_active_node, hipStream_t s) {
+    KParams p{};
+    p.relation = relation;
+    p.input = input;
+    p.output = output;
+    p.grad = output_grad;
+    p.act_bits = dst_active_bits;
+    p.act_words = (int)active_words;
+    if (d_input != nullptr) {
+        if (by_src == nullptr) return ULTRA_ERR_NULL_POINTER;
+        p.out = d_input;
+        p.add_rows = d_input_add;
+        int rc = run_plan<KIND_DX>(by_src, p, n_dst, 0, n_rel, F, sum_op, mul_op, workspace, workspace_bytes, s);
+        if (rc) return rc;
+    }
+    if (d_relation != nullptr) {
+        if (by_rel == nullptr) return ULTRA_ERR_NULL_POINTER;
+        if (!segments_abi_ok(by_rel)) return ULTRA_ERR_ABI;
+        if (by_rel->n_edges > 0 && by_rel->node_b == nullptr) return ULTRA_ERR_NULL_POINTER;
+        p.out = d_relation;
+        p.add_rows = nullptr;
+        p.act_node = src_active_node;
+        int rc = run_plan<KIND_DREL>(by_rel, p, n_src, n_dst, n_rel, F, sum_op, mul_op, workspace, workspace_bytes, s);
+        if (rc) return rc;
+    }
+    return ULTRA_OK;
+}
+
 int ultra_rspmm_backward_f32(const ultra_segments *by_src, const ultra_segments *by_rel, const float *relation,
                              const float *input, const float *output, const float *output_grad, float *d_input,
                              float *d_relation, void *workspace, size_t workspace_bytes, int64_t n_src, int64_t n_dst,
@@ -1953,34 +1746,8 @@ int ultra_rspmm_backward_accumulate_f32(const ultra_segments *by_src, const ultr
     if (output_grad == nullptr || relation == nullptr || input == nullptr) return ULTRA_ERR_NULL_POINTER;
     if (d_input_add != nullptr && sum_op != ULTRA_SUM_ADD) return ULTRA_ERR_BAD_OP;       // the sum-aggregation kernels carry the epilogue
     if (sum_op != ULTRA_SUM_ADD && output == nullptr) return ULTRA_ERR_NULL_POINTER;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (d_input != nullptr) {
-        if (by_src == nullptr) return ULTRA_ERR_NULL_POINTER;
-        KParams p{};
-        p.relation = relation;
-        p.input = input;
-        p.output = output;
-        p.grad = output_grad;
-        p.out = d_input;
-        p.add_rows = d_input_add;
-        const bool needs_rel = (mul_op == ULTRA_MUL_MUL) || (sum_op != ULTRA_SUM_ADD);
-        int rc = run_plan<KIND_DX>(by_src, p, n_dst, 0, n_rel, F, sum_op, mul_op, needs_rel, workspace, workspace_bytes, s);
-        if (rc) return rc;
-    }
-    if (d_relation != nullptr) {
-        if (by_rel == nullptr) return ULTRA_ERR_NULL_POINTER;
-        if (!segments_abi_ok(by_rel)) return ULTRA_ERR_ABI;
-        if (by_rel->n_edges > 0 && by_rel->node_b == nullptr) return ULTRA_ERR_NULL_POINTER;
-        KParams p{};
-        p.relation = relation;
-        p.input = input;
-        p.output = output;
-        p.grad = output_grad;
-        p.out = d_relation;
-        int rc = run_plan<KIND_DREL>(by_rel, p, n_src, n_dst, n_rel, F, sum_op, mul_op, false, workspace, workspace_bytes, s);
-        if (rc) return rc;
-    }
-    return ULTRA_OK;
+    return backward_plans(by_src, by_rel, relation, input, output, output_grad, d_input_add, d_input, d_relation, workspace,
+                          workspace_bytes, n_src, n_dst, n_rel, F, sum_op, mul_op, nullptr, 0, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // Backward of sum-aggregation with the caller's knowledge of WHICH rows carry gradient (see include/ultra_rspmm.h).
@@ -1992,27 +1759,9 @@ int ultra_rspmm_backward_active_f32(const ultra_segments *by_src, const ultra_se
     if (output_grad == nullptr || relation == nullptr || input == nullptr) return ULTRA_ERR_NULL_POINTER;
     if (dst_active_bits != nullptr && (active_words < (n_dst + 31) / 32 || active_words > 0x7fffffffLL)) return ULTRA_ERR_BAD_SHAPE;
     if ((dst_active_bits != nullptr || src_active_node != nullptr) && F % kTile != 0) return ULTRA_ERR_BAD_SHAPE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (d_input != nullptr) {
-        if (by_src == nullptr) return ULTRA_ERR_NULL_POINTER;
-        KParams p{};
-        p.relation = relation; p.input = input; p.grad = output_grad; p.out = d_input; p.add_rows = d_input_add;
-        p.act_bits = dst_active_bits; p.act_words = (int)active_words;
-        int rc = run_plan<KIND_DX>(by_src, p, n_dst, 0, n_rel, F, ULTRA_SUM_ADD, mul_op, mul_op == ULTRA_MUL_MUL, workspace,
-                                   workspace_bytes, s);
-        if (rc) return rc;
-    }
-    if (d_relation != nullptr) {
-        if (by_rel == nullptr) return ULTRA_ERR_NULL_POINTER;
-        if (!segments_abi_ok(by_rel)) return ULTRA_ERR_ABI;
-        if (by_rel->n_edges > 0 && by_rel->node_b == nullptr) return ULTRA_ERR_NULL_POINTER;
-        KParams p{};
-        p.relation = relation; p.input = input; p.grad = output_grad; p.out = d_relation;
-        p.act_bits = dst_active_bits; p.act_words = (int)active_words; p.act_node = src_active_node;
-        int rc = run_plan<KIND_DREL>(by_rel, p, n_src, n_dst, n_rel, F, ULTRA_SUM_ADD, mul_op, false, workspace, workspace_bytes, s);
-        if (rc) return rc;
-    }
-    return ULTRA_OK;
+    return backward_plans(by_src, by_rel, relation, input, nullptr, output_grad, d_input_add, d_input, d_relation, workspace,
+                          workspace_bytes, n_src, n_dst, n_rel, F, ULTRA_SUM_ADD, mul_op, dst_active_bits, active_words,
+                          src_active_node, static_cast<hipStream_t>(stream));
 }
 
 int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd, const float *relation, const float *input,
@@ -2031,26 +1780,15 @@ int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd, const float *rela
     const bool unit = fwd->weight == nullptr;
     long long blocks = (fwd->n_edges + 3) / 4;
     if (blocks > 8192) blocks = 8192;
-#define ULTRA_WCASE(S, M)                                                                                          \
-    if (sum_op == S && mul_op == M) {                                                                              \
-        if (unit)                                                                                                  \
-            hipLaunchKernelGGL((weight_grad_kernel<S, M, true>), dim3((int)blocks), dim3(256), 0, s, fwd->row,     \
-                               fwd->node_a, fwd->rel, fwd->weight, relation, input, output, output_grad, d_weight, \
-                               (long long)F, (long long)fwd->n_edges);                                             \
-        else                                                                                                       \
-            hipLaunchKernelGGL((weight_grad_kernel<S, M, false>), dim3((int)blocks), dim3(256), 0, s, fwd->row,    \
-                               fwd->node_a, fwd->rel, fwd->weight, relation, input, output, output_grad, d_weight, \
-                               (long long)F, (long long)fwd->n_edges);                                             \
-    }
-    ULTRA_WCASE(ULTRA_SUM_ADD, ULTRA_MUL_MUL)
-    ULTRA_WCASE(ULTRA_SUM_ADD, ULTRA_MUL_ADD)
-    ULTRA_WCASE(ULTRA_SUM_MIN, ULTRA_MUL_MUL)
-    ULTRA_WCASE(ULTRA_SUM_MIN, ULTRA_MUL_ADD)
-    ULTRA_WCASE(ULTRA_SUM_MAX, ULTRA_MUL_MUL)
-    ULTRA_WCASE(ULTRA_SUM_MAX, ULTRA_MUL_ADD)
-#undef ULTRA_WCASE
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return with_sum_mul(sum_op, mul_op, [&](auto sum, auto mul) {
+        return with_bool(unit, [&](auto uw) -> int {
+            hipLaunchKernelGGL((weight_grad_kernel<decltype(sum)::value, decltype(mul)::value, decltype(uw)::value>), dim3((int)blocks),
+                               dim3(256), 0, s, fwd->row, fwd->node_a, fwd->rel, fwd->weight, relation, input, output, output_grad,
+                               d_weight, (long long)F, (long long)fwd->n_edges);
+            HIP_TRY(hipGetLastError());
+            return ULTRA_OK;
+        });
+    });
 }
 
 // rspmm with rotate messages (rotate.inc)
@@ -2121,19 +1859,15 @@ int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd, const floa
     if (sum_op != ULTRA_SUM_ADD && output == nullptr) return ULTRA_ERR_NULL_POINTER;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int half = (int)(block / 2);
-    if (sum_op == ULTRA_SUM_ADD) launch_rotate_weight_grad<ULTRA_SUM_ADD>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
-    else if (sum_op == ULTRA_SUM_MIN) launch_rotate_weight_grad<ULTRA_SUM_MIN>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
-    else launch_rotate_weight_grad<ULTRA_SUM_MAX>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return with_sum(sum_op, [&](auto sum) {
+        return launch_rotate_weight_grad<decltype(sum)::value>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
+    });
 }
 
 
 static int combine_launch(const CombineParams &p, void *stream) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     DeviceInfo *di = nullptr;
-    int rc = device_info(dev, &di);
+    int rc = current_device_info(&di);
     if (rc) return rc;
     const long long n_tiles = (p.rows + kCbRows - 1) / kCbRows;
     long long blocks = (n_tiles + kCbWaves - 1) / kCbWaves;
@@ -2141,45 +1875,18 @@ static int combine_launch(const CombineParams &p, void *stream) {
     const bool prefetch = n_tiles >= (long long)di->n_cu * kCbWaves * 4;
     const long long resident = (long long)di->n_cu * (prefetch ? 1 : 2);
     if (blocks > resident) blocks = resident;
-    const size_t lds_max = (size_t)(kCbWaves * kCbTileFloats + 128 + kCbLdsQueries * 65) * sizeof(float);
-    const size_t lds = (size_t)(kCbWaves * kCbTileFloats + 128 + (p.in_bnode != nullptr && p.rpn <= kCbLdsQueries ? p.rpn * 65 : 0)) * sizeof(float);
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<false, 0>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<true, 0>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<false, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<true, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<false, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<true, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<false, 0, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(combine_kernel<true, 0, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        attr_set[dev] = true;
-    }
-    const dim3 grid((unsigned)blocks), block(kCbWaves * 64);
+    const bool bnd_lds = p.in_bnode != nullptr && p.rpn <= kCbLdsQueries;
+    const int lds_max = (int)((kCbWaves * kCbTileFloats + 128 + kCbLdsQueries * 65) * sizeof(float));
+    const size_t lds = (size_t)(kCbWaves * kCbTileFloats + 128 + (bnd_lds ? p.rpn * 65 : 0)) * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p.in_bnode != nullptr && p.rpn <= kCbLdsQueries) {
-        if (prefetch) hipLaunchKernelGGL((combine_kernel<true, 1>), grid, block, lds, st, p);
-        else hipLaunchKernelGGL((combine_kernel<false, 1>), grid, block, lds, st, p);
-    } else if (p.in_bnode != nullptr) {
-        if (prefetch) hipLaunchKernelGGL((combine_kernel<true, 2>), grid, block, lds, st, p);
-        else hipLaunchKernelGGL((combine_kernel<false, 2>), grid, block, lds, st, p);
-    } else if (p.z_out != nullptr) {
-        if (prefetch) hipLaunchKernelGGL((combine_kernel<true, 0, true>), grid, block, lds, st, p);
-        else hipLaunchKernelGGL((combine_kernel<false, 0, true>), grid, block, lds, st, p);
-    } else {
-        if (prefetch) hipLaunchKernelGGL((combine_kernel<true, 0>), grid, block, lds, st, p);
-        else hipLaunchKernelGGL((combine_kernel<false, 0>), grid, block, lds, st, p);
-    }
-    HIP_TRY(hipGetLastError());
-    return ULTRA_OK;
+    return with_bool(prefetch, [&](auto pf) {
+        constexpr bool PF = decltype(pf)::value;
+        auto go = [&](auto kern) { return launch_with_lds(kern, p, (int)blocks, lds, st, kCbWaves * 64, lds_max); };
+        if (bnd_lds) return go(combine_kernel<PF, 1>);
+        if (p.in_bnode != nullptr) return go(combine_kernel<PF, 2>);
+        if (p.z_out != nullptr) return go(combine_kernel<PF, 0, true>);
+        return go(combine_kernel<PF, 0>);
+    });
 }
 
 int ultra_combine_forward_f32(const float *input, const float *update, const float *weight, const float *bias,
