@@ -131,6 +131,24 @@ int ultra_rspmm_event_create(void **event_host);
 int ultra_rspmm_event_destroy(void *event);
 int ultra_rspmm_event_elapsed_ms(void *start_event, void *stop_event, float *ms_host);
 
+/*
+ * Test aid: which kernel the plan runs of THIS thread launched.  Every forward / backward / rotate plan run that reaches a
+ * launch writes one record -- a row of int32 fields -- at the launcher's leaf, from the template arguments of the kernel it
+ * instantiates there (family, kind, operators, variant, where the tables live), the grid / block / LDS bytes of the launch, the
+ * tiling copied into the kernel's parameters and the fix-up pass that followed.  A field a family does not have holds -1.
+ * `seq` counts the recorded runs of the thread and never goes back, also not across a clear.  The library keeps the newest 8
+ * records per thread; a backward call runs two plans (by source, by relation) and writes two.
+ * (ultra_rspmm_fwd_f32, the raw-CSR forward, launches rowgroup_kernel through the same launcher and writes a record too.)
+ *   _clear:   forgets the records (the count returns to 0).
+ *   _records: copies the newest min(count, 8, max_rows) records, oldest first, to rows_host[.][n_fields] and returns the
+ *             count of records written since the last clear -- NOT capped at 8, so that a reader notices an overflow.
+ *             rows_host == NULL: only the count.
+ *   _fields:  the field names in row order, separated by single spaces (a binding reads them instead of assuming an order).
+ */
+int ultra_rspmm_launch_records_clear(void);
+int ultra_rspmm_launch_records(int32_t *rows_host, int max_rows);
+const char *ultra_rspmm_launch_record_fields(void);
+
 /* Test/bench knob (process-wide): bit 0 forces the general kernel where the packed fast paths apply, bit 1 keeps
  * them from staging a small gathered matrix in LDS, bit 2 selects one chunk per wave (packed_kernel) where four
  * chunks per wave (quad_kernel) would run, bit 3 the chunked kernels where one row per 16-lane group (rowgroup_kernel)

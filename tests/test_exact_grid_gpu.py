@@ -154,13 +154,20 @@ def _knob(value):
     return manager()
 
 
-def _check_operator(csr, name, sum, mul, tag="full"):
-    """Forward and both gradients through autograd against the definition."""
-    from ultra_torchdrug_amd import functional as UF
+def _check_operator(csr, name, sum, mul, tag="full", launched=None):
+    """Forward and both gradients through autograd against the definition.  ``launched``: fields of the library's launch record
+    (``_lib.launch_records``) the FORWARD must show -- the record is thread-local and autograd runs the backward on a thread of
+    its own, so only the forward is held to it here (tests/test_launch_paths_gpu.py holds the direct backward entries)."""
+    from ultra_torchdrug_amd import _lib, functional as UF
     relation, x, grad = _inputs(name, tag)[:3]
     out_w, d_x_w, d_r_w, _, _ = _definition(name, sum, mul, tag)
     rel_t, x_t = _t(relation).requires_grad_(), _t(x).requires_grad_()
+    _lib.launch_records_clear()
     out = UF.generalized_rspmm(csr, rel_t, x_t, sum=sum, mul=mul)
+    if launched is not None:
+        count, records = _lib.launch_records()
+        want = dict(launched, kind=0, sum=SUMS.index(sum), mul=MULS.index(mul), status=0)
+        assert count == 1 and {k: records[0][k] for k in want} == want, (want, records)
     out.backward(_t(grad))
     assert _same(out, out_w), "forward"
     assert _same(x_t.grad, d_x_w), "d_input"
@@ -214,10 +221,20 @@ def test_wide_id_plans_equal_the_definition(name, knob):
     csr = _csr(name, wide_ids=True)
     assert csr.fwd.packed_src_shift == 32 and csr.by_src.packed_src_shift == 32 and GRAPHS[name][3] % 4 == 0
     assert (csr.fwd.n_pieces == 0 and csr.by_src.n_pieces == 0) == (name != "many_relations")
+    # the forward's kernel (launch record; family 1 = rowgroup_kernel, 3 = packed_kernel): 16 lanes per row, 32 under bit 4 where
+    # F % 128 == 0 (weights_dups: F = 128; ragged_isolated: F = 100), the relation rows (7 / 5) in LDS; packed_kernel's wide-id
+    # forms under bit 3 (var 3: relation tile in LDS) and for many_relations whatever the knob (var 2: 700 rows do not fit)
+    unit_w = int(not GRAPHS[name][4])
+    if name == "many_relations":
+        launched = dict(family=3, var=2, unit_w=unit_w)
+    elif knob == 8:
+        launched = dict(family=3, var=3, unit_w=unit_w)
+    else:
+        launched = dict(family=1, group=32 if (knob == 16 and name == "weights_dups") else 16, rel_mode=1, unit_w=unit_w, backward=0)
     with _knob(knob):
         for s in SUMS:
             for m in MULS:
-                _check_operator(csr, name, s, m)
+                _check_operator(csr, name, s, m, launched=launched)
 
 
 @pytest.mark.parametrize("sum", SUMS)
@@ -225,7 +242,7 @@ def test_hot_row_cache_plans_equal_the_definition(sum):
     csr = _csr("hot", hot_cache=True)
     assert csr.fwd.n_hot >= 16 and csr.by_src.n_hot >= 16
     for m in MULS:
-        _check_operator(csr, "hot", sum, m)
+        _check_operator(csr, "hot", sum, m, launched=dict(family=3, var=4, unit_w=0))       # packed_kernel, hot-row cache form
 
 
 # ------------------------------------------------------------------------------------------------ dense relation-graph form

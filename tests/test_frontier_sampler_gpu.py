@@ -459,15 +459,29 @@ def test_rowgroup_kernel_and_raw_csr_entry_match_oracle(oracle, case):
     assert csr.fwd.packed_src_shift == 32 and csr.fwd.row_ptr is not None and csr.fwd.n_pieces == 0
     lib = _lib.load()
     rel_t, x_t, g_t = _t(relation), _t(x), _t(grad)
-    for s in ("add", "min", "max"):
-        for m in ("mul", "add"):
+    # what the library's launch record must show (rel_mode 0 L2 / 1 LDS / 2 first rows from LDS): a 64-column tile holds 624
+    # relation rows, a 128-column one 312, a 256-column one 156, the partial mode up to four times as many; packed_kernel's wide-id
+    # form keeps the relation tile in LDS (var 3) up to 624 relations (var 2 beyond)
+    rel_mode, chunked_var, wide_group, wide_mode = {"short_rows": (1, 3, 64, 1), "weights_many_relations": (2, 2, 32, 2),
+                                                    "relations_beyond_lds": (2, 2, 64, 0), "ragged_with_empty_rows": (1, 3, 0, 0)}[case]
+
+    def launched(**want):
+        count, records = _lib.launch_records()
+        assert count == 1 and {k: records[0][k] for k in want} == want, (want, records)
+        _lib.launch_records_clear()
+
+    for s_id, s in enumerate(("add", "min", "max")):
+        for m_id, m in enumerate(("mul", "add")):
             want = oracle.rspmm_forward(csr_o, relation, x, s, m, piece=0)
+            _lib.launch_records_clear()                  # (the raw-CSR entry below launches rowgroup_kernel too, and records it)
             got = UF.rspmm_forward(csr, rel_t, x_t, s, m)
+            launched(family=1, group=16, rel_mode=rel_mode, backward=0, sum=s_id, mul=m_id, unit_w=int(csr.unit_weight), status=0)
             lib.ultra_rspmm_force_general_path(8)
             try:
                 chunked = UF.rspmm_forward(csr, rel_t, x_t, s, m)
             finally:
                 lib.ultra_rspmm_force_general_path(0)
+            launched(family=3, var=chunked_var, sum=s_id, mul=m_id, unit_w=int(csr.unit_weight), status=0)
             assert np.array_equal(got.cpu().numpy(), want), (s, m)
             assert torch.equal(got, chunked), (s, m)
             raw = UF.rspmm_forward_csr(csr.fwd.row_ptr, csr.fwd.node_a[:csr.n_edges], csr.fwd.rel,
@@ -478,9 +492,12 @@ def test_rowgroup_kernel_and_raw_csr_entry_match_oracle(oracle, case):
         lib.ultra_rspmm_force_general_path(16)
         try:
             for s in ("add", "max"):
+                _lib.launch_records_clear()
                 wide = UF.rspmm_forward(csr, rel_t, x_t, s, "mul")
+                launched(family=1, group=wide_group, rel_mode=wide_mode, backward=0)
                 assert np.array_equal(wide.cpu().numpy(), oracle.rspmm_forward(csr_o, relation, x, s, "mul", piece=0)), s
             d_x_w, _ = UF.rspmm_backward(csr, rel_t, x_t, None, g_t, "add", "mul", need_relation=False)
+            launched(family=1, group=wide_group, rel_mode=wide_mode, backward=1, needs_rel=1)
         finally:
             lib.ultra_rspmm_force_general_path(0)
         d_x_n, _ = UF.rspmm_backward(csr, rel_t, x_t, None, g_t, "add", "mul", need_relation=False)

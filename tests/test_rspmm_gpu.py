@@ -696,16 +696,32 @@ def test_removed_edges_as_marked_words_equal_zero_weights(mul):
     sparse_grad = (torch.randn(n, B, 64, device=dev, generator=gen) * member.t().unsqueeze(-1)).flatten(1).contiguous()
     lib = _lib.load()
 
-    def run():
+    def launched(*wants):
+        """The library's launch records of the call just made: quad_kernel (family 2) for every plan, on the marked words
+        (``dead``, unit-weight form) or with a weight per edge."""
+        count, records = _lib.launch_records()
+        assert count == len(wants) == len(records), (count, records)
+        for rec, (kind, dead, act) in zip(records, wants):
+            want = dict(family=2, kind=kind, dead=int(dead), unit_w=int(dead), act=act, x_lds=0, status=0)
+            assert {k: rec[k] for k in want} == want, (want, rec)
+        _lib.launch_records_clear()
+
+    def run(marked):
+        """``marked``: the sum / mul kernels run on the marked words (the TransE message never does)."""
+        dead = marked and mul == "mul"
+        _lib.launch_records_clear()
         out = UF.rspmm_forward(cut, relation, x, "add", mul)
+        launched((0, dead, 0))
         dx, drel = UF.rspmm_backward(cut, relation, x, None, grad, "add", mul)
+        launched((1, dead, 0), (2, dead, 0))
         dx2, drel2 = UF.rspmm_backward(cut, relation, x, None, sparse_grad, "add", mul, active_dst=bits)
+        launched((1, dead, 0), (2, dead, 2))               # d_relation under the destination bitmaps (quad.inc ACT = 2)
         return out, dx, drel, dx2, drel2
 
-    got = run()
+    got = run(True)
     lib.ultra_rspmm_force_general_path(128)              # bit 7: the weighted kernels
     try:
-        want = run()
+        want = run(False)
     finally:
         lib.ultra_rspmm_force_general_path(0)
     for a, b in zip(got, want):

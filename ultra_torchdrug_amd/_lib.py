@@ -70,6 +70,9 @@ SIGNATURES = {
     "ultra_rspmm_event_create": (i32, [ctypes.POINTER(vp)]),
     "ultra_rspmm_event_destroy": (i32, [vp]),
     "ultra_rspmm_event_elapsed_ms": (i32, [vp, vp, ctypes.POINTER(f32)]),
+    "ultra_rspmm_launch_records_clear": (i32, []),
+    "ultra_rspmm_launch_records": (i32, [vp, i32]),
+    "ultra_rspmm_launch_record_fields": (ctypes.c_char_p, []),
     "ultra_rspmm_force_general_path": (i32, [i32]),
     "ultra_rspmm_reserve_cus": (i32, [i32]),
     "ultra_rspmm_workspace_bytes": (sz, [seg, i64]),
@@ -210,6 +213,22 @@ def launch(device, name, *args):
     with torch.cuda.device(device):
         check(entry(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
                     torch.cuda.current_stream().cuda_stream))
+
+
+def launch_records_clear():
+    """Forget this thread's launch records (``ultra_rspmm_launch_records_clear``)."""
+    check(load().ultra_rspmm_launch_records_clear())
+
+
+def launch_records():
+    """``(count, records)``: how many plan runs of THIS thread reached a launch since the last clear, and the newest (at most
+    8) of them, oldest first, as dicts keyed by the library's own field names (``ultra_rspmm_launch_record_fields``)."""
+    lib = load()
+    names = lib.ultra_rspmm_launch_record_fields().decode().split()
+    rows = (ctypes.c_int32 * (8 * len(names)))()
+    count = int(lib.ultra_rspmm_launch_records(ctypes.cast(rows, vp), 8))
+    kept = min(count, 8)
+    return count, [dict(zip(names, rows[i * len(names):(i + 1) * len(names)])) for i in range(kept)]
 
 
 def device_info(device=0):

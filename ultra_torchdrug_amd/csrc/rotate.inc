@@ -258,7 +258,11 @@ int launch_rotate_w(const RotParams &p, bool unit_w, bool rel_lds, int grid, siz
         return with_bool(rel_lds, [&](auto rl) {
             constexpr bool UW = decltype(uw)::value, RL = decltype(rl)::value;
             if constexpr (RL && KIND == KIND_DREL) return (int)ULTRA_ERR_BAD_OP;      // rows are relations: no LDS table
-            else return launch_with_lds(rotate_segment_kernel<KIND, SUM, UW, RL>, p, grid, lds, stream, kBlock);
+            else {
+                LaunchRecord rec;
+                rec.family = kFamRotate; rec.kind = KIND; rec.sum = SUM; rec.unit_w = UW; rec.rel_lds = RL;
+                return launch_recorded(rec, rotate_segment_kernel<KIND, SUM, UW, RL>, p, grid, lds, stream, kBlock);
+            }
         });
     });
 }

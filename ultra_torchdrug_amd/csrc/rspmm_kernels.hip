@@ -29,6 +29,7 @@
 #include <mutex>
 
 #include "host_common.h"
+#include "launch_record.h"
 
 // hipError_t of the last failing HIP call on this thread (host_common.h; hidden: -fvisibility=hidden, the library exports
 // exactly what include/ultra_rspmm.h declares)
@@ -968,6 +969,19 @@ constexpr int kQuadUW = ULTRA_QUAD_UW;   // ... with per-edge weights: 8 would s
 #endif
 constexpr int kQuadUX = ULTRA_QUAD_UX;   // ... with the gathered matrix in LDS
 
+// What the plan runs of this thread launched (launch_record.h; ultra_rspmm_launch_records).  Host side only.
+thread_local LaunchRing g_launches;
+
+// A launcher's leaf: `rec` names the template arguments of `kern` as the leaf instantiates it; the launch geometry is what
+// goes to launch_with_lds and the tiling what the kernel's parameters hold.
+template <typename Kern, typename Params>
+int launch_recorded(LaunchRecord rec, Kern kern, const Params &p, int grid, size_t lds, hipStream_t stream, int block) {
+    rec.grid = grid; rec.block = block; rec.lds = (int32_t)lds;
+    rec.n_tiles = p.n_tiles; rec.split = p.split; rec.n_slots = p.n_slots; rec.blocks_per_label = p.blocks_per_label;
+    LaunchRecord &slot = g_launches.push(rec);
+    return slot.status = launch_with_lds(kern, p, grid, lds, stream, block);
+}
+
 // The launchers below take the variant from plan_path()'s decision and instantiate exactly the kernels a call can reach.
 
 template <int KIND, int SUM, int MUL>
@@ -978,8 +992,11 @@ int launch_general(const KParams &p, const PlanPath &path, hipStream_t stream) {
             // no LDS table where no per-edge relation operand is read: d_relation (rows are relations), d_input of add / add
             if constexpr (RL && (KIND == KIND_DREL || (KIND == KIND_DX && SUM == ULTRA_SUM_ADD && MUL == ULTRA_MUL_ADD)))
                 return (int)ULTRA_ERR_BAD_OP;
-            else
-                return launch_with_lds(segment_kernel<KIND, SUM, MUL, UW, RL>, p, path.grid, path.lds, stream, kBlock);
+            else {
+                LaunchRecord rec;
+                rec.family = FAM_GENERAL; rec.kind = KIND; rec.sum = SUM; rec.mul = MUL; rec.unit_w = UW; rec.rel_lds = RL;
+                return launch_recorded(rec, segment_kernel<KIND, SUM, MUL, UW, RL>, p, path.grid, path.lds, stream, kBlock);
+            }
         });
     });
 }
@@ -990,7 +1007,14 @@ int launch_packed(const PParams &p, const PlanPath &path, hipStream_t stream) {
         auto go = [&](auto var) {
             constexpr int V = decltype(var)::value;
             constexpr int UN = (V == 2 || V == 3) ? kUnrollBig : kUnroll;
-            return launch_with_lds(packed_kernel<KIND, SUM, MUL, decltype(uw)::value, V, UN>, p, path.grid, path.lds, stream, kBlock);
+            constexpr bool UW = decltype(uw)::value;
+            // d_input of add / add reads no relation operand: a wide-id plan never takes the form without the LDS tile
+            if constexpr (KIND == KIND_DX && MUL == ULTRA_MUL_ADD && V == 2) return (int)ULTRA_ERR_BAD_OP;
+            else {
+                LaunchRecord rec;
+                rec.family = FAM_PACKED; rec.kind = KIND; rec.sum = SUM; rec.mul = MUL; rec.unit_w = UW; rec.var = V; rec.unroll = UN;
+                return launch_recorded(rec, packed_kernel<KIND, SUM, MUL, UW, V, UN>, p, path.grid, path.lds, stream, kBlock);
+            }
         };
         if constexpr (KIND == KIND_DREL) return go(std::integral_constant<int, 0>{});      // the plain form only
         else return with_int<0, 1, 2, 3, 4>(path.var, go);
@@ -999,8 +1023,13 @@ int launch_packed(const PParams &p, const PlanPath &path, hipStream_t stream) {
 
 template <int KIND, int SUM, int MUL>
 int launch_quad(const PParams &p, const PlanPath &path, hipStream_t stream) {
-#define ULTRA_Q(UW, XL, U, ACT, DEAD) \
-    return launch_with_lds(quad_kernel<KIND, SUM, MUL, UW, XL, U, ACT, DEAD>, p, path.grid, path.lds, stream, kBlock)
+#define ULTRA_Q(UW, XL, U, ACT, DEAD)                                                                                          \
+    do {                                                                                                                       \
+        LaunchRecord rec;                                                                                                      \
+        rec.family = FAM_QUAD; rec.kind = KIND; rec.sum = SUM; rec.mul = MUL; rec.unit_w = UW; rec.x_lds = XL; rec.unroll = U; \
+        rec.act = ACT; rec.dead = DEAD; rec.concurrent = p.concurrent;                                                         \
+        return launch_recorded(rec, quad_kernel<KIND, SUM, MUL, UW, XL, U, ACT, DEAD>, p, path.grid, path.lds, stream, kBlock); \
+    } while (0)
     if constexpr (SUM == ULTRA_SUM_ADD && MUL == ULTRA_MUL_MUL) {       // the plan's marked word copy (quad.inc DEAD)
         if (path.dead) {
             if constexpr (KIND == KIND_DREL) {
@@ -1042,9 +1071,15 @@ int launch_rowgroup(const RowGroupParams &p, const PlanPath &path, hipStream_t s
             return with_int<kRelL2, kRelLds, kRelPart>(path.rel_mode, [&](auto rel) {
                 constexpr int REL = decltype(rel)::value;
                 if constexpr (!NEEDS_REL && REL != kRelL2) return (int)ULTRA_ERR_BAD_OP;
-                else
-                    return launch_with_lds(rowgroup_kernel<SUM, MUL, decltype(uw)::value, REL, NEEDS_REL, BACKWARD, decltype(g)::value>,
-                                           p, path.grid, path.lds, stream, kRgBlock);
+                else {
+                    constexpr bool UW = decltype(uw)::value;
+                    constexpr int G = decltype(g)::value;
+                    LaunchRecord rec;
+                    rec.family = FAM_ROWGROUP; rec.kind = BACKWARD ? KIND_DX : KIND_FWD; rec.sum = SUM; rec.mul = MUL; rec.unit_w = UW;
+                    rec.rel_mode = REL; rec.group = G; rec.needs_rel = NEEDS_REL; rec.backward = BACKWARD; rec.n_rel_lds = p.n_rel_lds;
+                    return launch_recorded(rec, rowgroup_kernel<SUM, MUL, UW, REL, NEEDS_REL, BACKWARD, G>, p, path.grid, path.lds, stream,
+                                           kRgBlock);
+                }
             });
         });
     });
@@ -1128,10 +1163,23 @@ int launch_words(const ultra_segments *seg, const KParams &p, const PlanPath &pa
 
 // fixup_kernel over the split rows: pieces added in piece order
 int launch_fixup(const FixParams &fp, int red, bool many_pieces, int grid, hipStream_t stream) {
-    if (red == ULTRA_SUM_ADD && many_pieces) hipLaunchKernelGGL((fixup_kernel<ULTRA_SUM_ADD, 64>), dim3(grid), dim3(256), 0, stream, fp);
-    else if (red == ULTRA_SUM_ADD) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_ADD>, dim3(grid), dim3(256), 0, stream, fp);
-    else if (red == ULTRA_SUM_MIN) hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MIN>, dim3(grid), dim3(256), 0, stream, fp);
-    else hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MAX>, dim3(grid), dim3(256), 0, stream, fp);
+    // (the record of the plan run this pass belongs to: its main kernel was launched just before, on this thread)
+    auto note = [&](int form, int sum) {
+        if (LaunchRecord *rec = g_launches.last()) { rec->fixup = form; rec->fixup_sum = sum; rec->fixup_grid = grid; }
+    };
+    if (red == ULTRA_SUM_ADD && many_pieces) {
+        note(FIX_MANY, ULTRA_SUM_ADD);
+        hipLaunchKernelGGL((fixup_kernel<ULTRA_SUM_ADD, 64>), dim3(grid), dim3(256), 0, stream, fp);
+    } else if (red == ULTRA_SUM_ADD) {
+        note(FIX_PLAIN, ULTRA_SUM_ADD);
+        hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_ADD>, dim3(grid), dim3(256), 0, stream, fp);
+    } else if (red == ULTRA_SUM_MIN) {
+        note(FIX_PLAIN, ULTRA_SUM_MIN);
+        hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MIN>, dim3(grid), dim3(256), 0, stream, fp);
+    } else {
+        note(FIX_PLAIN, ULTRA_SUM_MAX);
+        hipLaunchKernelGGL(fixup_kernel<ULTRA_SUM_MAX>, dim3(grid), dim3(256), 0, stream, fp);
+    }
     HIP_TRY(hipGetLastError());
     return ULTRA_OK;
 }
@@ -1208,6 +1256,11 @@ int run_plan(const ultra_segments *seg, KParams p, int64_t gather_rows, int64_t 
         case FAM_DENSE: {
             const DenseCall call{seg, KIND, mul_op, p.relation, p.input, p.grad, p.add_rows, p.bnode, p.bvec, p.bdim, p.out, workspace, F};
             rc = dense_launch(call, stream);
+            {       // (relgraph_dense.hip picks its own kernels: the record says that the dense form ran, and for which call)
+                LaunchRecord rec;
+                rec.family = FAM_DENSE; rec.kind = KIND; rec.sum = sum_op; rec.mul = mul_op; rec.unit_w = 1;
+                g_launches.push(rec).status = rc;
+            }
             break;
         }
         case FAM_ROWGROUP:
@@ -1400,6 +1453,18 @@ int ultra_rspmm_profile_next(void *start_event, void *stop_event) {
     g_prof_stop = static_cast<hipEvent_t>(stop_event);
     return ULTRA_OK;
 }
+
+int ultra_rspmm_launch_records_clear(void) {
+    g_launches.clear();
+    return ULTRA_OK;
+}
+
+int ultra_rspmm_launch_records(int32_t *rows_host, int max_rows) {
+    const int64_t count = rows_host == nullptr ? g_launches.written : g_launches.copy(rows_host, max_rows);
+    return count > 0x7fffffffLL ? 0x7fffffff : (int)count;
+}
+
+const char *ultra_rspmm_launch_record_fields(void) { return kLaunchRecordFieldNames; }
 
 size_t ultra_rspmm_workspace_bytes(const ultra_segments *seg, int64_t F) {
     if (seg == nullptr || F <= 0 || !segments_abi_ok(seg)) return 0;     // (the call over a foreign struct then fails with ULTRA_ERR_ABI)
