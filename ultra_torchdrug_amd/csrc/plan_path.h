@@ -302,9 +302,13 @@ inline PlanPath plan_path(const PlanInput &in) {
     // tiles of one label side by side (quad.inc): as many as the label has, while every team keeps >= 4
     // workgroups.  Measured on every shape tried (rocprofv3, F = 1 024 / 2 048): S-codexs 28.8 -> 19.7 us,
     // S-wn18rr 64.5 -> 60.6 / 172 -> 154 us, S-codexm 84.4 -> 80.8 us, S-fb15k237 246 -> 219 us -- also where
-    // the tiles' slices of the gathered matrix together exceed the XCD's 4 MB L2 (S-fb15k237: 4 x 3.7 MB): what
-    // the sequential walk gains in L2 hits it loses in per-tile start-up and tails; the Infinity Cache backs
-    // the gathers either way.
+    // ONE tile's slice of the gathered matrix about fits the XCD's 4 MiB L2 and four do not (S-fb15k237: 4 x 3.7 MB).
+    // There the walk one tile after the other fetches a third less beyond L2 (604 vs 930 MB, profiles/r04_l2_conc_ab.json)
+    // and is still 40 us slower, 13 us per extra tile pass.  What that is NOT (profiles/quad_tile_order_ab.json, HIP
+    // events, 226 us side by side): long pieces holding a pass up -- 263 us with piece_len = 128 and 32-edge chunks,
+    // 266 / 270 / 263 us with 128 / 64 / 32-edge chunks at piece_len = 512, and no faster with the piece waves at raised
+    // priority; the restaging of the relation tile per pass -- 16-byte loads took 2 us off each.  Unexplained and left as
+    // measured; the slice shares L2 with 2.2 MB of edge words per pass, which was not separated.
     const int bpl = r.geo.blocks_per_label;
     const int slots_per_label = (r.geo.n_slots + kXcd - 1) / kXcd;
     while (!k.no_concurrent_tiles && r.concurrent * 2 <= slots_per_label && bpl % (r.concurrent * 2) == 0 && bpl / (r.concurrent * 2) >= 4)

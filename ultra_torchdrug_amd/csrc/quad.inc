@@ -118,6 +118,11 @@ __global__ __launch_bounds__(kBlock) void quad_kernel(const PParams p) {
     const __amdgpu_buffer_rsrc_t rsrc_wt =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(UNIT_W ? p.gather : p.weight), 0, UNIT_W ? 0u : p.meta_bytes, 0x00020000);
     if ((uint32_t)(uintptr_t)(lds_char_ptr)lds_raw != 0u) __builtin_trap();
+    // The relation tile is staged with 16-byte loads where the table is aligned (the one pointer the dispatch does not require
+    // to be): the loop compiles to one load, a wait for it and one LDS write per round, so 474 relations (121 KB) were 30
+    // round trips to L2 as dwords and are 8 now -- S-fb15k237 evaluation step 1.995 -> 1.956 ms over its five launches.  Eight
+    // such loads in flight before the first write measured SLOWER (HISTORY, profiles/quad_tile_order_ab.json).
+    const bool rel_vec = (reinterpret_cast<uintptr_t>(p.relation) & 15u) == 0;
 
     for (int s = label + kXcd * team; s < p.n_slots; s += kXcd * conc) {
         const int tile = s / p.split;
@@ -127,11 +132,22 @@ __global__ __launch_bounds__(kBlock) void quad_kernel(const PParams p) {
         const uint32_t voff = (uint32_t)((active ? col : 0) * 4);
         float *lds_x = lds_rel + (NEEDS_REL ? p.n_rel * kTile : 0);
         if constexpr (NEEDS_REL) {
-            const int total = p.n_rel * kTile;
-            for (int i = threadIdx.x; i < total; i += kBlock) {
-                const int r = i >> 6;
-                const long long c = (long long)tile * kTile + (i & 63);
-                lds_rel[i] = (c < F) ? p.relation[(long long)r * F + c] : 0.0f;
+            if (rel_vec) {       // 16 bytes per lane: a lane's four columns are inside F or outside (F % 4 == 0)
+                const int total = p.n_rel * (kTile / 4);
+                for (int i = threadIdx.x; i < total; i += kBlock) {
+                    const int r = i >> 4;
+                    const long long c = (long long)tile * kTile + (i & 15) * 4;
+                    qf4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (c < F) v = *reinterpret_cast<const qf4 *>(p.relation + (long long)r * F + c);
+                    *reinterpret_cast<qf4 *>(lds_rel + 4 * i) = v;
+                }
+            } else {
+                const int total = p.n_rel * kTile;
+                for (int i = threadIdx.x; i < total; i += kBlock) {
+                    const int r = i >> 6;
+                    const long long c = (long long)tile * kTile + (i & 63);
+                    lds_rel[i] = (c < F) ? p.relation[(long long)r * F + c] : 0.0f;
+                }
             }
         }
         if constexpr (X_LDS) {
