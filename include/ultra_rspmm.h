@@ -688,6 +688,33 @@ int ultra_sampled_rank_keys(const float *pred, int64_t n_query, int64_t n_cand, 
 int ultra_edge_removal_weights(const ultra_segments *fwd, const ultra_segments *by_src, const ultra_segments *by_rel,
                                const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_pattern,
                                int64_t n_base_rel, float *w_fwd, float *w_src, float *w_rel, int64_t slack, void *stream);
+
+/* Top-K answers: the K best entities of every query that are not known completions, best first (csrc/sampler.inc).
+ * Replaces: nothing the reference has as one call -- its user takes the (Q, N) scores of `predict`, clears the known truths with
+ * the dense (Q, N) filter mask of ultra/task.py:65-100 and calls torch.topk; here the filter is the sorted key array above and
+ * no (Q, N) tensor is built or copied.
+ * For query q:  row = pred + q * row_stride;  completions C_q = {c : base_q + c in keys} with
+ * base_q = (anchor_q * n_rel + rel_q) * n_cand (anchor / rel read at [q * index_stride]);  the candidates are
+ * c in [0, n_cand) \ C_q;  keys == NULL: nothing is filtered.  The candidates are ordered by score DESCENDING, as floats, with
+ *   - -0.0 == +0.0;
+ *   - equal scores by ASCENDING entity index;
+ *   - a NaN score after every number, -inf included (it never outranks anything: `pos <= pred` is false for NaN in
+ *     get_ranking); NaNs among themselves by ascending index.
+ * Outputs, both contiguous [n_query, k]:
+ *   index[q, j] (int64) = the j-th candidate in that order, for j < min(k, n_free_q), n_free_q = n_cand - |C_q|;
+ *   value[q, j] (fp32)  = row[index[q, j]] with its exact bits (re-read from pred, not decoded from a sort key);
+ *   slots j >= n_free_q hold index = -1, value = -inf.  A NaN candidate is a candidate, not an empty slot.
+ * The result is unique: the same on every path, eager or replayed from a hipGraph.
+ * 1 <= k <= 128 and n_cand < 2^31, ULTRA_ERR_BAD_SHAPE otherwise.  Rows of at most 32768 candidates take one launch (one
+ * workgroup per query) and no workspace; longer rows take two: grid (slices of 32768, queries) leaves each slice's k best as
+ * 64-bit sort keys in the workspace (n_query * slices * k * 8 bytes = ultra_topk_keys_workspace, 0 for short rows;
+ * ULTRA_ERR_WORKSPACE when it is smaller), one workgroup per query then selects among them.  Only enqueues work: no allocation,
+ * no host synchronisation, capturable. */
+size_t ultra_topk_keys_workspace(int64_t n_query, int64_t n_cand, int64_t k);
+int ultra_topk_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t row_stride, int64_t k,
+                    const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel,
+                    int64_t index_stride, int64_t n_rel, float *value, int64_t *index,
+                    void *workspace, size_t workspace_bytes, void *stream);
 /* As ultra_edge_removal_weights, and ALSO the marked word copies that ultra_segments.packed_dead takes (any of them NULL: that plan
  * gets none): words_x = the plan's packed words (n_edges + slack of them) with bit 31 set where w_x is set to 0.  Only for plans
  * WITHOUT weights of their own (every weight exactly 1) whose packed words leave bit 31 free (node ids inside the word, id range

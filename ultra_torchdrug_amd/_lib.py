@@ -110,6 +110,8 @@ SIGNATURES = {
     "ultra_strict_negative": (i32, [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
     "ultra_filter_counts": (i32, [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp]),
     "ultra_sampled_rank_keys": (i32, [vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "ultra_topk_keys_workspace": (sz, [i64, i64, i64]),
+    "ultra_topk_keys": (i32, [vp, i64, i64, i64, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, sz, vp]),
     "ultra_edge_removal_weights": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
     "ultra_edge_removal_marks": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     "ultra_prepare_queries": (i32, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),

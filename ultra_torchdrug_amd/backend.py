@@ -11,6 +11,8 @@ optional functions: a backend is an object with this complete interface
     filtered_rank, filtered_rank_keys, strict_negatives, statistics, bce_adversarial_loss, candidate_tiles, candidate_rows,
     score_candidates_supported, score_candidates
     filter_counts, sampled_rank_keys   (reached ONLY when the task has a sampled metric ``hits@K_N`` or ``toy_eval``)
+    topk_keys                          (``task.answer`` / ``engine.answer``; device tensors run ``ultra_topk_keys``, CPU tensors
+                                        the dense path of the same definition)
 
 The parity tests install a second implementation of the same interface (``tests/oracle_ops.py``: the CPU oracle
 behind every operator) with :func:`use`, so that the SAME model code yields the oracle-side numbers; nothing under

@@ -206,6 +206,163 @@ __global__ __launch_bounds__(64 * kSampledWaves) void sampled_rank_keys_kernel(
     if (samples != nullptr && lane < n_sample) samples[q * n_sample + lane] = entity;       // unused slots: -1
 }
 
+// ---------------------------------------------------------------------------------------- top-K answers of a query
+// topk_keys_kernel: the K best candidates of a score row that do NOT complete (anchor_q, rel_q, ?), best first (the contract is in
+// include/ultra_rspmm.h).  Candidate c with score v becomes one 64-bit SORT KEY
+//       high half: order-preserving map of v (-0.0 folded into +0.0; every NaN in one class BELOW -inf)     low half: ~c
+// so that "better" is "larger key" -- equal scores go by ascending index -- and all keys of a row are distinct.  0 is no
+// candidate's key (the NaN class is 1): it marks an empty slot.
+// A workgroup keeps its K best keys, sorted, in LDS [0, 128) and their smallest as the THRESHOLD.  It walks its candidates in
+// tiles of 1024 (four independent loads per thread, the next tile's in flight across the barriers); a candidate that beats the
+// threshold is looked up in the query's range of the completion keys (binary search) and, when it is none of them, appended to
+// LDS [128, 2048) through an LDS counter (one atomic per wave).  When the next tile might not fit, and at the end, best + appended
+// are sorted (bitonic, descending, over the next power of two) and cut to K.  The threshold only changes there, between barriers.
+constexpr int kTopkMax = 128;                 // K <= 128
+constexpr int kTopkLds = 2048;                // keys in LDS (16 KB): [0, 128) the best so far, [128, 2048) survivors
+constexpr int kTopkTile = 1024;               // candidates per step of a workgroup
+constexpr unsigned long long kTopkEmpty = 0ull;
+enum { kTopkRow = 0, kTopkSlice = 1, kTopkCombine = 2 };
+
+struct TopkShared {
+    unsigned long long arr[kTopkLds];
+    unsigned long long thr;
+    long long range[2];
+    int count;
+};
+
+__device__ __forceinline__ unsigned long long topk_key(float v, long long c) {
+    unsigned u = __float_as_uint(v);
+    unsigned m = 1u;                                               // NaN: below -inf (which maps to 0x007fffff)
+    if (v == v) {
+        if (u == 0x80000000u) u = 0u;                              // -0.0 == +0.0
+        m = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    return ((unsigned long long)m << 32) | (unsigned long long)(~(unsigned)c);
+}
+
+// every thread of the workgroup calls it (the ballot and the shuffle are wave-wide)
+__device__ __forceinline__ void topk_push(TopkShared &sh, unsigned long long key, bool pass) {
+    const unsigned long long mask = __ballot(pass ? 1 : 0);
+    if (mask == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)mask) - 1;
+    int start = 0;
+    if (lane == leader) start = atomicAdd(&sh.count, __popcll(mask));
+    start = __shfl(start, leader, 64);
+    if (pass) sh.arr[kTopkMax + start + __popcll(mask & ((1ull << lane) - 1ull))] = key;
+}
+
+// best K of (best so far + appended) -> arr[0, K) descending, threshold = arr[K - 1], count = 0.  Called by every thread, after a
+// barrier behind the last append.
+__device__ void topk_flush(TopkShared &sh, int K) {
+    const int tid = threadIdx.x;
+    const int cnt = sh.count;
+    if (cnt == 0) return;
+    const int n = kTopkMax + cnt;
+    int P = 256;
+    while (P < n) P <<= 1;
+    for (int j = K + tid; j < kTopkMax; j += 256) sh.arr[j] = kTopkEmpty;        // leftovers of the last sort
+    for (int j = n + tid; j < P; j += 256) sh.arr[j] = kTopkEmpty;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const unsigned long long a = sh.arr[i], b = sh.arr[l];
+                if ((a < b) == ((i & k) == 0)) {
+                    sh.arr[i] = b;
+                    sh.arr[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        sh.thr = sh.arr[K - 1];
+        sh.count = 0;
+    }
+    __syncthreads();
+}
+
+// MODE kTopkRow:     grid (queries): the whole row, value / index written.
+// MODE kTopkSlice:   grid (slices, queries): candidates [slice * kRankSlice, ...), the slice's K keys -> ws[q, slice, 0 .. K).
+// MODE kTopkCombine: grid (queries): the best K of ws[q, 0 .. n_slices * K), value / index written.
+template <int MODE>
+__global__ __launch_bounds__(256) void topk_keys_kernel(const float *pred, long long row_stride, long long n_cand, int K,
+                                                        const int64_t *keys, long long n_keys, const int64_t *anchor,
+                                                        const int64_t *rel, long long index_stride, long long n_rel,
+                                                        unsigned long long *ws, long long n_slices, float *value, int64_t *index) {
+    __shared__ TopkShared sh;
+    const int tid = threadIdx.x;
+    const long long q = MODE == kTopkSlice ? blockIdx.y : blockIdx.x;
+    const float *row = pred + q * row_stride;
+    long long c0 = 0, c1 = n_cand;
+    if constexpr (MODE == kTopkSlice) {
+        c0 = (long long)blockIdx.x * kRankSlice;
+        c1 = c0 + kRankSlice < n_cand ? c0 + kRankSlice : n_cand;
+    }
+    if constexpr (MODE == kTopkCombine) c1 = n_slices * K;
+    const unsigned long long *src = ws + q * n_slices * K;         // (kTopkCombine reads it, kTopkSlice writes behind it)
+    const bool filtered = MODE != kTopkCombine && keys != nullptr;
+    int64_t base = 0;
+    if (tid < kTopkMax) sh.arr[tid] = kTopkEmpty;
+    if (tid == 0) {
+        sh.thr = kTopkEmpty;
+        sh.count = 0;
+    }
+    if (filtered) {
+        base = (anchor[q * index_stride] * n_rel + rel[q * index_stride]) * n_cand;
+        if (tid < 2) sh.range[tid] = lower_bound_i64(keys, n_keys, base + (tid ? c1 : c0));     // the slice's part of the range
+    }
+    __syncthreads();
+    const long long lo = filtered ? sh.range[0] : 0, hi = filtered ? sh.range[1] : 0;
+
+    unsigned long long cur[4], nxt[4] = {0ull, 0ull, 0ull, 0ull};
+    auto load_tile = [&](unsigned long long (&out)[4], long long c) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long cc = c + tid + 256 * i;
+            if constexpr (MODE == kTopkCombine) out[i] = cc < c1 ? src[cc] : kTopkEmpty;
+            else out[i] = cc < c1 ? (unsigned long long)__float_as_uint(row[cc]) : 0ull;          // raw bits: the key is formed later
+        }
+    };
+    load_tile(cur, c0);
+    for (long long c = c0; c < c1; c += kTopkTile) {
+        if (c + kTopkTile < c1) load_tile(nxt, c + kTopkTile);
+        const unsigned long long thr = sh.thr;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long cc = c + tid + 256 * i;
+            unsigned long long key = kTopkEmpty;
+            if (cc < c1) key = MODE == kTopkCombine ? cur[i] : topk_key(__uint_as_float((unsigned)cur[i]), cc);
+            bool pass = key > thr;
+            if (pass && lo < hi) {
+                const long long at = lo + lower_bound_i64(keys + lo, hi - lo, base + cc);
+                if (at < hi && keys[at] == base + cc) pass = false;                                // a known completion
+            }
+            topk_push(sh, key, pass);
+        }
+        __syncthreads();
+        const int cnt = sh.count;
+        __syncthreads();                                           // (nobody appends to the next tile before everybody has read cnt)
+        if (cnt > kTopkLds - kTopkMax - kTopkTile) topk_flush(sh, K);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+    }
+    topk_flush(sh, K);
+    if (tid < K) {
+        const unsigned long long key = sh.arr[tid];
+        if constexpr (MODE == kTopkSlice) {
+            ws[(q * n_slices + blockIdx.x) * K + tid] = key;
+        } else {
+            const long long e = key == kTopkEmpty ? -1 : (long long)(~(unsigned)key);
+            index[q * K + tid] = e;
+            value[q * K + tid] = e < 0 ? -INFINITY : row[e];       // the score's own bits, not the key's
+        }
+    }
+}
+
 // Lexicographic lower bound over three sorted int32 columns.
 __device__ __forceinline__ long long lower_bound_3(const int32_t *a, const int32_t *b, const int32_t *c, long long n,
                                                    int va, int vb, int vc) {
@@ -350,6 +507,45 @@ int ultra_sampled_rank_keys(const float *pred, int64_t n_query, int64_t n_cand, 
                        dim3(64 * kSampledWaves), 0, static_cast<hipStream_t>(stream), pred, (long long)row_stride,
                        (long long)n_cand, (long long)n_query, target, (long long)target_stride, keys, (long long)n_keys, anchor,
                        rel, (long long)index_stride, (long long)n_rel, rand, (int)n_sample, optimistic, pessimistic, samples);
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+size_t ultra_topk_keys_workspace(int64_t n_query, int64_t n_cand, int64_t k) {
+    if (n_query <= 0 || n_cand <= kRankSlice || k < 1 || k > kTopkMax) return 0;           // short rows: one launch, no workspace
+    return (size_t)n_query * (size_t)((n_cand + kRankSlice - 1) / kRankSlice) * (size_t)k * sizeof(unsigned long long);
+}
+
+int ultra_topk_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t row_stride, int64_t k, const int64_t *keys,
+                    int64_t n_keys, const int64_t *anchor, const int64_t *rel, int64_t index_stride, int64_t n_rel, float *value,
+                    int64_t *index, void *workspace, size_t workspace_bytes, void *stream) {
+    if (n_query < 0 || n_cand <= 0 || n_cand > 0x7fffffffLL || row_stride < n_cand || n_keys < 0 || index_stride < 0)
+        return ULTRA_ERR_BAD_SHAPE;
+    if (k < 1 || k > kTopkMax) return ULTRA_ERR_BAD_SHAPE;
+    if (n_query == 0) return ULTRA_OK;
+    if (pred == nullptr || value == nullptr || index == nullptr) return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && (anchor == nullptr || rel == nullptr)) return ULTRA_ERR_NULL_POINTER;
+    if (keys != nullptr && n_rel <= 0) return ULTRA_ERR_BAD_SHAPE;
+    const bool sliced = n_cand > kRankSlice;
+    if (n_query > (sliced ? 65535 : 0x7fffffffLL)) return ULTRA_ERR_BAD_SHAPE;              // grid.y / grid.x
+    const size_t need = ultra_topk_keys_workspace(n_query, n_cand, k);
+    if (need > 0 && (workspace == nullptr || workspace_bytes < need)) return ULTRA_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned long long *ws = static_cast<unsigned long long *>(workspace);
+    if (sliced) {
+        const long long n_slices = (n_cand + kRankSlice - 1) / kRankSlice;
+        hipLaunchKernelGGL(topk_keys_kernel<kTopkSlice>, dim3((unsigned)n_slices, (unsigned)n_query), dim3(256), 0, s, pred,
+                           (long long)row_stride, (long long)n_cand, (int)k, keys, (long long)n_keys, anchor, rel,
+                           (long long)index_stride, (long long)n_rel, ws, n_slices, value, index);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(topk_keys_kernel<kTopkCombine>, dim3((unsigned)n_query), dim3(256), 0, s, pred, (long long)row_stride,
+                           (long long)n_cand, (int)k, keys, (long long)n_keys, anchor, rel, (long long)index_stride,
+                           (long long)n_rel, ws, n_slices, value, index);
+    } else {
+        hipLaunchKernelGGL(topk_keys_kernel<kTopkRow>, dim3((unsigned)n_query), dim3(256), 0, s, pred, (long long)row_stride,
+                           (long long)n_cand, (int)k, keys, (long long)n_keys, anchor, rel, (long long)index_stride,
+                           (long long)n_rel, ws, 0LL, value, index);
+    }
     HIP_TRY(hipGetLastError());
     return ULTRA_OK;
 }

@@ -642,6 +642,40 @@ def _ranks_of_unique_queries(task, local, batch_size, graphed, statistics=False,
     return torch.stack([ranks[:n], ranks[n:]], dim=1)
 
 
+@torch.no_grad()
+def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None, filtered=None):
+    """``task.answer`` over any number of queries: the ``k`` best unfiltered entities of ``(anchor[q], relation[q], ?)`` (``head``:
+    of ``(?, relation[q], anchor[q])``).  The queries are scored ``2 * batch_size`` at a time through one :class:`GraphedScores`
+    (the last chunk repeats its end) and ``functional.topk_keys`` is enqueued on each chunk's static scores: nothing of size
+    ``(Q, N)`` beside those scores is built and nothing is read back per chunk.  ``graphed`` (default: on a GPU, in eval mode,
+    when there are at least two full chunks): the score pass is captured once and replayed.  A model without a fused all-entity
+    score head goes through ``task.answer`` chunk by chunk.  Returns ``(entities int64 (Q, k), scores fp32 (Q, k))``."""
+    from . import backend
+    anchor, q_rel, base = task.answer_queries(anchor, relation, head)
+    keys, n_rel, n_node = task.answer_filter(head, filtered)
+    n, chunk = len(anchor), 2 * batch_size
+    if graphed is None:
+        graphed = task.device.type == "cuda" and n >= 2 * chunk and not task.training
+    entities, scores = [], []
+    scorer = None
+    for c in range(0, n, chunk):
+        ids = torch.arange(c, c + chunk, device=anchor.device).clamp(max=n - 1)              # the last chunk repeats its end
+        args = (anchor[ids], q_rel[ids], base[ids])
+        if scorer is None:
+            probe = GraphedScores(task, *args, graphed=False)
+            if probe(*args) is None:                     # no fused all-entity score path for this model
+                parts = [task.answer(anchor[i:i + chunk], base[i:i + chunk], k, head, filtered) for i in range(0, n, chunk)]
+                return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+            scorer = GraphedScores(task, *args, graphed=bool(graphed) and n >= 2 * chunk)
+        value, index = backend.get().topk_keys(scorer(*args), k, keys, args[0], args[2], n_rel, n_node)
+        keep = min(chunk, n - c)
+        entities.append(index[:keep])
+        scores.append(value[:keep])
+    if not entities:
+        return task.answer(anchor, base, k, head, filtered)
+    return torch.cat(entities), torch.cat(scores)
+
+
 # engine.evaluate scores distinct queries instead of triples when the shard holds at most this share of distinct queries
 UNIQUE_QUERY_GAIN = 0.9
 

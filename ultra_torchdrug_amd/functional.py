@@ -1153,6 +1153,74 @@ def sampled_rank_keys(pred, target, keys, anchor, rel, n_rel, rand, n_node=None,
     return (optimistic, pessimistic, samples) if return_samples else (optimistic, pessimistic)
 
 
+TOPK_MAX = 128                  # answers per query of ultra_topk_keys
+
+
+def dense_topk(pred, k, keys, anchor, rel, n_rel):
+    """:func:`topk_keys` on host tensors, from a dense mask: the definition of ``include/ultra_rspmm.h`` as a stable descending
+    sort (ties and ``-0.0 == +0.0`` keep their ascending index order) with NaN scores moved behind every number and the
+    completions behind those."""
+    rows, n = pred.shape
+    group = torch.isnan(pred).long()                                    # 0 number, 1 NaN, 2 known completion
+    if keys is not None and rows:
+        base = (anchor * int(n_rel) + rel) * n
+        first, last = torch.searchsorted(keys, base), torch.searchsorted(keys, base + n)
+        count = last - first
+        row = torch.repeat_interleave(torch.arange(rows), count)
+        at = torch.arange(int(count.sum())) - torch.repeat_interleave(count.cumsum(0) - count, count) + first[row]
+        group[row, keys[at] - base[row]] = 2
+    by_score = torch.sort(torch.nan_to_num(pred, nan=0.0, posinf=float("inf"), neginf=-float("inf")), dim=1, descending=True,
+                          stable=True).indices
+    order = by_score.gather(1, torch.sort(group.gather(1, by_score), dim=1, stable=True).indices)
+    if n < k:
+        order = torch.cat([order, order.new_zeros(rows, k - n)], dim=1)
+    order = order[:, :k]
+    listed = torch.arange(k)[None, :] < (group != 2).sum(dim=1, keepdim=True)
+    index = torch.where(listed, order, torch.full_like(order, -1))
+    value = torch.where(listed, pred.gather(1, order), torch.full((), -float("inf"), dtype=pred.dtype))
+    return value, index
+
+
+def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
+    """The ``k`` best entities of every row of ``pred`` that do not complete ``(anchor[q], rel[q], ?)``, best first
+    (``ultra_topk_keys``, the contract is in ``include/ultra_rspmm.h``): scores descending as floats, ``-0.0 == +0.0``, equal
+    scores by ascending entity, NaN scores after every number.  ``pred`` / ``keys`` / ``anchor`` / ``rel`` / ``n_node`` as in
+    :func:`sampled_rank_keys` (``keys=None``: nothing is filtered); ``1 <= k <= 128``.  Returns ``(value fp32 (B, k), index int64
+    (B, k))``; a row with fewer than ``k`` candidates ends in ``index = -1`` / ``value = -inf``.  The filter is looked up in the
+    sorted keys inside the kernel -- no ``(B, N)`` mask or masked copy of the scores -- with no host synchronisation; the
+    workspace of rows longer than 32768 comes from the caching allocator before the launch.  CPU tensors take a dense path of
+    the same definition."""
+    if pred.dim() != 2 or pred.dtype != torch.float32 or (pred.shape[1] and pred.stride(1) != 1):
+        raise RuntimeError("topk_keys: pred must be fp32 (B, N) with contiguous rows")
+    rows, n_cand = pred.shape
+    if n_cand < 1:
+        raise RuntimeError("topk_keys: pred lists no candidate")
+    if n_node is not None and int(n_node) != n_cand:
+        raise RuntimeError("topk_keys: the scores list %d candidates but the completion keys were built over "
+                           "%d nodes (filter graph and fact graph must share the entity set)" % (n_cand, int(n_node)))
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise RuntimeError("topk_keys: 1 to %d answers per query, got %d" % (TOPK_MAX, k))
+    anchor, rel, stride = _index_pair("topk_keys", anchor, rel, rows, pred.device)
+    if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous()
+                             or keys.device != pred.device):
+        raise RuntimeError("topk_keys: keys must be a contiguous int64 vector on %s" % pred.device)
+    if keys is not None and int(n_rel) <= 0:
+        raise RuntimeError("topk_keys: n_rel must be positive, got %d" % int(n_rel))
+    if rows > 1 and pred.stride(0) < n_cand:
+        raise RuntimeError("topk_keys: the rows of pred overlap")
+    if not pred.is_cuda:
+        return dense_topk(pred, k, keys, anchor, rel, n_rel)
+    value = torch.empty(rows, k, dtype=torch.float32, device=pred.device)
+    index = torch.empty(rows, k, dtype=torch.int64, device=pred.device)
+    if rows:
+        ws_bytes = int(_lib.load().ultra_topk_keys_workspace(rows, n_cand, k))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=pred.device) if ws_bytes else None
+        _launch(pred.device, "ultra_topk_keys", pred, rows, n_cand, pred.stride(0) if rows > 1 else n_cand, k, keys,
+                keys.numel() if keys is not None else 0, anchor, rel, stride, int(n_rel), value, index, ws, ws_bytes)
+    return value, index
+
+
 # Training, opt-in (ULTRA_KEEP_PRE_NORM=1): the fused epilogue's forward keeps z = Linear(cat[input, update]) (one more
 # (N, B, 64) tensor per layer) and the fused backward loads it instead of recomputing it -- a third of that kernel's matrix
 # work, identical gradients.  Measured on an MI355X it only moves the backward kernel 380 -> 365 us at 655 k rows (the kernel

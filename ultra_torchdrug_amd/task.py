@@ -21,6 +21,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import backend, layer
+from .functional import TOPK_MAX
 from .graph import Graph
 
 
@@ -412,6 +413,55 @@ class KnowledgeGraphCompletion(nn.Module):
         if head:
             h, t, r = t, h, r + self.fact_graph.num_relation
         return self.model.visualize(self.fact_graph, rel_inputs, h, t, r)
+
+    def answer_queries(self, anchor, relation, head=False):
+        """The range-checked queries of :meth:`answer` in tail form: ``(anchor, query relation in [0, 2R), base relation)``,
+        each int64 ``(Q,)`` on the task's device -- ``head=True`` asks ``(anchor, relation + R, ?)``
+        (``negative_sample_to_tail``)."""
+        anchor = torch.as_tensor(anchor, device=self.device).reshape(-1)
+        relation = torch.as_tensor(relation, device=self.device).reshape(-1)
+        if anchor.dtype != torch.int64 or relation.dtype != torch.int64 or anchor.shape != relation.shape:
+            raise ValueError("answer: anchor and relation must be int64 (Q,), got %s %s and %s %s"
+                             % (anchor.dtype, tuple(anchor.shape), relation.dtype, tuple(relation.shape)))
+        if len(anchor):
+            # once per call, as engine.validate_triples: the kernels index with these ids without a bounds check of their own
+            n, r = self.num_entity, self.num_relation
+            lo, hi_node, hi_rel = int(torch.min(anchor.min(), relation.min())), int(anchor.max()), int(relation.max())
+            if lo < 0 or hi_node >= n or hi_rel >= r:
+                raise ValueError("queries out of range for context `%s` (%d entities, %d relations): min id %d, max entity %d, "
+                                 "max relation %d" % (self.split, n, r, lo, hi_node, hi_rel))
+        return anchor, (relation + self.fact_graph.num_relation if head else relation), relation
+
+    def answer_filter(self, head=False, filtered=None):
+        """``(keys, n_rel, n_node)`` of the filter of :meth:`answer`: the current context's sorted completion keys of the asked
+        side, or ``None`` when the ranking is not filtered."""
+        graph = self.graph
+        if filtered is None:
+            filtered = self.filtered_ranking
+        return (graph.completion_keys(1 if head else 0) if filtered else None), max(graph.num_relation, 1), graph.num_node
+
+    @torch.no_grad()
+    def answer(self, anchor, relation, k=10, head=False, filtered=None):
+        """Which entities complete ``(anchor, relation, ?)`` -- or, with ``head=True``, ``(?, relation, anchor)`` -- best first (an
+        addition of this package; the reference's user masks the ``predict`` scores and calls ``torch.topk``).  ``anchor`` /
+        ``relation``: int64 ``(Q,)``, ``relation`` in ``[0, R)``.  Entities that complete the query in the current context's
+        filter graph are left out (``filtered``, default ``self.filtered_ranking``).  Returns ``(entities int64 (Q, k), scores
+        fp32 (Q, k))`` in the order ``functional.topk_keys`` defines (score descending, ties by ascending entity, NaN last); a
+        query with fewer than ``k`` candidates ends in ``-1`` / ``-inf``."""
+        anchor, q_rel, base = self.answer_queries(anchor, relation, head)
+        keys, n_rel, n_node = self.answer_filter(head, filtered)
+        k = int(k)
+        if not 1 <= k <= TOPK_MAX:
+            raise ValueError("answer: 1 to %d answers per query, got %d" % (TOPK_MAX, k))
+        if len(anchor) == 0:
+            return anchor.new_zeros(0, k), torch.zeros(0, k, device=anchor.device)
+        pred = self.model.score_all_entities(self.fact_graph, self.relation_representations(base), anchor, q_rel)
+        if pred is None:                          # no fused score head: predict on triples whose other entity is 0
+            zero = torch.zeros_like(anchor)
+            batch = torch.stack([zero, anchor, base] if head else [anchor, zero, base], dim=1)
+            pred = self.predict(batch)[:, 1 if head else 0]
+        value, index = backend.get().topk_keys(pred, k, keys, anchor, base, n_rel, n_node)
+        return index, value
 
     def training_indices(self, batch):
         """task.py:264-274: ``(B, 1 + num_negative)`` index grids, column 0 = the positive triple, the rest strict
