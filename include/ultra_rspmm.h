@@ -715,6 +715,40 @@ int ultra_topk_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t 
                     const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel,
                     int64_t index_stride, int64_t n_rel, float *value, int64_t *index,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* Divergence guard of training steps (csrc/guard.inc): does a LIST of fp32 tensors hold a non-finite element?
+ * Replaces: torch.autograd.set_detect_anomaly(True) of the reference's training run (script/run_full.py:127), which raises at the
+ * step that produces a NaN.  A step replayed from a hipGraph cannot raise, so the verdict is left in a device RECORD that the
+ * host reads outside the graph.
+ * An fp32 element is non-finite iff its exponent bits are all ones, (bits & 0x7f800000) == 0x7f800000: +inf, -inf and NaN of
+ * either sign and any payload; denormals, +-FLT_MAX and -0.0 are finite.
+ * record: int32 [ULTRA_GUARD_FIELDS] in device memory, written by the host ONCE as {0, -1, -1, INT32_MAX} and then only by these
+ * two calls:
+ *   record[ULTRA_GUARD_STEP]            committed steps so far (the steps are numbered from 1)
+ *   record[ULTRA_GUARD_TRIPPED_STEP]    -1 until the first trip, then the number of the step that tripped; sticky
+ *   record[ULTRA_GUARD_TRIPPED_TENSOR]  the lowest index among the tensors that tripped in that step (-1 before)
+ *   record[ULTRA_GUARD_PENDING]         the lowest index that tripped since the last commit; INT32_MAX when clean
+ * ultra_nonfinite_scan_f32: tensor i of the list is numel[i] contiguous floats at ptrs[i] (4-byte aligned, no more: a view may
+ *   start at any element) and has the index first_index + i; ptrs and numel are HOST arrays of n_tensors entries (an entry with
+ *   numel 0 is skipped and keeps its index; its pointer may be NULL).  Every tensor with a non-finite element does
+ *   atomicMin(&record[ULTRA_GUARD_PENDING], its index).  Addresses and sizes travel in the kernel arguments,
+ *   ultra_nonfinite_scan_tensors() tensors per launch, one workgroup per ultra_nonfinite_scan_chunk() elements: as many launches
+ *   as the list needs, and kernel launches only -- no memset, no memcpy, no allocation, no host synchronisation; capturable.
+ * ultra_nonfinite_commit: one thread, behind the scans of a step on the same stream: if nothing tripped before and pending is
+ *   not clean, tripped_step = step + 1 and tripped_tensor = pending; then pending = INT32_MAX and, with advance != 0,
+ *   step = step + 1.  advance == 0 latches in the middle of a step: what was scanned so far is reported ahead of anything
+ *   scanned later in the same step, whatever its index (a parameter that was bad before the forward ahead of the loss). */
+#define ULTRA_GUARD_STEP 0
+#define ULTRA_GUARD_TRIPPED_STEP 1
+#define ULTRA_GUARD_TRIPPED_TENSOR 2
+#define ULTRA_GUARD_PENDING 3
+#define ULTRA_GUARD_FIELDS 4
+int ultra_nonfinite_scan_tensors(void);
+int ultra_nonfinite_scan_chunk(void);
+int ultra_nonfinite_scan_f32(const float *const *ptrs, const int64_t *numel, int64_t n_tensors, int64_t first_index,
+                             int32_t *record, void *stream);
+int ultra_nonfinite_commit(int32_t *record, int advance, void *stream);
+
 /* As ultra_edge_removal_weights, and ALSO the marked word copies that ultra_segments.packed_dead takes (any of them NULL: that plan
  * gets none): words_x = the plan's packed words (n_edges + slack of them) with bit 31 set where w_x is set to 0.  Only for plans
  * WITHOUT weights of their own (every weight exactly 1) whose packed words leave bit 31 free (node ids inside the word, id range

@@ -94,8 +94,9 @@ def capture_semantics(task):
     reference, they never form the product); eager calls test the tables per call, a replay cannot.  A model with a
     non-finite parameter -- a damaged checkpoint -- is therefore captured on the full kernels (shortcuts declined, dense form
     off for the duration of the capture: a process-wide switch, restored to 0), whose NaN propagation is the reference's,
-    with a warning.  Yields whether the parameters are finite.  (Captured TRAINING steps take finiteness on trust: their
-    weights change under the graph, and a run that reached ``inf`` is lost either way.)"""
+    with a warning.  Yields whether the parameters are finite.  (Captured TRAINING steps take finiteness on trust -- their
+    weights change under the graph -- unless they are given a :class:`FiniteGuard`, which scans the parameters inside every
+    replay and raises at the step that finds one non-finite.)"""
     from . import _lib, functional
     params = [p.detach() for p in task.parameters() if p.is_cuda and p.is_floating_point() and p.numel()]
     finite = bool(torch.stack([torch.isfinite(p).all() for p in params]).all()) if params else True
@@ -113,6 +114,143 @@ def capture_semantics(task):
     finally:
         functional.CAPTURE_ASSUMES_FINITE = saved
         lib.ultra_rspmm_force_general_path(0)
+
+
+class NonFiniteError(FloatingPointError):
+    """A guarded training step met an ``inf`` or a ``NaN`` (:class:`FiniteGuard`).  ``step``: the number of the first bad step
+    (guarded steps are counted from 1); ``kind``: ``"loss"``, ``"parameter"`` or ``"gradient"``; ``name``: the parameter's name
+    (``"loss"`` for the loss).  On a rank of a process group whose own tensors were finite -- another rank tripped -- ``kind``
+    and ``name`` are ``None`` and ``step`` is the step of the poll."""
+
+    def __init__(self, step, kind, name):
+        self.step, self.kind, self.name = step, kind, name
+        what = ("another rank met a non-finite value" if kind is None else
+                "non-finite loss" if kind == "loss" else "non-finite %s `%s`" % (kind, name))
+        super().__init__("%s in training step %d" % (what, step))
+
+
+class FiniteGuard:
+    """Divergence guard of the training steps (``train_step``, :class:`GraphedTrainStep`, :class:`GraphedMultiGraphTrainStep`,
+    keyword ``guard=``): a step that meets an ``inf`` or a ``NaN`` in the loss, in a parameter or in a gradient raises
+    :class:`NonFiniteError` instead of applying it.  The reference stops such a run with ``torch.autograd.set_detect_anomaly``
+    (``script/run_full.py:127``); a captured step cannot raise, so HIP kernels (``functional.nonfinite_scan`` /
+    ``nonfinite_commit``: kernel nodes only) leave the verdict in a four-word device record (``self.record``, layout in
+    ``functional``) that the host reads after the replay.
+
+    INDEX ORDER of the scanned tensors (``self.names``): ``"loss"``; then ``"parameter <name>"`` for every entry of
+    ``task.named_parameters()``; then ``"gradient <name>"`` for every entry again.  A parameter without a gradient is skipped,
+    its index stays reserved.  Where several tensors are bad in one step the lowest index is reported.
+
+    ONE GUARDED STEP: (1) the parameters are scanned as the step finds them, before the forward, and latched -- a finite loss does not imply
+    a finite model here: the sparse first layer and the dense relation-graph form never multiply a relation entry by a zero row,
+    so an ``inf`` weight can give finite scores; (2) the loss and the gradients this step's backward wrote are scanned, on every
+    rank its own, before any all-reduce; (3) commit; (4) poll: one small device-to-host read of the record outside the graph; in
+    a process group the tripped flag is MAX-all-reduced (one word, on every rank, on every polled step), so all ranks raise at
+    the same call and their sequences of collectives stay equal (``communicate=False`` steps decide locally, no collective);
+    (5) ``optimizer.step()`` -- not reached by a step that tripped: no parameter and no optimizer state is touched by it.  Every
+    later step raises again, at once, until :meth:`reset`.
+
+    ``poll_every = k > 1``: the record is read on every k-th step only.  The steps in between apply whatever their gradients
+    held; the error still names the FIRST bad step (the record is sticky), but the parameters since that step are lost -- go
+    back to a checkpoint older than ``error.step``.
+
+    The guard looks at the loss, the parameters and the gradients, not at intermediate tensors such as the relation tables."""
+
+    def __init__(self, task, poll_every=1):
+        from . import functional
+        if int(poll_every) < 1:
+            raise ValueError("FiniteGuard: poll_every must be at least 1, got %r" % (poll_every,))
+        self.task, self.poll_every = task, int(poll_every)
+        named = list(task.named_parameters())
+        for name, p in named:
+            if p.dtype != torch.float32:
+                raise RuntimeError("FiniteGuard: parameter `%s` is %s; the scan reads fp32 bit patterns" % (name, p.dtype))
+        self.parameters = [p for _, p in named]
+        self.names = ["loss"] + ["parameter " + name for name, _ in named] + ["gradient " + name for name, _ in named]
+        self._slot = {id(p): i for i, p in enumerate(self.parameters)}
+        self.device = self.parameters[0].device if self.parameters else task.device
+        self.record = functional.nonfinite_record(self.device)
+        self.calls = 0                              # guarded steps so far (every poll_every-th of them reads the record)
+        self.error = None                           # the NonFiniteError of the trip, once the host knows of it
+
+    # ------------------------------------------------------------------ the device side of a step (capturable)
+    def scan_parameters(self):
+        """Scan and LATCH: a parameter that is bad when the step begins is what the error names, not the loss (index 0) that
+        the forward computes from it."""
+        from . import functional
+        functional.nonfinite_scan(self.parameters, self.record, first_index=1)
+        functional.nonfinite_commit(self.record, advance=False)
+
+    def scan_loss(self, loss):
+        from . import functional
+        functional.nonfinite_scan([loss.reshape(-1)], self.record, first_index=0)
+
+    def scan_gradients(self, parameters=None, gradients=None):
+        """The gradients of ``parameters`` (default: all of the task's): ``gradients[id(p)]`` where a mapping is given (a
+        captured phase: the tensors its backward produced), else ``p.grad``; ``None``: skipped."""
+        from . import functional
+        slots = [None] * len(self.parameters)
+        for p in (self.parameters if parameters is None else parameters):
+            slots[self._slot[id(p)]] = gradients.get(id(p)) if gradients is not None else p.grad
+        live = [i for i, g in enumerate(slots) if g is not None]
+        if live:
+            functional.nonfinite_scan(slots[live[0]:live[-1] + 1], self.record,
+                                      first_index=1 + len(self.parameters) + live[0])
+
+    def commit(self):
+        from . import functional
+        functional.nonfinite_commit(self.record)
+
+    # ------------------------------------------------------------------ the host side
+    @property
+    def tripped(self):
+        """Whether a trip is known to the host (set by the poll that found it, cleared by :meth:`reset`); reads nothing."""
+        return self.error is not None
+
+    def raise_if_tripped(self):
+        if self.error is not None:
+            raise self.error
+
+    def check(self, communicate=True):
+        """Read the record NOW (one device-to-host read; in a process group one MAX all-reduce of one word before it, so every
+        rank must call it) and raise :class:`NonFiniteError` if a step tripped, here or on another rank."""
+        from . import functional
+        self.raise_if_tripped()
+        record = self.record
+        if communicate and get_world_size() > 1:
+            flag = (record[functional.GUARD_TRIPPED_STEP:functional.GUARD_TRIPPED_STEP + 1] >= 0).to(torch.int32)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            record = torch.cat([record, flag])
+        host = record.tolist()
+        if host[functional.GUARD_TRIPPED_STEP] >= 0:
+            label = self.names[host[functional.GUARD_TRIPPED_TENSOR]]
+            kind, _, name = label.partition(" ")
+            self.error = NonFiniteError(host[functional.GUARD_TRIPPED_STEP], kind, name or "loss")
+        elif len(host) > functional.GUARD_FIELDS and host[-1] > 0:
+            self.error = NonFiniteError(host[functional.GUARD_STEP], None, None)
+        self.raise_if_tripped()
+
+    def poll(self, communicate=True):
+        """Step (4) of a guarded step: counts the step and, on every ``poll_every``-th, :meth:`check`."""
+        self.calls += 1
+        if self.calls % self.poll_every == 0:
+            self.check(communicate)
+
+    def reset(self, step=None):
+        """Forget the trip (device record and host); the step count goes on (``step``: set it).  In a process group: on every
+        rank.  The caller restores finite parameters first, or the next step trips again."""
+        from . import functional
+        if step is None:
+            step = int(self.record[functional.GUARD_STEP])
+        self.record.copy_(functional.nonfinite_record(self.device, step))
+        self.error = None
+
+    def _warm(self):
+        """The guard's two kernels once on a scratch record, outside any capture (their code is loaded before a capture)."""
+        from . import functional
+        scratch = functional.nonfinite_record(self.device)
+        functional.nonfinite_scan(self.parameters[:1], scratch)
+        functional.nonfinite_commit(scratch)
 
 
 class GraphedPredict:
@@ -217,16 +355,28 @@ class GraphedTrainStep:
     so they issue none; RCCL is warmed by ``reducer.warm()`` (one explicit all-reduce per bucket) unless
     ``warm_collectives=False`` (a caller that builds several steps, :class:`GraphedMultiGraphTrainStep`, warms once itself).
     Every rank that constructs a step issues the same collectives, whatever graph its example batch is from, and every
-    ``__call__`` sends exactly ONE round of buckets (checked)."""
+    ``__call__`` sends exactly ONE round of buckets (checked).
+
+    ``guard``: a :class:`FiniteGuard`.  Its scans and its commit are recorded into the graph(s) as kernel nodes -- the parameters
+    before the forward, the loss and the gradients behind the backward that wrote them (phased: every phase scans the gradients
+    it completes, behind its packs; the commit ends the last phase) -- and every call polls the record between the replay (and
+    the step's collectives) and ``optimizer.step()``.  ``reduce_in_graph=True`` refuses a guard.  Without one the step records
+    and launches exactly what it did before the guard existed."""
 
     def __init__(self, task, optimizer, example_batch, warmup=3, reducer=None, reduce_in_graph=False, warm_collectives=True,
-                 phased=True):
+                 phased=True, guard=None):
         assert example_batch.is_cuda and task.training
+        if guard is not None and reduce_in_graph:
+            raise ValueError("GraphedTrainStep: a FiniteGuard scans each rank's own gradients before they are all-reduced; "
+                             "with reduce_in_graph=True the all-reduce runs inside the backward of the captured graph -- "
+                             "use the phased or the after mode with a guard")
         model = task.model
         if model.remove_one_hop or not model._removal_by_zero_weight(sums_only=True):
             raise ValueError("GraphedTrainStep needs summed messages and remove_one_hop=False (the edge removal that can "
                              "be captured); use engine.train_step for this model")
-        self.task, self.optimizer, self.reducer = task, optimizer, reducer
+        self.task, self.optimizer, self.reducer, self.guard = task, optimizer, reducer, guard
+        # the captures' verification replays the guard's nodes: the record is put back afterwards as it is now
+        guard_record = None if guard is None else guard.record.clone()
         self.static_batch = validate_triples(task, example_batch).clone()
         self.reduce_in_graph = False
         self.mode = "single"
@@ -243,6 +393,8 @@ class GraphedTrainStep:
                     optimizer.zero_grad(set_to_none=True)       # plans, completion keys, kernel attributes, workspaces, allocator
                     loss, _ = task(self.static_batch)
                     loss.backward()
+                if guard is not None:
+                    guard._warm()
             torch.cuda.current_stream().wait_stream(side)
             active = reducer is not None and reducer._active()
             if reducer is not None and (warm_collectives or reduce_in_graph):
@@ -280,6 +432,9 @@ class GraphedTrainStep:
                 self._grads = [(p, p.grad) for p in task.parameters() if p.grad is not None]
         finally:
             model.check_indices = True
+            if guard is not None:
+                torch.cuda.synchronize()
+                guard.record.copy_(guard_record)
 
     def _capture(self, reduce):
         import contextlib
@@ -287,9 +442,16 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         hooks = contextlib.nullcontext() if (reduce or self.reducer is None) else self.reducer.paused()
         # thread_local: other threads of the process (the RCCL watchdog polls events) must not abort the capture
+        guard = self.guard
         with hooks, torch.cuda.graph(self.graph, capture_error_mode="thread_local" if reduce else "relaxed"):
+            if guard is not None:
+                guard.scan_parameters()
             self.static_loss, self.static_metric = self.task(self.static_batch)
             self.static_loss.backward()
+            if guard is not None:
+                guard.scan_loss(self.static_loss)
+                guard.scan_gradients()
+                guard.commit()
             if reduce:
                 self.reducer.finish()
         self.last_negatives = self.task.last_negatives      # (B, num_negative): the tensor every replay rewrites
@@ -310,7 +472,7 @@ class GraphedTrainStep:
         return phase_of, reducer.groups
 
     def _capture_phased(self):
-        task, model, reducer = self.task, self.task.model, self.reducer
+        task, model, reducer, guard = self.task, self.task.model, self.reducer, self.guard
         if len(model.layers) < 2 or not task.rel_models:
             raise _NoPhases("the model has fewer than two entity layers or no relation model")
         self.cut_after = model.cut_at()
@@ -333,9 +495,17 @@ class GraphedTrainStep:
         def pack(phase):
             for b in groups[phase]:
                 reducer.pack(b, produced)
+            if guard is not None:                    # the gradients this phase completed, as its backward wrote them
+                if phase == 0:
+                    guard.scan_loss(self.static_loss)
+                guard.scan_gradients(params[phase], produced)
+                if phase == 2:
+                    guard.commit()
 
         with reducer.paused():
             with torch.cuda.graph(graphs[0], capture_error_mode="relaxed"):
+                if guard is not None:
+                    guard.scan_parameters()
                 model.record_cuts = task.record_cuts = True         # only this forward records the cut tensors
                 try:
                     self.static_loss, self.static_metric = task(self.static_batch)
@@ -445,6 +615,9 @@ class GraphedTrainStep:
     def __call__(self, batch):
         """One step on ``batch`` (same shape as the example): returns ``(loss, metrics averaged over ranks)``."""
         assert batch.shape == self.static_batch.shape
+        guard = self.guard
+        if guard is not None:
+            guard.raise_if_tripped()
         self.static_batch.copy_(batch)
         for p, grad in self._grads:
             p.grad = grad
@@ -455,10 +628,14 @@ class GraphedTrainStep:
             if self.communicate and reducer.total_launched - sent != len(reducer.buckets):
                 raise RuntimeError("GraphedTrainStep: %d bucket all-reduces went out in one step, expected %d"
                                    % (reducer.total_launched - sent, len(reducer.buckets)))
+            if guard is not None:
+                guard.poll(self.communicate)
             self.optimizer.step()
             return self.static_loss.detach(), (reduce_metrics(self.static_metric) if self.communicate else self.static_metric)
         if not self.communicate:                    # measurement only: the step without any cross-rank traffic
             self.graph.replay()
+            if guard is not None:
+                guard.poll(False)
             self.optimizer.step()
             return self.static_loss.detach(), self.static_metric
         if self.mode == "after":
@@ -474,6 +651,8 @@ class GraphedTrainStep:
             self.graph.replay()
             if reducer is None:
                 allreduce_gradients(self.task)
+        if guard is not None:
+            guard.poll(True)
         self.optimizer.step()
         return self.static_loss.detach(), reduce_metrics(self.static_metric)
 
@@ -500,8 +679,9 @@ class GraphedMultiGraphTrainStep:
     ``examples``: optional ``{graph_id: (batch_size, 3) triples}`` to capture with (default: the first ``batch_size`` fact
     edges of each graph).  Contexts with fewer than ``batch_size`` fact edges keep the eager step."""
 
-    def __init__(self, task, optimizer, batch_size, reducer=None, warmup=3, examples=None, phased=True):
+    def __init__(self, task, optimizer, batch_size, reducer=None, warmup=3, examples=None, phased=True, guard=None):
         self.task, self.optimizer, self.batch_size, self.reducer, self.warmup = task, optimizer, int(batch_size), reducer, warmup
+        self.guard = guard                          # ONE FiniteGuard for the captured step of every graph and the eager steps
         self.steps = {}
         self.communicate = True                     # see GraphedTrainStep.communicate
         saved = task.split
@@ -515,7 +695,7 @@ class GraphedMultiGraphTrainStep:
                 if len(example) != self.batch_size:
                     continue
                 self.steps[str(name)] = GraphedTrainStep(task, optimizer, example.to(device), warmup=warmup, reducer=reducer,
-                                                         warm_collectives=False, phased=phased)
+                                                         warm_collectives=False, phased=phased, guard=guard)
         finally:
             if saved is not None:
                 task.use(saved)
@@ -532,7 +712,8 @@ class GraphedMultiGraphTrainStep:
         if step is None or len(triples) != self.batch_size:          # ragged batch / tiny graph: the eager step
             # (honours `communicate` too: a no-traffic measurement must not contain an eager step's collectives, and a rank on
             # the eager branch must issue what its replaying peers issue -- ADVICE r4)
-            return train_step(self.task, self.optimizer, (triples, graph_id), reducer=self.reducer, communicate=self.communicate)
+            return train_step(self.task, self.optimizer, (triples, graph_id), reducer=self.reducer, communicate=self.communicate,
+                              guard=self.guard)
         return step(triples)
 
     @property
@@ -1129,22 +1310,33 @@ def reduce_metrics(metric):
     return {k: packed[i] for i, k in enumerate(keys)}
 
 
-def train_step(task, optimizer, batch, reducer=None, communicate=True):
+def train_step(task, optimizer, batch, reducer=None, communicate=True, guard=None):
     """One fine-tuning step (``ultra/engine.py:62-92`` / torchdrug ``Engine.train``): forward, backward,
     gradient all-reduce, optimizer step.  Returns (loss, metrics averaged over ranks).  ``reducer``: a
     :class:`GradientReducer` over ``task`` -- its hooks start each layer's all-reduce on a side stream while backward
     is still running; without one the gradients go through one flat blocking all-reduce after backward.
     ``communicate=False`` (timing only: what the collectives cost): no cross-rank traffic at all -- the backward runs with the
-    reducer's hooks paused, no gradient and no metric reduce."""
+    reducer's hooks paused, no gradient and no metric reduce.  ``guard``: a :class:`FiniteGuard` -- the step raises
+    :class:`NonFiniteError` before ``optimizer.step()`` when its loss, a parameter or a gradient is not finite (the gradient
+    all-reduce of the step has been issued and retired by then, on every rank)."""
     import contextlib
+    if guard is not None:
+        guard.raise_if_tripped()
+        guard.scan_parameters()
     loss, metric = task(batch)
     optimizer.zero_grad(set_to_none=True)
     with (reducer.paused() if (reducer is not None and not communicate) else contextlib.nullcontext()):
         loss.backward()
+    if guard is not None:                           # this rank's own gradients: before the all-reduce mixes the ranks'
+        guard.scan_loss(loss)
+        guard.scan_gradients()
+        guard.commit()
     if communicate:
         if reducer is not None:
             reducer.finish()
         else:
             allreduce_gradients(task)
+    if guard is not None:
+        guard.poll(communicate)
     optimizer.step()
     return loss.detach(), (reduce_metrics(metric) if communicate else metric)

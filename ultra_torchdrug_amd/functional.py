@@ -1221,6 +1221,74 @@ def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
     return value, index
 
 
+# The divergence guard's record (``include/ultra_rspmm.h``): int32 fields ``step`` (committed steps; they are numbered from 1),
+# ``tripped_step`` (-1 until the first trip, then the number of that step; sticky), ``tripped_tensor`` (the lowest index among
+# the tensors that tripped in that step), ``pending`` (the lowest index that tripped since the last commit; GUARD_CLEAN = none).
+GUARD_STEP, GUARD_TRIPPED_STEP, GUARD_TRIPPED_TENSOR, GUARD_PENDING, GUARD_FIELDS = 0, 1, 2, 3, 4
+GUARD_CLEAN = 0x7fffffff
+_NONFINITE_BITS = 0x7f800000
+
+
+def nonfinite_record(device, step=0):
+    """A fresh record ``[step, -1, -1, GUARD_CLEAN]`` on ``device`` (created by the host, outside any capture)."""
+    return torch.tensor([int(step), -1, -1, GUARD_CLEAN], dtype=torch.int32).to(device)
+
+
+def _check_record(record, device):
+    if (record.dtype != torch.int32 or record.dim() != 1 or record.numel() != GUARD_FIELDS or not record.is_contiguous()
+            or record.device != device):
+        raise RuntimeError("the guard's record must be a contiguous int32 vector of %d fields on %s" % (GUARD_FIELDS, device))
+
+
+def nonfinite_scan(tensors, record, first_index=0):
+    """Tensor ``i`` of ``tensors`` has the index ``first_index + i``; every one that holds a non-finite element -- exponent
+    bits all ones: ``inf`` and ``NaN`` of either sign and any payload, not denormals, ``+-FLT_MAX`` or ``-0.0`` -- lowers
+    ``record[GUARD_PENDING]`` to its index (``ultra_nonfinite_scan_f32``: the whole list in a few launches, the addresses in the
+    kernel arguments; kernels only, capturable, nothing is read back).  A ``None`` entry is skipped and keeps its index.  The
+    tensors are fp32 and contiguous (a view may start at any element) on the record's device; CPU tensors take a dense torch
+    path of the same definition."""
+    device = record.device
+    _check_record(record, device)
+    first_index = int(first_index)
+    if first_index < 0:
+        raise RuntimeError("nonfinite_scan: first_index must not be negative, got %d" % first_index)
+    tensors = [None if t is None else t.detach() for t in tensors]
+    for i, t in enumerate(tensors):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise RuntimeError("nonfinite_scan: tensor %d is %s; the scan reads fp32 bit patterns" % (first_index + i, t.dtype))
+        if t.device != device:
+            raise RuntimeError("nonfinite_scan: tensor %d is on %s, the record on %s" % (first_index + i, t.device, device))
+        if not t.is_contiguous():
+            raise RuntimeError("nonfinite_scan: tensor %d is not contiguous" % (first_index + i))
+    if not record.is_cuda:
+        for i, t in enumerate(tensors):
+            if t is not None and t.numel() and bool(((t.view(torch.int32) & _NONFINITE_BITS) == _NONFINITE_BITS).any()):
+                record[GUARD_PENDING] = min(int(record[GUARD_PENDING]), first_index + i)
+        return
+    if not tensors:
+        return
+    ptrs = _pointer_array([t if t is not None and t.numel() else None for t in tensors])
+    numel = (ctypes.c_int64 * len(tensors))(*[0 if t is None else t.numel() for t in tensors])
+    _launch(device, "ultra_nonfinite_scan_f32", ptrs, numel, len(tensors), first_index, record)
+
+
+def nonfinite_commit(record, advance=True):
+    """Ends a step of the guard, behind its scans (``ultra_nonfinite_commit``, one thread): if nothing tripped before and
+    ``pending`` is not clean, ``tripped_step = step + 1`` and ``tripped_tensor = pending``; then ``pending`` is reset and
+    ``step`` counted.  ``advance=False`` only latches, in the middle of a step: what was scanned so far is reported ahead of
+    whatever is scanned later in the step."""
+    _check_record(record, record.device)
+    if record.is_cuda:
+        _launch(record.device, "ultra_nonfinite_commit", record, int(bool(advance)))
+        return
+    step, tripped, _, pending = record.tolist()
+    if tripped < 0 and pending != GUARD_CLEAN:
+        record[GUARD_TRIPPED_STEP], record[GUARD_TRIPPED_TENSOR] = step + 1, pending
+    record[GUARD_PENDING], record[GUARD_STEP] = GUARD_CLEAN, step + int(bool(advance))
+
+
 # Training, opt-in (ULTRA_KEEP_PRE_NORM=1): the fused epilogue's forward keeps z = Linear(cat[input, update]) (one more
 # (N, B, 64) tensor per layer) and the fused backward loads it instead of recomputing it -- a third of that kernel's matrix
 # work, identical gradients.  Measured on an MI355X it only moves the backward kernel 380 -> 365 us at 655 k rows (the kernel
