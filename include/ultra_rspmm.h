@@ -418,6 +418,39 @@ int ultra_beam_search_step_f32(const int32_t *row_ptr, const int32_t *src, const
                                int64_t n_node, int64_t n_edges, int64_t tail, int64_t K, float *distance,
                                int32_t *back_edge, int32_t *back_rank, void *stream);
 
+/*
+ * Hop distances from many sources: bit-parallel multi-source BFS (csrc/hop_distance.hip).
+ * Replaces: NeuralBellmanFordNetwork._get_shortest_distance (ultra/model.py:302-314) and RelationModel._get_shortest_distance
+ * (ultra/rel_model.py:77-89) -- num_iters passes of gather + scatter_min over (E, B) tensors.
+ * Over the coalesced dst-CSR of a directed graph (RelCSR.csr_arrays; the relation of an edge plays no part):
+ *   row_ptr int32 [n_node + 1], src int32 [n_edges]   (rows = destination nodes: edge e of row v runs src[e] -> v)
+ *   w fp32 [n_edges] or NULL                          an edge whose weight is exactly 0.0f DOES NOT EXIST for this call (the form
+ *                                                     in which edges are removed for a step); other weights are not looked at;
+ *                                                     NULL = every edge exists and the read is skipped
+ *   sources int64 [n_source]                          may repeat (equal columns); one outside [0, n_node) reaches nothing
+ * Definition:  dist[v][b] = the number of edges on a shortest path sources[b] -> v along the edge direction when that number is
+ * <= num_iters, and n_node otherwise (the reference's sentinel, `ones * graph.num_node`: unreachable, or farther than the cap).
+ * dist[sources[b]][b] = 0; self-loops and duplicate edges change nothing; columns are independent; num_iters >= 0 (the
+ * reference's default is 100, and the cap is part of the definition: num_iters = 0 leaves only the sources at 0).
+ * Outputs, at least one of them non-NULL (ULTRA_ERR_BAD_SHAPE otherwise), each written completely:
+ *   dist_matrix  int32 [n_node][n_source]             the reference's layout, or NULL
+ *   dist_targets int32 [n_source][per_source]         dist[targets[b][j]][b] for targets int64 [n_source][per_source], computed
+ *                                                     WITHOUT the matrix (a target outside [0, n_node) holds n_node), or NULL
+ * The sources are taken 64 at a time, one 64-bit word per node each for visited / frontier / next, so the workspace is
+ * ultra_hop_distance_workspace(n_node) = 3 * 8 * n_node + 16 bytes whatever n_source is (ULTRA_ERR_WORKSPACE when smaller).
+ * poll != 0: after every level the host reads one device word (the number of bits the level added) and a source block ends
+ * at the first level that adds nothing -- the call synchronises the stream.  poll == 0, or a stream that is being captured:
+ * exactly num_iters levels are enqueued per source block and nothing is read (no allocation, no synchronisation; capturable);
+ * the surplus levels change nothing, so both ways give the same integers, as does every schedule (the bitmaps are combined
+ * with integer OR only).  ULTRA_ERR_BAD_SHAPE for a negative size or num_iters, n_node >= 2^31 - 1 or n_edges >= 2^31.  Row
+ * bounds are clamped to [0, n_edges] and out-of-range edge sources are skipped.
+ */
+size_t ultra_hop_distance_workspace(int64_t n_node);
+int ultra_hop_distance(const int32_t *row_ptr, const int32_t *src, const float *w, int64_t n_node, int64_t n_edges,
+                       const int64_t *sources, int64_t n_source, int64_t num_iters, const int64_t *targets,
+                       int64_t per_source, int32_t *dist_matrix, int32_t *dist_targets, int poll, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 
 /*
  * Dense epilogue of one Bellman-Ford layer, fused (dim must be 64, the shipped architecture):

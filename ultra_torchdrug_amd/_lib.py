@@ -89,6 +89,8 @@ SIGNATURES = {
     "ultra_rspmm_backward_accumulate_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]),
     "ultra_rspmm_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]),
     "ultra_beam_search_step_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]),
+    "ultra_hop_distance_workspace": (sz, [i64]),
+    "ultra_hop_distance": (i32, [vp, vp, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, i32, vp, sz, vp]),
     "ultra_rspmm_backward_active_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp, i64, vp, vp]),
     "ultra_node_bitmap": (i32, [vp, i64, i64, i64, vp, vp]),
     "ultra_rspmm_drelation_boundary_f32": (i32, [seg, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, vp]),

@@ -23,6 +23,8 @@
 //       -> (d_relation, d_input)
 //   ultra_mi::beam_search_step(row_ptr, src, edge_grad, input, tail) -> (distance, back_edge, back_rank)
 //       one layer of the path beam search of TransferNBFNet.visualize (CUDA and CPU keys)
+//   ultra_mi::hop_distance(row_ptr, src, w?, sources, num_iters, targets?) -> Tensor
+//       hop distances from many sources, int32 (N, B) or -- with targets (B, K) -- int32 (B, K) (CUDA and CPU keys)
 //   plan-based forms used by ultra_torchdrug_amd.functional (the plan = the bytes of one `ultra_segments` struct in a
 //   CPU uint8 tensor; the device arrays it points to are owned by the Python RelCSR object):
 //   ultra_mi::rspmm_plan_fwd(plan, relation, input, add_rows?, boundary_node?, boundary_value?, n_src, sum_op, mul_op) -> Tensor
@@ -34,6 +36,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
+#include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cfloat>
@@ -1093,6 +1096,139 @@ std::tuple<Tensor, Tensor, Tensor> beam_search_step_hip(const Tensor &row_ptr, c
     return {distance, back_edge, back_rank};
 }
 
+// ------------------------------------------------------------------------------------------------ hop_distance
+// Hop distances from many sources (include/ultra_rspmm.h, ultra_hop_distance): dist[v][b] = edges on a
+// shortest path sources[b] -> v when <= num_iters, N otherwise; an edge of weight exactly 0 does not exist.  The device key runs
+// the bit-parallel BFS of csrc/hop_distance.hip; the CPU key below is a host implementation of its own (out-adjacency by a
+// counting sort, then a queue BFS per source).  Integers: the two agree entry for entry.
+struct HopArgs {
+    int64_t n_node, n_edges, n_source, per_source;
+    bool has_w, has_targets;
+};
+
+HopArgs check_hop(const Tensor &row_ptr, const Tensor &src, const optional<Tensor> &w, const Tensor &sources, int64_t num_iters,
+                  const optional<Tensor> &targets, bool read_values) {
+    TORCH_CHECK_VALUE(num_iters >= 0, "ultra_mi::hop_distance: num_iters must not be negative, got ", num_iters);
+    TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.numel() >= 1 && src.dim() == 1 && sources.dim() == 1,
+                "ultra_mi::hop_distance: row_ptr (N + 1,), src (E,), sources (B,) expected");
+    TORCH_CHECK(row_ptr.scalar_type() == at::kInt && src.scalar_type() == at::kInt, "ultra_mi::hop_distance: int32 row_ptr / src");
+    TORCH_CHECK(sources.scalar_type() == at::kLong, "ultra_mi::hop_distance: int64 sources");
+    const bool has_w = w.has_value() && w->defined(), has_targets = targets.has_value() && targets->defined();
+    const int64_t n_node = row_ptr.numel() - 1, n_edges = src.numel(), n_source = sources.numel();
+    if (has_w)
+        TORCH_CHECK(w->dim() == 1 && w->numel() == n_edges && w->scalar_type() == at::kFloat,
+                    "ultra_mi::hop_distance: w must be fp32 (E,)");
+    if (has_targets)
+        TORCH_CHECK(targets->dim() == 2 && targets->size(0) == n_source && targets->scalar_type() == at::kLong,
+                    "ultra_mi::hop_distance: targets must be int64 (B, K), got ", targets->sizes());
+    for (const Tensor *t : {&src, &sources})
+        TORCH_CHECK(t->device() == row_ptr.device(), "ultra_mi::hop_distance: all tensors must share a device");
+    TORCH_CHECK(!has_w || w->device() == row_ptr.device(), "ultra_mi::hop_distance: all tensors must share a device");
+    TORCH_CHECK(!has_targets || targets->device() == row_ptr.device(), "ultra_mi::hop_distance: all tensors must share a device");
+    TORCH_CHECK(n_node < INT32_MAX && n_edges < INT32_MAX, "ultra_mi::hop_distance: graph too large for int32 indices");
+    // values are read here (reductions, a few host reads on the device) so that bad ones raise on both keys -- except inside a
+    // stream capture, where nothing can be read: there the kernels' own range checks stand alone
+    if (read_values) {
+        if (n_source > 0) {
+            const int64_t lo = sources.min().item<int64_t>(), hi = sources.max().item<int64_t>();
+            TORCH_CHECK(lo >= 0 && hi < n_node, "ultra_mi::hop_distance: sources outside [0, ", n_node, "): min ", lo, ", max ", hi);
+        }
+        if (has_targets && targets->numel() > 0) {
+            const int64_t lo = targets->min().item<int64_t>(), hi = targets->max().item<int64_t>();
+            TORCH_CHECK(lo >= 0 && hi < n_node, "ultra_mi::hop_distance: targets outside [0, ", n_node, "): min ", lo, ", max ", hi);
+        }
+        const Tensor rp = row_ptr.to(at::kLong);
+        bool bad = rp[0].item<int64_t>() != 0 || rp[n_node].item<int64_t>() != n_edges;
+        if (!bad && n_node > 0) {
+            Tensor flags = (rp.narrow(0, 1, n_node) < rp.narrow(0, 0, n_node)).any();
+            if (n_edges > 0) flags = flags | (src < 0).any() | (src >= n_node).any();
+            bad = flags.item<bool>();
+        }
+        TORCH_CHECK(!bad, "ultra_mi::hop_distance: malformed CSR (row_ptr must run from 0 to E without decreasing, src must lie "
+                    "in [0, N))");
+    }
+    return {n_node, n_edges, n_source, has_targets ? targets->size(1) : 0, has_w, has_targets};
+}
+
+Tensor hop_distance_cpu(const Tensor &row_ptr, const Tensor &src, const optional<Tensor> &w, const Tensor &sources,
+                        int64_t num_iters, const optional<Tensor> &targets) {
+    for (const Tensor *t : {&row_ptr, &src, &sources})
+        TORCH_CHECK(t->device().is_cpu(), "ultra_mi (CPU): hop_distance: all tensors must share a device");
+    const HopArgs a = check_hop(row_ptr, src, w, sources, num_iters, targets, true);
+    const int64_t N = a.n_node, E = a.n_edges, B = a.n_source, K = a.per_source;
+    Tensor out = a.has_targets ? at::empty({B, K}, row_ptr.options()) : at::empty({N, B}, row_ptr.options());
+    if (out.numel() == 0) return out;
+    const Tensor rp_t = row_ptr.contiguous(), s_t = src.contiguous(), b_t = sources.contiguous();
+    const Tensor w_t = a.has_w ? w->contiguous() : Tensor(), t_t = a.has_targets ? targets->contiguous() : Tensor();
+    const int *rp = rp_t.data_ptr<int>(), *sp = E ? s_t.data_ptr<int>() : nullptr;
+    const float *wp = a.has_w && E ? w_t.data_ptr<float>() : nullptr;
+    const int64_t *bp = b_t.data_ptr<int64_t>(), *tp = a.has_targets ? t_t.data_ptr<int64_t>() : nullptr;
+    int *op = out.data_ptr<int>();
+    // the edges that exist, grouped by their source node: out_ptr / out_dst (a counting sort of the dst-CSR)
+    std::vector<int64_t> out_ptr((size_t)N + 1, 0);
+    for (int64_t e = 0; e < E; ++e)
+        if (wp == nullptr || wp[e] != 0.0f) ++out_ptr[(size_t)sp[e] + 1];
+    for (int64_t v = 0; v < N; ++v) out_ptr[(size_t)v + 1] += out_ptr[(size_t)v];
+    std::vector<int> out_dst((size_t)out_ptr[(size_t)N]);
+    {
+        std::vector<int64_t> at_(out_ptr.begin(), out_ptr.end() - 1);
+        for (int64_t v = 0; v < N; ++v)
+            for (int64_t e = rp[v]; e < rp[v + 1]; ++e)
+                if (wp == nullptr || wp[e] != 0.0f) out_dst[(size_t)at_[(size_t)sp[e]]++] = (int)v;
+    }
+    at::parallel_for(0, B, 1, [&](int64_t b0, int64_t b1) {
+        std::vector<int> dist((size_t)N), queue((size_t)N);
+        for (int64_t b = b0; b < b1; ++b) {
+            std::fill(dist.begin(), dist.end(), (int)N);
+            size_t head = 0, tail = 0;
+            dist[(size_t)bp[b]] = 0;
+            queue[tail++] = (int)bp[b];
+            while (head < tail) {
+                const int u = queue[head++];
+                const int d = dist[(size_t)u];
+                if (d >= num_iters) break;                      // the queue is in distance order: the cap ends the search
+                for (int64_t i = out_ptr[(size_t)u]; i < out_ptr[(size_t)u + 1]; ++i) {
+                    const int v = out_dst[(size_t)i];
+                    if (dist[(size_t)v] == (int)N) {
+                        dist[(size_t)v] = d + 1;
+                        queue[tail++] = v;
+                    }
+                }
+            }
+            if (tp != nullptr)
+                for (int64_t j = 0; j < K; ++j) op[b * K + j] = dist[(size_t)tp[b * K + j]];
+            else
+                for (int64_t v = 0; v < N; ++v) op[v * B + b] = dist[(size_t)v];
+        }
+    });
+    return out;
+}
+
+Tensor hop_distance_hip(const Tensor &row_ptr, const Tensor &src, const optional<Tensor> &w, const Tensor &sources,
+                        int64_t num_iters, const optional<Tensor> &targets) {
+    check_dense(row_ptr, "row_ptr", at::kInt, row_ptr);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(row_ptr.device());
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    TORCH_CHECK(hipStreamIsCapturing(static_cast<hipStream_t>(current_stream(row_ptr)), &capture) == hipSuccess,
+                "ultra_mi::hop_distance: hipStreamIsCapturing failed");
+    const HopArgs a = check_hop(row_ptr, src, w, sources, num_iters, targets, capture == hipStreamCaptureStatusNone);
+    const int64_t N = a.n_node, B = a.n_source, K = a.per_source;
+    Tensor out = a.has_targets ? at::empty({B, K}, row_ptr.options()) : at::empty({N, B}, row_ptr.options());
+    if (out.numel() == 0) return out;
+    const Tensor rp = row_ptr.contiguous(), s = src.contiguous(), b = sources.contiguous();
+    const Tensor w_c = a.has_w ? w->contiguous() : Tensor(), t_c = a.has_targets ? targets->contiguous() : Tensor();
+    const int64_t ws_bytes = (int64_t)ultra_hop_distance_workspace(N);
+    Tensor ws = at::empty({(ws_bytes + 7) / 8}, row_ptr.options().dtype(at::kLong));
+    // poll = 1: the library itself runs the fixed number of levels on a capturing stream
+    check_status(ultra_hop_distance(rp.data_ptr<int>(), a.n_edges ? s.data_ptr<int>() : nullptr,
+                                    a.has_w && a.n_edges ? w_c.data_ptr<float>() : nullptr, N, a.n_edges, b.data_ptr<int64_t>(), B,
+                                    num_iters, a.has_targets ? t_c.data_ptr<int64_t>() : nullptr, K,
+                                    a.has_targets ? nullptr : out.data_ptr<int>(), a.has_targets ? out.data_ptr<int>() : nullptr,
+                                    1, ws.data_ptr(), (size_t)ws_bytes, current_stream(row_ptr)),
+                 "ultra_hop_distance");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
@@ -1105,6 +1241,7 @@ TORCH_LIBRARY(ultra_mi, m) {
     m.def("rspmm_plan_bwd(Tensor? by_src, Tensor? by_rel, Tensor relation, Tensor input, Tensor? output, Tensor output_grad, "
           "Tensor(a!)? d_input, bool accumulate, int n_src, int n_dst, int sum_op, int mul_op) -> Tensor");
     m.def("beam_search_step(Tensor row_ptr, Tensor src, Tensor edge_grad, Tensor input, int tail) -> (Tensor, Tensor, Tensor)");
+    m.def("hop_distance(Tensor row_ptr, Tensor src, Tensor? w, Tensor sources, int num_iters, Tensor? targets) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return ultra_rspmm_abi_version(); });
     m.def("rspmm_rotate_fwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, int block, "
           "int sum_op) -> Tensor");
@@ -1140,6 +1277,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("rspmm_fwd", rspmm_fwd_hip);
     m.impl("rspmm_bwd", rspmm_bwd_hip);
     m.impl("beam_search_step", beam_search_step_hip);
+    m.impl("hop_distance", hop_distance_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)
@@ -1148,6 +1286,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CPU, m) {
     m.impl("rspmm_fwd", rspmm_fwd_cpu);
     m.impl("rspmm_bwd", rspmm_bwd_cpu);
     m.impl("beam_search_step", beam_search_step_cpu);
+    m.impl("hop_distance", hop_distance_cpu);
 }
 
 // the plan tensor lives on the CPU while the dense operands live on the device: no single backend key fits

@@ -824,14 +824,18 @@ def _ranks_of_unique_queries(task, local, batch_size, graphed, statistics=False,
 
 
 @torch.no_grad()
-def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None, filtered=None):
+def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None, filtered=None, with_hops=False):
     """``task.answer`` over any number of queries: the ``k`` best unfiltered entities of ``(anchor[q], relation[q], ?)`` (``head``:
     of ``(?, relation[q], anchor[q])``).  The queries are scored ``2 * batch_size`` at a time through one :class:`GraphedScores`
     (the last chunk repeats its end) and ``functional.topk_keys`` is enqueued on each chunk's static scores: nothing of size
     ``(Q, N)`` beside those scores is built and nothing is read back per chunk.  ``graphed`` (default: on a GPU, in eval mode,
     when there are at least two full chunks): the score pass is captured once and replayed.  A model without a fused all-entity
-    score head goes through ``task.answer`` chunk by chunk.  Returns ``(entities int64 (Q, k), scores fp32 (Q, k))``."""
+    score head goes through ``task.answer`` chunk by chunk.  Returns ``(entities int64 (Q, k), scores fp32 (Q, k))`` and, with
+    ``with_hops``, ``task.answer_hops`` of all of them as a third result (one hop-distance call behind the chunks)."""
     from . import backend
+    if with_hops:
+        entities, scores = answer(task, anchor, relation, k, head, batch_size, graphed, filtered)
+        return entities, scores, task.answer_hops(task.answer_queries(anchor, relation, head)[0], entities)
     anchor, q_rel, base = task.answer_queries(anchor, relation, head)
     keys, n_rel, n_node = task.answer_filter(head, filtered)
     n, chunk = len(anchor), 2 * batch_size
@@ -942,6 +946,52 @@ def evaluate(task, triples, batch_size=16, graphed=None, cache_relations=None, u
         return task.evaluate(ranking, rel=both[:, 2].contiguous()), ranking
     ranking = gather_variable(ranks)
     return task.evaluate(ranking), ranking
+
+
+@torch.no_grad()
+def evaluate_by_distance(task, triples, max_hops=None, **evaluate_kwargs):
+    """:func:`evaluate`, and its metrics again per hop distance between head and tail (the standard diagnostic of this model
+    family: a model of L layers conditions a score on the anchor only within L hops, so a weak result on a new graph is either the
+    model or the graph's diameter).  ``max_hops`` defaults to the number of layers.  :func:`evaluate` runs once, unchanged;
+    ``distance`` = ``task.hop_distance(triples, num_iters=max_hops)`` is computed on every rank for the whole set (cheap, no
+    collective).  Returns ``(by_distance, distance, ranking)``: ``by_distance`` maps ``0, 1, ..., max_hops`` and ``"beyond"``
+    (farther than ``max_hops``, or unreachable) to ``{"count": rows, **task.evaluate(those rows)}`` with the ``rel=`` /
+    ``num_candidates=`` arguments :func:`evaluate` passes, restricted to the rows; empty buckets are left out, and the buckets
+    partition the triples.  ``distance`` int32 ``(n,)`` holds ``task.num_entity`` for "beyond"."""
+    if max_hops is None:
+        max_hops = len(task.model.layers)
+    max_hops = int(max_hops)
+    if max_hops < 0:
+        raise ValueError("evaluate_by_distance: max_hops must not be negative, got %d" % max_hops)
+    _, ranking = evaluate(task, triples, **evaluate_kwargs)
+    triples = triples.to(task.device)
+    distance = task.hop_distance(triples, num_iters=max_hops)
+    rel = triples[:, 2].contiguous() if task.metric_per_rel else None
+    num_candidates = None
+    if task.needs_statistics:
+        # what evaluate() gathered as rank_statistics column 1: the number of unfiltered candidates of either query of a triple
+        from . import backend
+        graph, (h, t, r) = task.graph, triples.t()
+        if backend.get().accepts(triples):
+            n_rel = max(graph.num_relation, 1)
+            keys = (graph.completion_keys(0), graph.completion_keys(1)) if task.filtered_ranking else (None, None)
+            num_candidates = torch.stack([backend.get().filter_counts(keys[0], h, r, n_rel, graph.num_node),
+                                          backend.get().filter_counts(keys[1], t, r, n_rel, graph.num_node)], dim=1)
+        else:
+            batch_size = evaluate_kwargs.get("batch_size", 16)
+            mask = [task.target(triples[i:i + batch_size])[0].sum(dim=-1) for i in range(0, len(triples), batch_size)]
+            num_candidates = torch.cat(mask) if mask else torch.zeros(0, 2, dtype=torch.long, device=triples.device)
+            if not task.filtered_ranking:
+                num_candidates = torch.full_like(num_candidates, graph.num_node)
+    by_distance = {}
+    for name in list(range(max_hops + 1)) + ["beyond"]:
+        rows = (distance > max_hops) if name == "beyond" else (distance == name)
+        count = int(rows.sum())
+        if count:
+            by_distance[name] = {"count": count,
+                                 **task.evaluate(ranking[rows], rel=None if rel is None else rel[rows],
+                                                 num_candidates=None if num_candidates is None else num_candidates[rows])}
+    return by_distance, distance, ranking
 
 
 @torch.no_grad()

@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1859,3 +1859,76 @@ def beam_search_step(row_ptr, src, edge_grad, input, tail):
     if input.dim() != 2 or not 1 <= input.shape[1] <= BEAM_MAX:
         raise ValueError("beam_search_step: input must be (N, K) with 1 <= K <= %d, got %s" % (BEAM_MAX, tuple(input.shape)))
     return _torch_ext.load().beam_search_step(row_ptr, src, edge_grad, input, int(tail))
+
+
+HOP_ITERS = 100      # the reference's num_iters (ultra/model.py:302): the cap is part of the definition
+
+
+def _hop_csr(csr):
+    if isinstance(csr, RelCSR):
+        row_ptr, src, _, w = csr.csr_arrays
+        return row_ptr, src, w
+    if isinstance(csr, (tuple, list)) and len(csr) == 3:
+        return tuple(csr)
+    raise TypeError("hop_distance: csr must be a RelCSR or a (row_ptr, src, w) triple, got %s" % type(csr).__name__)
+
+
+def hop_distance(csr, sources, num_iters=HOP_ITERS, targets=None, poll=None):
+    """Hop distances from many sources at once (``torch.ops.ultra_mi.hop_distance``: the bit-parallel multi-source BFS of
+    ``csrc/hop_distance.hip`` for device tensors, a queue BFS on the host for CPU tensors -- the same integers; the contract is
+    in ``include/ultra_rspmm.h``).
+
+    ``csr``: a :class:`RelCSR` or ``(row_ptr int32 (N + 1,), src int32 (E,), w fp32 (E,) | None)``, the coalesced dst-CSR
+    (:attr:`RelCSR.csr_arrays` without its relation column); ``sources`` int64 ``(B,)``.  Returns int32 ``(N, B)``:
+    ``dist[v, b]`` = edges on a shortest path ``sources[b] -> v`` along the edge direction if that is ``<= num_iters``, else
+    ``N`` (unreachable, or farther than the cap: ``_get_shortest_distance``, ``ultra/model.py:302-314``).  An edge whose
+    coalesced weight is exactly 0 does not exist (``Graph.reweighted`` / ``Graph.without_triples`` remove edges that way); other
+    weights are ignored.  With ``targets`` int64 ``(B, K)`` the result is int32 ``(B, K)``, ``out[b, j] = dist[targets[b, j],
+    b]``, computed without the matrix.  ``poll`` (device only): ``True`` stops each block of 64 sources at the first level that
+    adds nothing, by one small host read per level; ``False`` enqueues exactly ``num_iters`` levels and reads nothing;
+    ``None``: poll unless the stream is being captured.  The result does not depend on it.  ``ULTRA_BINDING=ctypes`` and an explicit
+    ``poll=False`` (an argument of the C entry, not of the operator) go through the C ABI directly."""
+    row_ptr, src, w = _hop_csr(csr)
+    sources = torch.as_tensor(sources, device=row_ptr.device) if not isinstance(sources, torch.Tensor) else sources
+    num_iters = int(num_iters)
+    if not row_ptr.is_cuda or (_torch_ext.binding() == "torch" and poll is not False):
+        return _torch_ext.load().hop_distance(row_ptr, src, w, sources, num_iters, targets)
+    # the C ABI through _launch: the operator's checks, restated (values are read only outside a capture)
+    capturing = torch.cuda.is_current_stream_capturing()
+    given = [t for t in (row_ptr, src, w, sources, targets) if t is not None]
+    if any(not isinstance(t, torch.Tensor) or t.device != row_ptr.device for t in given):
+        raise RuntimeError("hop_distance: all tensors must share a device")
+    if num_iters < 0:
+        raise ValueError("hop_distance: num_iters must not be negative, got %d" % num_iters)
+    if row_ptr.dtype != torch.int32 or src.dtype != torch.int32 or row_ptr.dim() != 1 or src.dim() != 1 or not row_ptr.numel():
+        raise RuntimeError("hop_distance: row_ptr (N + 1,) and src (E,) must be int32")
+    n_node, n_edges = row_ptr.numel() - 1, src.numel()
+    if w is not None and (w.dtype != torch.float32 or tuple(w.shape) != (n_edges,)):
+        raise RuntimeError("hop_distance: w must be fp32 (E,)")
+    if sources.dtype != torch.int64 or sources.dim() != 1:
+        raise RuntimeError("hop_distance: sources must be int64 (B,)")
+    n_source = sources.numel()
+    if targets is not None and (targets.dtype != torch.int64 or targets.dim() != 2 or targets.shape[0] != n_source):
+        raise RuntimeError("hop_distance: targets must be int64 (B, K), got %s %s" % (targets.dtype, tuple(targets.shape)))
+    if not capturing:
+        for name, ids in (("sources", sources), ("targets", targets)):
+            if ids is not None and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_node):
+                raise RuntimeError("hop_distance: %s outside [0, %d)" % (name, n_node))
+        rp = row_ptr.long()
+        bad = int(rp[0]) != 0 or int(rp[-1]) != n_edges or bool((rp[1:] < rp[:-1]).any())
+        if bad or (n_edges and (int(src.min()) < 0 or int(src.max()) >= n_node)):
+            raise RuntimeError("hop_distance: malformed CSR (row_ptr must run from 0 to E without decreasing, src must lie in "
+                               "[0, N))")
+    per_source = targets.shape[1] if targets is not None else 0
+    out = torch.empty((n_source, per_source) if targets is not None else (n_node, n_source), dtype=torch.int32,
+                      device=row_ptr.device)
+    if out.numel() == 0:
+        return out
+    ws_bytes = int(_lib.load().ultra_hop_distance_workspace(n_node))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=row_ptr.device)
+    poll = (not capturing) if poll is None else bool(poll)
+    _launch(row_ptr.device, "ultra_hop_distance", row_ptr.contiguous(), src.contiguous() if n_edges else None,
+            w.contiguous() if (w is not None and n_edges) else None, n_node, n_edges, sources.contiguous(), n_source, num_iters,
+            targets.contiguous() if targets is not None else None, per_source, None if targets is not None else out,
+            out if targets is not None else None, int(poll), ws, ws_bytes)
+    return out

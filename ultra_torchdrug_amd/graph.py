@@ -139,6 +139,16 @@ class Graph:
         g._relcsr = self.relcsr.with_removed_edges(h, t, r, n_base_rel)
         return g
 
+    def hop_distance(self, sources, num_iters=100, targets=None):
+        """Hop distances along the edges (``node_in -> node_out``) from ``sources`` int64 ``(B,)``: int32 ``(num_node, B)``, or
+        with ``targets`` int64 ``(B, K)`` int32 ``(B, K)`` -- ``functional.hop_distance`` over ``self.relcsr``; ``num_node``
+        stands for unreachable or farther than ``num_iters``; edges of weight 0 do not exist."""
+        from . import functional
+        sources = torch.as_tensor(sources, dtype=torch.long, device=self.device).reshape(-1)
+        if targets is not None:
+            targets = torch.as_tensor(targets, dtype=torch.long, device=self.device)
+        return functional.hop_distance(self.relcsr, sources, num_iters, targets)
+
     def completion_keys(self, anchor_col):
         """Sorted DISTINCT int64 keys ``(anchor * num_relation + relation) * num_node + other`` of the triples, with
         ``anchor`` = column ``anchor_col`` of ``edge_list`` (0: head, answers "which tails complete (h, r, ?)"; 1: tail)

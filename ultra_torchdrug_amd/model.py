@@ -645,6 +645,13 @@ class TransferNBFNet(nn.Module):
                 and mlp.layers[1].out_features == 1 and mlp.activation is torch.nn.functional.relu
                 and not mlp.short_cut)
 
+    def _get_shortest_distance(self, graph, h_index, num_iters=100):
+        """``model.py:302-314``: int32 ``(num_node, len(h_index))`` hop distances from every ``h_index`` along the edges of
+        ``graph``, ``graph.num_node`` where a node is unreachable or farther than ``num_iters`` -- one multi-source BFS
+        (``functional.hop_distance``) where the reference runs ``num_iters`` passes of gather + ``scatter_min``.  (Like the
+        reference, nothing in ``forward`` calls it: ``dist_embed`` stays unused.)"""
+        return graph.hop_distance(torch.as_tensor(h_index, device=graph.device).reshape(-1), num_iters)
+
     def _undirected(self, graph):
         """``graph.undirected(add_inverse=True)`` (model.py:166), memoised on the graph object: the reference
         re-materialises (and torchdrug re-sorts) the doubled edge list on every call; evaluation reuses one

@@ -249,6 +249,11 @@ class RelNBFNet(nn.Module):
     def construct_relation_graph(self, graph):
         return construct_relation_graph(graph)
 
+    def _get_shortest_distance(self, graph, num_iters=100):
+        """``rel_model.py:77-89``: int32 ``(num_node, num_node)`` hop distances between all nodes of ``graph`` (column ``b`` =
+        distances from node ``b``), ``graph.num_node`` for unreachable or farther than ``num_iters``."""
+        return graph.hop_distance(torch.arange(graph.num_node, device=graph.device), num_iters)
+
     def forward(self, graph, input, r_idx, all_loss=None, metric=None):
         assert input is None                                    # rel_model.py:21
         x = self.model(graph, h_index=r_idx)

@@ -440,27 +440,73 @@ class KnowledgeGraphCompletion(nn.Module):
             filtered = self.filtered_ranking
         return (graph.completion_keys(1 if head else 0) if filtered else None), max(graph.num_relation, 1), graph.num_node
 
+    def message_graph(self):
+        """The graph that carries the messages of the current context: the fact graph with inverse edges, the object
+        ``TransferNBFNet._undirected`` memoises (nothing removed)."""
+        return self.model._undirected(self.fact_graph)
+
     @torch.no_grad()
-    def answer(self, anchor, relation, k=10, head=False, filtered=None):
+    def hop_distance(self, triples, num_iters=100):
+        """Hops from ``h`` to ``t`` of every row of ``triples`` (``(n, 3)`` rows of (h, t, r)) in :meth:`message_graph`, int32
+        ``(n,)``; ``num_entity`` where ``t`` is unreachable or farther than ``num_iters``.  With inverse edges the graph is
+        symmetric, so the number serves the tail side and the head side of the triple alike.  A model of L layers conditions
+        the score of ``t`` on ``h`` only when this is at most L.  One BFS source per distinct head (heads with many triples take
+        one per 64 of them) and the targets form of ``functional.hop_distance``: no ``(N, B)`` matrix."""
+        from . import functional
+        graph = self.message_graph()
+        triples = torch.as_tensor(triples, device=graph.device)
+        n = len(triples)
+        if n == 0:
+            return torch.zeros(0, dtype=torch.int32, device=graph.device)
+        order = torch.argsort(triples[:, 0], stable=True)
+        h, t = triples[order, 0], triples[order, 1]
+        heads, count = torch.unique_consecutive(h, return_counts=True)
+        width = min(int(count.max()), 64)
+        at = torch.arange(n, device=h.device) - torch.repeat_interleave(count.cumsum(0) - count, count)   # place in its head's run
+        rows = (count + width - 1) // width
+        row = torch.repeat_interleave(rows.cumsum(0) - rows, count) + at // width
+        col = at % width
+        sources = torch.repeat_interleave(heads, rows)
+        targets = sources[:, None].repeat(1, width)                  # unused slots ask for the source itself
+        targets[row, col] = t
+        found = functional.hop_distance(graph.relcsr, sources, num_iters, targets)
+        out = torch.empty(n, dtype=torch.int32, device=h.device)
+        out[order] = found[row, col]
+        return out
+
+    @torch.no_grad()
+    def answer_hops(self, anchor, entities):
+        """Hops from ``anchor[q]`` to every ``entities[q, j]`` in :meth:`message_graph` within the model's number of layers,
+        int32 ``(Q, k)``: ``num_entity`` for farther or unreachable, ``-1`` where the slot holds no entity (``-1``)."""
+        from . import functional
+        found = functional.hop_distance(self.message_graph().relcsr, anchor, len(self.model.layers), entities.clamp(min=0))
+        return torch.where(entities < 0, torch.full_like(found, -1), found)
+
+    @torch.no_grad()
+    def answer(self, anchor, relation, k=10, head=False, filtered=None, with_hops=False):
         """Which entities complete ``(anchor, relation, ?)`` -- or, with ``head=True``, ``(?, relation, anchor)`` -- best first (an
         addition of this package; the reference's user masks the ``predict`` scores and calls ``torch.topk``).  ``anchor`` /
         ``relation``: int64 ``(Q,)``, ``relation`` in ``[0, R)``.  Entities that complete the query in the current context's
         filter graph are left out (``filtered``, default ``self.filtered_ranking``).  Returns ``(entities int64 (Q, k), scores
         fp32 (Q, k))`` in the order ``functional.topk_keys`` defines (score descending, ties by ascending entity, NaN last); a
-        query with fewer than ``k`` candidates ends in ``-1`` / ``-inf``."""
+        query with fewer than ``k`` candidates ends in ``-1`` / ``-inf``.  ``with_hops``: a third result, :meth:`answer_hops`
+        of the returned entities -- an answer farther from its anchor than the model has layers was scored without the anchor."""
         anchor, q_rel, base = self.answer_queries(anchor, relation, head)
         keys, n_rel, n_node = self.answer_filter(head, filtered)
         k = int(k)
         if not 1 <= k <= TOPK_MAX:
             raise ValueError("answer: 1 to %d answers per query, got %d" % (TOPK_MAX, k))
         if len(anchor) == 0:
-            return anchor.new_zeros(0, k), torch.zeros(0, k, device=anchor.device)
+            empty = anchor.new_zeros(0, k), torch.zeros(0, k, device=anchor.device)
+            return empty + (torch.zeros(0, k, dtype=torch.int32, device=anchor.device),) if with_hops else empty
         pred = self.model.score_all_entities(self.fact_graph, self.relation_representations(base), anchor, q_rel)
         if pred is None:                          # no fused score head: predict on triples whose other entity is 0
             zero = torch.zeros_like(anchor)
             batch = torch.stack([zero, anchor, base] if head else [anchor, zero, base], dim=1)
             pred = self.predict(batch)[:, 1 if head else 0]
         value, index = backend.get().topk_keys(pred, k, keys, anchor, base, n_rel, n_node)
+        if with_hops:
+            return index, value, self.answer_hops(anchor, index)
         return index, value
 
     def training_indices(self, batch):
