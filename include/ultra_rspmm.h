@@ -791,6 +791,27 @@ int ultra_edge_removal_marks(const ultra_segments *fwd, const ultra_segments *by
                              float *w_fwd, float *w_src, float *w_rel, int64_t slack, uint32_t *words_fwd, uint32_t *words_src,
                              uint32_t *words_rel, int64_t n_node, void *stream);
 
+/* ultra_pair_removal: remove_easy_edges with remove_one_hop = True (ultra/model.py:57-74) as edge weights, on the three plans of
+ * the graph WITH inverse edges.  The weight arrays (n_edges + slack floats each) become the plans' own weights (1.0 when NULL,
+ * 1.0 in the slack) except 0.0 at EVERY edge u -> v, whatever its relation, with (u, v) == (h[i], t[i]) or (u, v) == (t[i], h[i])
+ * for some i < n_pattern.  On such a graph an edge (a, b, r) and its inverse (b, a, r + R) always go together, as in the reference,
+ * which matches the base edges in both orders and then adds the inverses.  Pairs that no edge connects (most negatives of a batch)
+ * change nothing, a pair listed several times is removed once, h[i] == t[i] removes the self loops of that node, and an id outside
+ * [0, n_node) matches nothing and writes nothing.
+ * words_fwd / words_src / words_rel: optional marked word copies for ultra_segments.packed_dead, with the meaning and the
+ * preconditions of ultra_edge_removal_marks (when any of them is given: no plan has weights of its own, slack <= 16, and the
+ * plans that get one leave bit 31 of their packed words free for ids below n_node; ULTRA_ERR_BAD_SHAPE otherwise).  All three
+ * NULL: weights only, the plans may carry weights.
+ * The lookup: in the forward plan, sorted by (dst, src, rel), the edges of an ordered pair are one contiguous run (0 .. n_rel
+ * edges); in the d_input plan, sorted by (src, dst, rel), a run of the same length in the same relation order; in the
+ * d_relation plan, sorted by (rel, dst, src), one point lookup per edge with the relation read from the forward run.  One lane
+ * searches each of the 2 * n_pattern ordered pairs and a wave walks each run that exists; every write is a store of 0.0f or
+ * an atomicOr of bit 31, so the result does not depend on how the work is split.  The fill launch(es) of the triple entries +
+ * one search launch; only enqueues work: no allocation, no host synchronisation, capturable. */
+int ultra_pair_removal(const ultra_segments *fwd, const ultra_segments *by_src, const ultra_segments *by_rel, const int64_t *h,
+                       const int64_t *t, int64_t n_pattern, float *w_fwd, float *w_src, float *w_rel, int64_t slack,
+                       uint32_t *words_fwd, uint32_t *words_src, uint32_t *words_rel, int64_t n_node, void *stream);
+
 
 /*
  * Native plan builder (rocPRIM radix sort + scans), replaces sparse.coalesce() + coo2csr that torchdrug runs inside

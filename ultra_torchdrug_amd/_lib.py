@@ -120,6 +120,7 @@ SIGNATURES = {
     "ultra_nonfinite_commit": (i32, [vp, i32, vp]),
     "ultra_edge_removal_weights": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
     "ultra_edge_removal_marks": (i32, [seg, seg, seg, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "ultra_pair_removal": (i32, [seg, seg, seg, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     "ultra_prepare_queries": (i32, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ultra_relation_stack_inputs": (i32, [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp]),
     "ultra_statistics_blocks": (i32, [i64]),

@@ -11,6 +11,8 @@ optional functions: a backend is an object with this complete interface
     filtered_rank, filtered_rank_keys, strict_negatives, statistics, bce_adversarial_loss, candidate_tiles, candidate_rows,
     score_candidates_supported, score_candidates
     filter_counts, sampled_rank_keys   (reached ONLY when the task has a sampled metric ``hits@K_N`` or ``toy_eval``)
+    remove_pairs                       (reached ONLY when ``model.remove_one_hop``, on device graphs of a backend that accepts
+                                        the index tensors; every other backend keeps the mask route of ``easy_edge_mask``)
     topk_keys                          (``task.answer`` / ``engine.answer``; device tensors run ``ultra_topk_keys``, CPU tensors
                                         the dense path of the same definition)
 

@@ -410,6 +410,76 @@ __global__ __launch_bounds__(256) void edge_removal_kernel(const RemovalParams p
     if (p.m_rel != nullptr) atomicOr(p.m_rel + e, 0x80000000u);
 }
 
+// The one-hop rule (ultra/model.py:57-74 with remove_one_hop = True): EVERY edge between the heads and the tails of a batch goes,
+// in either direction and under any relation.  An ordered pair (src, dst) is a range lookup where a triple is a point lookup:
+//   forward plan    (dst, src, rel): its edges are ONE run, found by the lower bound of (dst, src, 0);
+//   d_input plan    (src, dst, rel): a run of the same length in the same relation order, from the lower bound of (src, dst, 0);
+//   d_relation plan (rel, dst, src): one point lookup per edge of the run, with the relation read from the forward run.
+// One lane searches one ordered pair -- most pairs of a batch are negatives that no edge connects and end there; the runs that
+// exist (0 .. 2R edges each) are then walked by the whole wave, one after the other, lane l taking the edges l, l + 64, ...
+// Every write is a store of 0.0f or an atomicOr of bit 31: a pair listed twice, (u, v) beside (v, u) with u == v, or another
+// split of the work over lanes and waves write the same words with the same values.
+struct PairRemovalParams {
+    const int32_t *f_row, *f_a, *f_rel;          // forward:    (dst, src, rel)
+    const int32_t *s_row, *s_a, *s_rel;          // d_input:    (src, dst, rel)
+    const int32_t *r_row, *r_b, *r_a;            // d_relation: (rel, dst, src)
+    long long n_edges;
+    const int64_t *h, *t;                        // [n_pattern] node pairs; both orders are removed
+    long long n_pattern;
+    long long n_node;                            // ids outside [0, n_node) match nothing
+    float *w_fwd, *w_src, *w_rel;                // [n_edges + slack], pre-filled with the plans' own weights
+    uint32_t *m_fwd, *m_src, *m_rel;             // optional marked copies of the plans' packed words (bit 31 = removed), or NULL
+};
+
+__global__ __launch_bounds__(256) void pair_removal_kernel(const PairRemovalParams p) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const long long E = p.n_edges;                                    // < 2^31 (check_segments): positions fit an int
+    int src = 0, dst = 0, f0 = 0, s0 = 0;
+    bool found = false;
+    if (i < 2 * p.n_pattern) {
+        const long long k = i >> 1;
+        const long long a = (i & 1) ? p.t[k] : p.h[k], b = (i & 1) ? p.h[k] : p.t[k];
+        if (a >= 0 && a < p.n_node && b >= 0 && b < p.n_node) {
+            src = (int)a;
+            dst = (int)b;
+            const long long e = lower_bound_3(p.f_row, p.f_a, p.f_rel, E, dst, src, 0);     // relations are >= 0: the run's start
+            found = e < E && p.f_row[e] == dst && p.f_a[e] == src;
+            if (found) {
+                f0 = (int)e;
+                s0 = (int)lower_bound_3(p.s_row, p.s_a, p.s_rel, E, src, dst, 0);
+            }
+        }
+    }
+    // (no lane has left: the shuffles below read every lane of the wave)
+    unsigned long long todo = __ballot(found ? 1 : 0);
+    while (todo != 0ull) {
+        const int owner = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const int u = __shfl(src, owner, 64), v = __shfl(dst, owner, 64);
+        const long long fb = __shfl(f0, owner, 64), sb = __shfl(s0, owner, 64);
+        for (long long j = lane;; j += 64) {
+            const long long ef = fb + j;
+            if (ef >= E || p.f_row[ef] != v || p.f_a[ef] != u) break;                       // past the run
+            const int rel = p.f_rel[ef];
+            p.w_fwd[ef] = 0.0f;
+            if (p.m_fwd != nullptr) atomicOr(p.m_fwd + ef, 0x80000000u);
+            // the same edge in the other two orders; the comparisons hold for plans of one edge set and keep every write inside
+            // the arrays for any others
+            const long long es = sb + j;
+            if (es < E && p.s_row[es] == u && p.s_a[es] == v && p.s_rel[es] == rel) {
+                p.w_src[es] = 0.0f;
+                if (p.m_src != nullptr) atomicOr(p.m_src + es, 0x80000000u);
+            }
+            const long long er = lower_bound_3(p.r_row, p.r_b, p.r_a, E, rel, v, u);
+            if (er < E && p.r_row[er] == rel && p.r_b[er] == v && p.r_a[er] == u) {
+                p.w_rel[er] = 0.0f;
+                if (p.m_rel != nullptr) atomicOr(p.m_rel + er, 0x80000000u);
+            }
+        }
+    }
+}
+
 // the weight arrays (ones) and the word copies of the three plans in one launch: blockIdx.y picks the array
 struct RemovalFillParams {
     float *w[3];
@@ -631,6 +701,65 @@ int ultra_edge_removal_marks(const ultra_segments *fwd, const ultra_segments *by
         p.w_fwd = w_fwd; p.w_src = w_src; p.w_rel = w_rel;
         p.m_fwd = words_fwd; p.m_src = words_src; p.m_rel = words_rel;
         hipLaunchKernelGGL(edge_removal_kernel, dim3((unsigned)((2 * n_pattern + 255) / 256)), dim3(256), 0, s, p);
+    }
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+int ultra_pair_removal(const ultra_segments *fwd, const ultra_segments *by_src, const ultra_segments *by_rel, const int64_t *h,
+                       const int64_t *t, int64_t n_pattern, float *w_fwd, float *w_src, float *w_rel, int64_t slack,
+                       uint32_t *words_fwd, uint32_t *words_src, uint32_t *words_rel, int64_t n_node, void *stream) {
+    int rc = check_segments(fwd);
+    if (!rc) rc = check_segments(by_src);
+    if (!rc) rc = check_segments(by_rel);
+    if (rc) return rc;
+    if (fwd->n_edges != by_src->n_edges || fwd->n_edges != by_rel->n_edges || n_pattern < 0 || slack < 0 || n_node <= 0)
+        return ULTRA_ERR_BAD_SHAPE;
+    if (n_pattern > (1LL << 37)) return ULTRA_ERR_BAD_SHAPE;                           // grid.x: one lane per ordered pair
+    if (w_fwd == nullptr || w_src == nullptr || w_rel == nullptr) return ULTRA_ERR_NULL_POINTER;
+    if (n_pattern > 0 && (h == nullptr || t == nullptr)) return ULTRA_ERR_NULL_POINTER;
+    if (fwd->n_edges > 0 && by_rel->node_b == nullptr) return ULTRA_ERR_NULL_POINTER;
+    const ultra_segments *plans[3] = {fwd, by_src, by_rel};
+    uint32_t *marks[3] = {words_fwd, words_src, words_rel};
+    const bool marked = words_fwd != nullptr || words_src != nullptr || words_rel != nullptr;
+    if (marked) {                                                                      // as ultra_edge_removal_marks
+        if (slack > 16) return ULTRA_ERR_BAD_SHAPE;
+        for (int k = 0; k < 3; ++k) {
+            if (plans[k]->weight != nullptr) return ULTRA_ERR_BAD_SHAPE;               // ones only: the marks replace the weights
+            if (marks[k] == nullptr) continue;
+            if (plans[k]->packed == nullptr || plans[k]->packed_src_shift >= 31 ||
+                ((unsigned long long)(n_node - 1) >> (31 - plans[k]->packed_src_shift)) != 0ull)
+                return ULTRA_ERR_BAD_SHAPE;
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long E = fwd->n_edges, total = E + slack;
+    if (total > 0) {
+        const unsigned blocks = (unsigned)((total + 255) / 256);
+        if (marked) {
+            RemovalFillParams f;
+            f.w[0] = w_fwd; f.w[1] = w_src; f.w[2] = w_rel;
+            for (int k = 0; k < 3; ++k) { f.m[k] = marks[k]; f.words[k] = plans[k]->packed; }
+            f.n_total = total;
+            hipLaunchKernelGGL(removal_fill_kernel, dim3(blocks, 3), dim3(256), 0, s, f);
+        } else {
+            hipLaunchKernelGGL(fill_weights_kernel, dim3(blocks), dim3(256), 0, s, fwd->weight, w_fwd, E, total);
+            hipLaunchKernelGGL(fill_weights_kernel, dim3(blocks), dim3(256), 0, s, by_src->weight, w_src, E, total);
+            hipLaunchKernelGGL(fill_weights_kernel, dim3(blocks), dim3(256), 0, s, by_rel->weight, w_rel, E, total);
+        }
+    }
+    if (n_pattern > 0 && E > 0) {
+        PairRemovalParams p;
+        p.f_row = fwd->row; p.f_a = fwd->node_a; p.f_rel = fwd->rel;
+        p.s_row = by_src->row; p.s_a = by_src->node_a; p.s_rel = by_src->rel;
+        p.r_row = by_rel->row; p.r_b = by_rel->node_b; p.r_a = by_rel->node_a;
+        p.n_edges = E;
+        p.h = h; p.t = t;
+        p.n_pattern = n_pattern;
+        p.n_node = n_node;
+        p.w_fwd = w_fwd; p.w_src = w_src; p.w_rel = w_rel;
+        p.m_fwd = words_fwd; p.m_src = words_src; p.m_rel = words_rel;
+        hipLaunchKernelGGL(pair_removal_kernel, dim3((unsigned)((2 * n_pattern + 255) / 256)), dim3(256), 0, s, p);
     }
     HIP_TRY(hipGetLastError());
     return ULTRA_OK;

@@ -324,10 +324,11 @@ class GraphedTrainStep:
     sampling, removal of the batch's own edges, forward, backward.  A step is ~800 launches, most of them tiny, and
     their host-side issue cost exceeds the GPU time of the kernels.  Nothing in the step has a data-dependent shape any
     more: the negatives come from the sorted completion keys (``ultra_strict_negative``) and the edge removal from a
-    binary search in the plans (``ultra_edge_removal_weights``), where the reference builds ``(B / 2, N)`` masks, calls
-    ``nonzero`` and re-sorts a new graph (task.py:102-118, model.py:57-74).  The optimizer step follows the replay
-    eagerly.  Models the native removal does not cover (min / max / PNA aggregation, ``remove_one_hop``) keep eager
-    steps: use :func:`train_step`.
+    binary search in the plans (``ultra_edge_removal_weights``; with ``remove_one_hop=True`` the range lookup of
+    ``ultra_pair_removal``), where the reference builds ``(B / 2, N)`` masks, calls ``nonzero`` and re-sorts a new graph
+    (task.py:102-118, model.py:57-74).  The optimizer step follows the replay eagerly.  Models the native removal does not
+    cover -- mean / min / max / PNA aggregation, rotate messages, under either removal rule -- keep eager steps: use
+    :func:`train_step`.
 
     Without a reducer (one rank): ONE graph.  With a :class:`GradientReducer` the gradient all-reduce goes one of three ways
     (``mode`` tells which is active):
@@ -371,9 +372,10 @@ class GraphedTrainStep:
                              "with reduce_in_graph=True the all-reduce runs inside the backward of the captured graph -- "
                              "use the phased or the after mode with a guard")
         model = task.model
-        if model.remove_one_hop or not model._removal_by_zero_weight(sums_only=True):
-            raise ValueError("GraphedTrainStep needs summed messages and remove_one_hop=False (the edge removal that can "
-                             "be captured); use engine.train_step for this model")
+        if not model._removal_by_zero_weight(sums_only=True):
+            raise ValueError("GraphedTrainStep needs summed messages (sum aggregation of DistMult / TransE messages: the edge "
+                             "removal that can be captured, under either rule of remove_one_hop); use engine.train_step for "
+                             "this model")
         self.task, self.optimizer, self.reducer, self.guard = task, optimizer, reducer, guard
         # the captures' verification replays the guard's nodes: the record is put back afterwards as it is now
         guard_record = None if guard is None else guard.record.clone()

@@ -1027,6 +1027,23 @@ def remove_triples(graph, h, t, r, n_base_rel):
     return graph.without_triples(h, t, r, n_base_rel)
 
 
+def remove_pairs(graph, h, t):
+    """``graph`` (with inverse edges) minus EVERY edge between ``h[i]`` and ``t[i]`` -- either direction, any relation --, as zero
+    weights on its cached plans: ``remove_easy_edges`` with ``remove_one_hop=True`` (``ultra/model.py:57-74``) for summed
+    messages, natively and capturable (``ultra_pair_removal``).  Ids outside ``[0, num_node)`` match nothing."""
+    if not graph.edge_list.is_cuda:
+        # host graphs: the same zero weights from sorted pair keys (no device plans to patch)
+        n = graph.num_node
+        h, t = h.reshape(-1), t.reshape(-1)
+        ok = (h >= 0) & (h < n) & (t >= 0) & (t < n)
+        h, t = h[ok], t[ok]
+        gone = torch.cat([h * n + t, t * n + h])
+        e = graph.edge_list
+        keep = ~torch.isin(e[:, 0] * n + e[:, 1], gone)
+        return graph.reweighted(graph.edge_weight * keep)
+    return graph.without_pairs(h, t)
+
+
 def filtered_rank_keys(pred, target, keys, anchor, rel, n_rel, n_node=None):
     """Filtered ranks of one prediction side without filter lists or masks: ``pred`` fp32 ``(B, N)`` (a strided view of
     the ``(B, 2, N)`` scores is fine), ``target`` / ``anchor`` / ``rel`` int64 ``(B,)``; ``keys``: the graph's sorted

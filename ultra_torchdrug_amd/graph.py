@@ -139,6 +139,19 @@ class Graph:
         g._relcsr = self.relcsr.with_removed_edges(h, t, r, n_base_rel)
         return g
 
+    def without_pairs(self, h, t):
+        """This graph (one WITH inverse edges) minus every edge between ``h[i]`` and ``t[i]``, in either direction and under
+        any relation, as zero weights on the shared plans (``RelCSR.with_removed_pairs``): what ``remove_easy_edges`` with
+        ``remove_one_hop=True`` + ``undirected`` give (``ultra/model.py:57-74,166``) for summed messages.  As with
+        :meth:`without_triples`, only ``relcsr`` of the result reflects the removal."""
+        g = Graph.__new__(Graph)
+        g.edge_list, g.edge_weight = self.edge_list, self.edge_weight
+        g.num_node, g.num_relation = self.num_node, self.num_relation
+        g.requires_grad, g._adjacency, g._match_index = False, None, self._match_index
+        g._completion = getattr(self, "_completion", None)
+        g._relcsr = self.relcsr.with_removed_pairs(h, t)
+        return g
+
     def hop_distance(self, sources, num_iters=100, targets=None):
         """Hop distances along the edges (``node_in -> node_out``) from ``sources`` int64 ``(B,)``: int32 ``(num_node, B)``, or
         with ``targets`` int64 ``(B, K)`` int32 ``(B, K)`` -- ``functional.hop_distance`` over ``self.relcsr``; ``num_node``

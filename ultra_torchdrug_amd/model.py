@@ -491,7 +491,7 @@ class TransferNBFNet(nn.Module):
         """model.py:145-194: scores of shape ``h_index.shape``.  ``all_entities=True`` is the caller's promise that
         every row of the corrupted side lists ALL entities in order (full-batch evaluation, task.py:249-259); the
         tail gather is then the identity and the score head runs as one fused kernel."""
-        keep, removal = None, None
+        keep, removal, pairs = None, None, None
         if self.check_indices:
             # BEFORE anything consumes the ids (edge removal, negative flip, the fused kernels index with them without a bounds
             # check of their own -- frontier: src_ptr[h]; candidate tiles: an LDS bitmap at (t, b); score rows: hidden[t, b]): an id
@@ -512,10 +512,13 @@ class TransferNBFNet(nn.Module):
             # training: the batch's own positive edges must not carry messages (model.py:146-147).  The reference
             # builds (and torchdrug re-sorts) a new graph every step; here the cached plans of the full graph are
             # reused and the removed edges get weight 0 for this step -- identical sums, no sort.
-            if (graph.num_relation and r_index is not None and not self.remove_one_hop
-                    and self._removal_by_zero_weight(sums_only=True)):
+            native = graph.num_relation and r_index is not None and self._removal_by_zero_weight(sums_only=True)
+            if native and not self.remove_one_hop:
                 # one native call on the graph with inverse edges (below): no match(), no host synchronisation
                 removal = (h_index, t_index, r_index)
+            elif native and graph.edge_list.is_cuda and backend.get().accepts(h_index):
+                # the one-hop rule the same way: every edge between the heads and the tails, by a range lookup in the plans
+                pairs = (h_index, t_index)
             else:
                 keep = self.easy_edge_mask(graph, h_index, t_index, r_index)
                 if not (graph.num_relation and self._removal_by_zero_weight()):
@@ -545,6 +548,8 @@ class TransferNBFNet(nn.Module):
                 graph = graph.reweighted(graph.edge_weight * keep.repeat_interleave(2))
             if removal is not None:
                 graph = backend.get().remove_triples(graph, *removal, num_relations)
+            if pairs is not None:
+                graph = backend.get().remove_pairs(graph, *pairs)
             h_index, t_index, r_index = self.negative_sample_to_tail(h_index, t_index, r_index, num_relations)
         else:
             graph = self.as_relational_graph(graph)

@@ -666,11 +666,34 @@ class RelCSR:
         graph with inverse edges; triples that are not edges are ignored).  One native call fills the weight arrays of
         all three plans by binary search in their sorted index arrays: no ``match``, no host synchronisation, static
         shapes (capturable).  Shares every index array and schedule with this object."""
-        base = getattr(self, "_base", None) or self
-        dev = self.device
         h, t, r = (x.reshape(-1).contiguous() for x in (h, t, r))
-        E = base.n_edges
-        plans = (self.fwd, self.by_src, self.by_rel)         # their weights are the starting point
+        plans, w, marks, n_node = self._removal_buffers()
+        removal = (*[p.pointer for p in plans], h, t, r, h.numel(), int(n_base_rel), *w, PACK_SLACK)
+        if marks[0] is not None:
+            _lib.launch(self.device, "ultra_edge_removal_marks", *removal, *marks, n_node)
+        else:
+            _lib.launch(self.device, "ultra_edge_removal_weights", *removal)
+        return self._with_removal(plans, w, marks)
+
+    def with_removed_pairs(self, h, t):
+        """RelCSR over the same edge set in which EVERY edge between ``h[i]`` and ``t[i]`` -- either direction, any relation --
+        carries weight 0: ``remove_easy_edges`` with ``remove_one_hop=True`` (``ultra/model.py:57-74``) on the graph with
+        inverse edges.  Pairs that no edge connects are ignored.  One native call (``ultra_pair_removal``): a range lookup
+        per ordered pair where :meth:`with_removed_edges` looks up points; the same marks / weights decision, no ``match``,
+        no host synchronisation, static shapes (capturable).  Shares every index array and schedule with this object."""
+        h, t = (x.reshape(-1).contiguous() for x in (h, t))
+        if h.numel() != t.numel() or h.dtype != torch.int64 or t.dtype != torch.int64:
+            raise ValueError("with_removed_pairs: h and t must be int64 tensors with the same number of elements")
+        plans, w, marks, n_node = self._removal_buffers()
+        _lib.launch(self.device, "ultra_pair_removal", *[p.pointer for p in plans], h, t, h.numel(), *w, PACK_SLACK, *marks, n_node)
+        return self._with_removal(plans, w, marks)
+
+    def _removal_buffers(self):
+        """``(plans, w, marks, n_node)`` of a per-step removal: the three plans whose weights are the starting point, a weight
+        array for each and -- the marks / weights decision -- a word array for each or three ``None``."""
+        dev = self.device
+        E = (getattr(self, "_base", None) or self).n_edges
+        plans = (self.fwd, self.by_src, self.by_rel)
         w = [torch.empty(E + PACK_SLACK, dtype=torch.float32, device=dev) for _ in range(3)]
         # a graph of unit weights whose packed words leave bit 31 free: the removed edges ALSO as marks in copies of the words, on
         # which the sum / mul kernels run their unit-weight form (csrc/quad.inc DEAD) instead of loading a weight per edge
@@ -680,11 +703,12 @@ class RelCSR:
                 all(p.weight is None and p.packed is not None and p.packed_src_shift < 31
                     and (n_node - 1) >> (31 - p.packed_src_shift) == 0 for p in plans)):
             marks = [torch.empty(E + PACK_SLACK, dtype=torch.int32, device=dev) for _ in range(3)]
-        removal = (*[p.pointer for p in plans], h, t, r, h.numel(), int(n_base_rel), *w, PACK_SLACK)
-        if marks[0] is not None:
-            _lib.launch(dev, "ultra_edge_removal_marks", *removal, *marks, n_node)
-        else:
-            _lib.launch(dev, "ultra_edge_removal_weights", *removal)
+        return plans, w, marks, n_node
+
+    def _with_removal(self, plans, w, marks):
+        """The RelCSR that carries the filled weight arrays ``w`` (and word copies ``marks``) on shallow copies of ``plans``."""
+        base = getattr(self, "_base", None) or self
+        E = base.n_edges
         other = RelCSR.__new__(RelCSR)
         other.shape, other._opts = self.shape, self._opts
         other.chunk_edges, other.piece_len = self.chunk_edges, self.piece_len

@@ -744,14 +744,16 @@ class KnowledgeGraphCompletion(nn.Module):
         return all_loss, metric
 
 
-def build_ultra(num_relation, input_dim=64, hidden_dims=(64,) * 6, rel_hidden=64, rel_layers=6, **task_kwargs):
+def build_ultra(num_relation, input_dim=64, hidden_dims=(64,) * 6, rel_hidden=64, rel_layers=6, remove_one_hop=False,
+                **task_kwargs):
     """The shipped architecture: ``config/transductive/inference.yaml:8-39`` (6 x 64d, distmult, sum, shortcut,
-    layer norm, projected relations; relation model 6 x 64d)."""
+    layer norm, projected relations; relation model 6 x 64d).  ``remove_one_hop``: the entity model's edge-removal rule in
+    training (``ultra/model.py:57-74``); every other keyword goes to the task."""
     from .model import TransferNBFNet
     from .rel_model import RelationModelList
     model = TransferNBFNet(input_dim=input_dim, hidden_dims=list(hidden_dims), num_relation=num_relation,
                            message_func="distmult", aggregate_func="sum", short_cut=True, layer_norm=True,
-                           project=True, mod=True, remove_one_hop=False)
+                           project=True, mod=True, remove_one_hop=bool(remove_one_hop))
     rel_models = RelationModelList(num_rel_models=1, num_relation=2 * num_relation,
                                    rel_model=dict(class_str="RelNBFNet", input_dim=input_dim, input_type="ones",
                                                   num_layers=rel_layers, hidden=rel_hidden))
