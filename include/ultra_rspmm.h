@@ -453,6 +453,30 @@ int ultra_hop_distance(const int32_t *row_ptr, const int32_t *src, const float *
 
 
 /*
+ * The boundary condition of a relation projection whose source is a fuzzy SET of entities (an addition of this package for
+ * multi-hop logical queries; the reference's one-hot boundary, /root/reference/ultra/model.py:108-109, is
+ * the set {anchor} with membership 1):
+ *   member   fp32 [n_query] rows of n_node memberships, row q at member + q * row_stride (row_stride >= n_node)
+ *   floor    fp32 [n_query] or NULL     the cut of each row
+ *   query    fp32 [n_query][dim]        the query relation's representation
+ *   boundary fp32 [n_node][n_query][dim], written completely
+ *   count    int32 [n_query] or NULL    the number of kept entities per row
+ * Definition: entity v is KEPT for query q iff m = member[q * row_stride + v] satisfies m > 0 and (floor == NULL or
+ * m >= floor[q]); a NaN membership is never kept, and under a NaN floor nothing is.  Kept: boundary[v][q][d] = m * query[q][d],
+ * ONE fp32 multiply.  Not kept: the dim floats are +0.0 bits whatever query holds (a zero row stays zero under a non-finite
+ * query, as the rows scatter_add leaves alone do).  Ties at the floor are all kept: the set never depends on the entity order.
+ * count[q] is zeroed by a kernel of the entry on the stream (not a memset: see ultra_rspmm_frontier_f32) and summed with integer
+ * atomics, one per (tile of 64 nodes, query) that kept anything: exact under every schedule.
+ * The entry only enqueues -- no allocation, no host read, capturable.  All offsets are 64-bit (n_node * n_query * dim may pass
+ * 2^31).  Rows are written 16 bytes per lane when dim % 4 == 0 and query / boundary are 16-byte aligned, 4 bytes per lane
+ * otherwise: the same bits.  ULTRA_ERR_BAD_SHAPE for n_query < 1, n_node < 1, dim < 1, row_stride < n_node or a NULL member /
+ * query / boundary.  Bytes moved at least: 4 * (n_query * n_node + n_node * n_query * dim).
+ */
+int ultra_set_boundary_f32(const float *member, int64_t n_query, int64_t n_node, int64_t row_stride, const float *floor,
+                           const float *query, int64_t dim, float *boundary, int32_t *count, void *stream);
+
+
+/*
  * Dense epilogue of one Bellman-Ford layer, fused (dim must be 64, the shipped architecture):
  *     out = [input +]  relu?( LayerNorm?( Linear( cat[input, update] ) ) )
  * replaces GeneralizedRelationalConv*.combine (/root/reference/ultra/layer.py:184-190, :386-392: cat, nn.Linear,

@@ -15,6 +15,9 @@ optional functions: a backend is an object with this complete interface
                                         the index tensors; every other backend keeps the mask route of ``easy_edge_mask``)
     topk_keys                          (``task.answer`` / ``engine.answer``; device tensors run ``ultra_topk_keys``, CPU tensors
                                         the dense path of the same definition)
+    set_boundary                       (reached ONLY from ``project``, on tensors the backend accepts; a backend whose
+                                        ``accepts()`` is false gets ``functional.dense_set_boundary``, the same definition in
+                                        torch ops)
 
 The parity tests install a second implementation of the same interface (``tests/oracle_ops.py``: the CPU oracle
 behind every operator) with :func:`use`, so that the SAME model code yields the oracle-side numbers; nothing under

@@ -863,6 +863,29 @@ def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None
     return torch.cat(entities), torch.cat(scores)
 
 
+@torch.no_grad()
+def answer_query(task, structure, anchors, relations, k=10, batch_size=16, **cut):
+    """``task.answer_query`` over any number of queries of ONE structure: the ids are parsed and range-checked once, then the
+    queries run ``batch_size`` at a time (the last chunk is ragged: nothing is padded, a set projection costs what its queries
+    cost) and everything runs eager -- a whole query is not captured in a hipGraph.  ``cut``: ``threshold`` / ``max_sources`` of
+    ``task.project``.  Queries are independent columns of every kernel on the route, so each chunk equals ``task.answer_query``
+    of the same rows.  Returns ``(entities int64 (Q, k), membership fp32 (Q, k))``."""
+    unknown = set(cut) - {"threshold", "max_sources"}
+    if unknown:
+        raise TypeError("answer_query: unknown arguments %s" % sorted(unknown))
+    threshold, max_sources = cut.get("threshold", 0.0), cut.get("max_sources")
+    task._check_cut(max_sources)
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("answer_query: batch_size must be positive, got %d" % batch_size)
+    tree, anchors, relations = task.query_inputs(structure, anchors, relations)
+    parts = [task._answer_query_checked(tree, anchors[i:i + batch_size], relations[i:i + batch_size], k, threshold, max_sources)
+             for i in range(0, len(anchors), batch_size)]
+    if not parts:
+        return task._answer_query_checked(tree, anchors, relations, k, threshold, max_sources)
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
 # engine.evaluate scores distinct queries instead of triples when the shard holds at most this share of distinct queries
 UNIQUE_QUERY_GAIN = 0.9
 

@@ -1238,6 +1238,54 @@ def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
     return value, index
 
 
+def dense_set_boundary(member, query, floor=None, with_count=False):
+    """:func:`set_boundary` in torch ops, in the dtype of ``query`` (the host twin, and the form the fp64 ATen definition of a
+    projection uses): entity ``v`` is kept for query ``q`` iff ``member[q, v] > 0`` and ``member[q, v] >= floor[q]`` (a NaN is
+    never kept); kept rows hold ``member[q, v] * query[q]``, every other row ``+0.0`` whatever ``query`` holds."""
+    m = member.to(query.dtype)
+    keep = m > 0
+    if floor is not None:
+        keep = keep & (m >= floor.to(query.dtype).unsqueeze(-1))
+    keep_t = keep.t().unsqueeze(-1)                                      # (N, Q, 1)
+    boundary = torch.where(keep_t, m.t().unsqueeze(-1) * query.unsqueeze(0), query.new_zeros(()))
+    return (boundary, keep.sum(dim=1).to(torch.int32)) if with_count else boundary
+
+
+def set_boundary(member, query, floor=None, with_count=False):
+    """The boundary condition of a projection from fuzzy entity SETS (``ultra_set_boundary_f32``, the contract is in
+    ``include/ultra_rspmm.h``): ``member`` fp32 ``(Q, N)`` memberships, ``query`` fp32 ``(Q, D)``, ``floor`` fp32 ``(Q,)`` or
+    ``None``.  Entity ``v`` is kept for query ``q`` iff ``member[q, v] > 0`` and ``member[q, v] >= floor[q]``; returns the
+    ``(N, Q, D)`` tensor ``member[q, v] * query[q]`` with ``+0.0`` rows for everything not kept, and with ``with_count`` also the
+    int32 ``(Q,)`` numbers of kept entities.  One launch that reads the memberships once and writes the boundary once; no host
+    synchronisation (capturable).  The rows of ``member`` may be strided (a view of a wider matrix) but not overlap.  CPU tensors
+    take :func:`dense_set_boundary`."""
+    if member.dim() != 2 or query.dim() != 2 or member.dtype != torch.float32 or query.dtype != torch.float32:
+        raise RuntimeError("set_boundary: member must be fp32 (Q, N) and query fp32 (Q, D), got %s %s and %s %s"
+                           % (member.dtype, tuple(member.shape), query.dtype, tuple(query.shape)))
+    n_query, n_node = member.shape
+    dim = query.shape[1]
+    if n_query < 1 or n_node < 1 or dim < 1 or query.shape[0] != n_query:
+        raise RuntimeError("set_boundary: member (Q, N) and query (Q, D) must share Q >= 1 with N, D >= 1, got %s and %s"
+                           % (tuple(member.shape), tuple(query.shape)))
+    if n_node > 1 and member.stride(1) != 1:
+        raise RuntimeError("set_boundary: the rows of member must be contiguous")
+    if n_query > 1 and member.stride(0) < n_node:
+        raise RuntimeError("set_boundary: the rows of member overlap")
+    if query.device != member.device:
+        raise RuntimeError("set_boundary: member is on %s, query on %s" % (member.device, query.device))
+    if floor is not None and (floor.dtype != torch.float32 or floor.shape != (n_query,) or floor.device != member.device):
+        raise RuntimeError("set_boundary: floor must be fp32 (%d,) on %s" % (n_query, member.device))
+    if not member.is_cuda:
+        return dense_set_boundary(member, query, floor, with_count)
+    query = query.contiguous()
+    floor = None if floor is None else floor.contiguous()
+    boundary = torch.empty(n_node, n_query, dim, dtype=torch.float32, device=member.device)
+    count = torch.empty(n_query, dtype=torch.int32, device=member.device) if with_count else None
+    _launch(member.device, "ultra_set_boundary_f32", member, n_query, n_node, member.stride(0) if n_query > 1 else n_node,
+            floor, query, dim, boundary, count)
+    return (boundary, count) if with_count else boundary
+
+
 # The divergence guard's record (``include/ultra_rspmm.h``): int32 fields ``step`` (committed steps; they are numbered from 1),
 # ``tripped_step`` (-1 until the first trip, then the number of that step; sticky), ``tripped_tensor`` (the lowest index among
 # the tensors that tripped in that step), ``pending`` (the lowest index that tripped since the last commit; GUARD_CLEAN = none).

@@ -113,27 +113,32 @@ class TransferNBFNet(nn.Module):
         relation = torch.zeros(len(edge_list), 1, dtype=torch.long, device=graph.device)
         return Graph(torch.cat([edge_list, relation], dim=-1), edge_weight, graph.num_node, 1)
 
-    def bellmanford(self, graph, h_index, r_index, separate_grad=False, want_feature=True, grad_candidates=None):
+    def bellmanford(self, graph, h_index, r_index, separate_grad=False, want_feature=True, grad_candidates=None, boundary=None):
         """model.py:101-143.  Returns ``node_feature`` of shape ``(num_node, batch, feature_dim)``; with
         ``want_feature=False`` only its two parts (``hidden``: last layer output, ``query``) -- the fused score
         kernel reads them directly and the ``cat`` of model.py:134-138 is never materialised.
         ``separate_grad=True``: every layer on its own clone of the graph with the materialised message route (model.py:120).
         ``separate_grad="native"``: every layer gets its own leaf edge-weight tensor, ``step_graph.edge_grad_leaf``
-        (:meth:`_edge_grad_graph`), for :meth:`visualize`."""
-        bs = h_index.shape[0]
+        (:meth:`_edge_grad_graph`), for :meth:`visualize`.
+        ``boundary`` (:meth:`project`): a ready ``(num_node, batch, input_dim)`` boundary condition -- a fuzzy set of sources per
+        query -- in place of the one-hot rows at ``h_index``, which is then not read (pass ``None``); the layers get it in its
+        dense form only, so no shortcut that rests on a one-row boundary is taken."""
+        bs = r_index.shape[0]
         if self.query.dim() == 2:
             query = self.query[r_index]
         else:
             # (row r_index[b] of block b; as a gather its backward is one scatter, advanced indexing's is a sort plus ~10 launches)
             query = self.query.gather(1, r_index.view(bs, 1, 1).expand(bs, 1, self.query.shape[-1])).squeeze(1)
-        index = h_index.unsqueeze(-1).expand_as(query)
-        boundary = torch.zeros(graph.num_node, *query.shape, device=query.device, dtype=query.dtype)
-        boundary.scatter_add_(0, index.unsqueeze(0), query.unsqueeze(0))
+        given = boundary is not None
+        if not given:
+            index = h_index.unsqueeze(-1).expand_as(query)
+            boundary = torch.zeros(graph.num_node, *query.shape, device=query.device, dtype=query.dtype)
+            boundary.scatter_add_(0, index.unsqueeze(0), query.unsqueeze(0))
         graph.query = query
         graph.boundary = boundary
         # the same boundary in sparse form: row h_index[b] of query block b holds query[b] (inference kernels read
-        # this instead of the dense tensor in every layer's epilogue)
-        graph.boundary_sparse = (h_index.to(torch.int32), query)
+        # this instead of the dense tensor in every layer's epilogue); a given boundary has many rows per query: dense only
+        graph.boundary_sparse = None if given else (h_index.to(torch.int32), query)
 
         graph.relation_tables = self._relation_tables(bs)
         hiddens, step_graphs = [], []
@@ -485,6 +490,47 @@ class TransferNBFNet(nn.Module):
         first, second = self.mlp.layers
         return backend.get().score_all_entities(parts["hidden"], parts["query"], first.weight, first.bias,
                                                  second.weight, second.bias)
+
+    @torch.no_grad()
+    def project(self, graph, rel_query_list, member, r_index, floor=None):
+        """One relation projection of fuzzy entity SETS (an addition of this package for multi-hop logical queries, DESIGN.md
+        section 16; the reference's model starts every Bellman-Ford at one anchor): logits ``(Q, N)`` of every entity as the tail
+        of ``r_index[q]`` over the set ``member[q]``, and the int32 ``(Q,)`` sizes of the sets after the cut.  ``member``: fp32
+        ``(Q, N)`` memberships; entity ``v`` takes part in query ``q`` iff ``member[q, v] > 0`` and ``member[q, v] >= floor[q]``
+        (``floor`` fp32 ``(Q,)`` or ``None``), and then starts from ``member[q, v] * query[q]`` where :meth:`score_all_entities`
+        starts its one anchor from ``query[q]`` (``functional.set_boundary``: one HIP launch on the device).  ``r_index``: int64
+        ``(Q,)`` in tail form, ``[0, 2R)`` over the graph with inverse edges; ``rel_query_list`` as :meth:`forward` takes it.
+        Inference only.  The layers run as in :meth:`bellmanford` from the dense boundary: the sparse first layer, the frontier
+        and the fused layers, which rest on a one-row boundary, are not taken.  A set that holds one entity with membership
+        exactly 1.0 is the boundary of :meth:`score_all_entities` for that anchor, bit for bit."""
+        if not graph.num_relation:
+            raise ValueError("project needs a relational graph")
+        self.query = rel_query_list[0]
+        for i, conv in enumerate(self.layers):
+            conv.relation = rel_query_list[i + 1] if len(rel_query_list) > 1 else rel_query_list[0]
+        graph = self._undirected(graph)
+        n_query = r_index.shape[0]
+        if self.query.dim() == 2:
+            query = self.query[r_index]
+        else:
+            query = self.query.gather(1, r_index.view(n_query, 1, 1).expand(n_query, 1, self.query.shape[-1])).squeeze(1)
+        if tuple(member.shape) != (n_query, graph.num_node):
+            raise ValueError("project: member must be (%d, %d), got %s" % (n_query, graph.num_node, tuple(member.shape)))
+        ops = backend.get()
+        if ops.accepts(member) and query.dtype == torch.float32:
+            boundary, count = ops.set_boundary(member, query, floor, with_count=True)
+        else:
+            from . import functional
+            boundary, count = functional.dense_set_boundary(member, query, floor, with_count=True)
+        parts = self.bellmanford(graph, None, r_index, want_feature=False, boundary=boundary)
+        if self._fused_head_ok(r_index, None):
+            first, second = self.mlp.layers
+            score = ops.score_all_entities(parts["hidden"], parts["query"], first.weight, first.bias, second.weight, second.bias)
+        else:
+            hidden = parts["hidden"]
+            feature = torch.cat([hidden, parts["query"].expand(hidden.shape[0], -1, -1)], dim=-1)
+            score = self.mlp(feature).squeeze(-1).t().contiguous()
+        return score, count
 
     def forward(self, graph, rel_query_list, h_index, t_index, r_index=None, all_loss=None, metric=None,
                 all_entities=False):

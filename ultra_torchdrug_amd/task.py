@@ -90,6 +90,61 @@ def dense_sampled_ranks(pred, target, mask, rand):
     return optimistic, pessimistic, torch.where(drawn, entity, free_rank)
 
 
+# The 14 query types of the BetaE / KGReasoning benchmarks in their own notation: 'e' an anchor entity, 'r' a relation
+# projection, 'n' a complement, 'u' marks a union; a tuple of branches without it is an intersection.
+_P1, _P2, _P3 = ("e", ("r",)), ("e", ("r", "r")), ("e", ("r", "r", "r"))
+_N1, _N2 = ("e", ("r", "n")), ("e", ("r", "r", "n"))
+QUERY_STRUCTURES = {
+    "1p": _P1, "2p": _P2, "3p": _P3,
+    "2i": (_P1, _P1), "3i": (_P1, _P1, _P1),
+    "ip": ((_P1, _P1), ("r",)), "pi": (_P2, _P1),
+    "2u": (_P1, _P1, ("u",)), "up": ((_P1, _P1, ("u",)), ("r",)),
+    "2in": (_P1, _N1), "3in": (_P1, _P1, _N1),
+    "inp": ((_P1, _N1), ("r",)), "pin": (_P2, _N1), "pni": (_N2, _P1),
+}
+
+
+def parse_query_structure(structure):
+    """``structure`` (a name of ``QUERY_STRUCTURES`` or a nested tuple in BetaE notation) as a tree, with the numbers of anchors
+    and relations it consumes: ``(tree, n_anchor, n_relation)``.  Grammar: ``('e', ops)`` an anchor followed by ``ops``, a
+    non-empty tuple of ``'r'`` (project) and ``'n'`` (complement) that starts with ``'r'``; ``(node, node, ...)`` the
+    intersection of two or more nodes; ``(node, node, ..., ('u',))`` their union; ``((node, ...), ops)`` ``ops`` applied to an
+    intersection or union.  Tree nodes: ``('e', ops)``, ``('i', [nodes])``, ``('u', [nodes])``, ``('ops', node, ops)``.
+    Anything else raises ``ValueError``."""
+    if isinstance(structure, str):
+        if structure not in QUERY_STRUCTURES:
+            raise ValueError("unknown query structure `%s` (have %s)" % (structure, ", ".join(QUERY_STRUCTURES)))
+        structure = QUERY_STRUCTURES[structure]
+    count = {"e": 0, "r": 0}
+
+    def is_ops(x):
+        return isinstance(x, tuple) and len(x) > 0 and all(isinstance(o, str) and o in ("r", "n") for o in x)
+
+    def node(x):
+        if not isinstance(x, tuple) or len(x) < 2:
+            raise ValueError("malformed query structure at %r" % (x,))
+        if isinstance(x[0], str):
+            if x[0] != "e" or len(x) != 2 or not is_ops(x[1]) or x[1][0] != "r":
+                raise ValueError("an anchor is ('e', ops) with ops a tuple of 'r' / 'n' that starts with 'r', got %r" % (x,))
+            count["e"] += 1
+            count["r"] += x[1].count("r")
+            return ("e", x[1])
+        if len(x) == 2 and is_ops(x[1]):
+            inner = node(x[0])
+            if inner[0] not in ("i", "u"):
+                raise ValueError("ops follow an anchor inside ('e', ops), or an intersection / union: got %r" % (x,))
+            count["r"] += x[1].count("r")
+            return ("ops", inner, x[1])
+        union = x[-1] == ("u",)
+        branches = x[:-1] if union else x
+        if len(branches) < 2:
+            raise ValueError("an intersection / union takes two or more branches, got %r" % (x,))
+        return ("u" if union else "i", [node(b) for b in branches])
+
+    tree = node(structure)
+    return tree, count["e"], count["r"]
+
+
 class KnowledgeGraphCompletion(nn.Module):
     """``tasks.KnowledgeGraphCompletionAdapted`` with the configuration surface of
     ``config/transductive/inference.yaml:8-39``; with ``toy_eval`` and the sampled metric names ``hits@K_N`` it is also the
@@ -508,6 +563,156 @@ class KnowledgeGraphCompletion(nn.Module):
         if with_hops:
             return index, value, self.answer_hops(anchor, index)
         return index, value
+
+    # ------------------------------------------------------------------ logical queries
+    def _first_hop(self, anchor, relation):
+        """Logits ``(Q, N)`` of ``(anchor[q], relation[q], ?)``, ``relation`` in ``[0, 2R)``: the single-source route of
+        :meth:`answer` (``score_all_entities``, else ``predict`` on triples whose other entity is 0)."""
+        n_rel = self.fact_graph.num_relation
+        base = relation % n_rel
+        pred = self.model.score_all_entities(self.fact_graph, self.relation_representations(base), anchor, relation)
+        if pred is None:
+            head = relation >= n_rel
+            zero = torch.zeros_like(anchor)
+            batch = torch.stack([torch.where(head, zero, anchor), torch.where(head, anchor, zero), base], dim=1)
+            pred = self.predict(batch)[torch.arange(len(anchor), device=anchor.device), head.long()]
+        return pred
+
+    def _project_sets(self, member, relation, threshold, max_sources):
+        """:meth:`project` behind its argument checks."""
+        from . import functional
+        ops = backend.get()
+        n_rel = self.fact_graph.num_relation
+        member = member.float()
+        floor = torch.full((len(member),), float(threshold), dtype=torch.float32, device=member.device)
+        if max_sources is not None:
+            # the K-th largest membership of every row; rows with fewer than K positive members are cut by the threshold alone
+            zero = torch.zeros(len(member), dtype=torch.int64, device=member.device)
+            topk = ops.topk_keys if ops.accepts(member) else functional.topk_keys
+            kth = topk(member, int(max_sources), None, zero, zero, 1)[0][:, -1]
+            floor = torch.maximum(floor, torch.where(kth > 0, kth, torch.zeros_like(kth)))
+        logits, count = self.model.project(self.fact_graph, self.relation_representations(relation % n_rel), member, relation,
+                                           floor)
+        p = torch.sigmoid(logits)
+        return torch.where((count > 0).unsqueeze(-1), p, torch.zeros_like(p))
+
+    @staticmethod
+    def _check_cut(max_sources):
+        if max_sources is not None and not 1 <= int(max_sources) <= TOPK_MAX:
+            raise ValueError("project: max_sources must be None or 1 to %d, got %r" % (TOPK_MAX, max_sources))
+
+    @torch.no_grad()
+    def project(self, member, relation, threshold=0.0, max_sources=None):
+        """One relation projection of fuzzy entity sets (an addition of this package, after ULTRAQuery -- Galkin et al. 2024 --
+        which answers multi-hop queries zero-shot with this link predictor; the reference has no such call): ``member`` fp32
+        ``(Q, N)`` memberships in ``[0, 1]``, ``relation`` int64 ``(Q,)`` in ``[0, 2R)`` (``r >= R``: the inverse of ``r - R``).
+        Returns the memberships ``(Q, N)`` of the tails of ``relation[q]`` over the set ``member[q]``: ``sigmoid`` of
+        ``TransferNBFNet.project``, in the model's precision (fp32).  The relation representations are those of the base
+        relation ``relation % R`` (the cache is honoured), the query row is ``relation``, as :meth:`answer` does for ``head``.
+        The cut: entity ``v`` takes part iff ``member[q, v] > 0`` and ``member[q, v] >= max(threshold, K-th largest membership
+        of row q)`` with ``K = max_sources`` (``None`` or 1 to 128; a row with fewer than ``K`` positive members is cut by
+        ``threshold`` alone); ties at the cut all stay.  The defaults cut nothing: the plain fuzzy definition.  Which cut answers
+        best is a question for benchmark data, and none has been run.  DECISION: a set that is empty after the cut has no
+        answers -- its row is all zeros, not the scores of a zero boundary."""
+        self._check_cut(max_sources)
+        member = torch.as_tensor(member, device=self.device)
+        relation = torch.as_tensor(relation, device=self.device).reshape(-1)
+        if member.dim() != 2 or member.shape[1] != self.num_entity or not member.is_floating_point():
+            raise ValueError("project: member must be floating point (Q, %d), got %s %s"
+                             % (self.num_entity, member.dtype, tuple(member.shape)))
+        if relation.dtype != torch.int64 or relation.shape != (len(member),):
+            raise ValueError("project: relation must be int64 (%d,), got %s %s" % (len(member), relation.dtype, tuple(relation.shape)))
+        if len(relation) == 0:
+            return member.new_zeros(0, self.num_entity, dtype=torch.float32)
+        if int(relation.min()) < 0 or int(relation.max()) >= 2 * self.num_relation:
+            raise ValueError("project: relations must lie in [0, %d), got [%d, %d]"
+                             % (2 * self.num_relation, int(relation.min()), int(relation.max())))
+        return self._project_sets(member, relation, threshold, max_sources)
+
+    def query_inputs(self, structure, anchors, relations):
+        """The parsed structure and the range-checked ``anchors`` int64 ``(Q, A)`` / ``relations`` int64 ``(Q, P)`` of
+        :meth:`answer_query` on the task's device (one host read per call, as :meth:`answer_queries`)."""
+        tree, n_anchor, n_relation = parse_query_structure(structure)
+        anchors = torch.as_tensor(anchors, device=self.device)
+        relations = torch.as_tensor(relations, device=self.device)
+        if (anchors.dtype != torch.int64 or relations.dtype != torch.int64 or anchors.dim() != 2 or relations.dim() != 2
+                or anchors.shape[1] != n_anchor or relations.shape[1] != n_relation or len(anchors) != len(relations)):
+            raise ValueError("answer_query: the structure takes anchors int64 (Q, %d) and relations int64 (Q, %d), got %s %s "
+                             "and %s %s" % (n_anchor, n_relation, anchors.dtype, tuple(anchors.shape), relations.dtype,
+                                            tuple(relations.shape)))
+        if len(anchors):
+            n, r = self.num_entity, 2 * self.num_relation
+            lo, hi_node, hi_rel = int(torch.min(anchors.min(), relations.min())), int(anchors.max()), int(relations.max())
+            if lo < 0 or hi_node >= n or hi_rel >= r:
+                raise ValueError("queries out of range for context `%s` (%d entities, relations in [0, %d)): min id %d, max "
+                                 "entity %d, max relation %d" % (self.split, n, r, lo, hi_node, hi_rel))
+        return tree, anchors, relations
+
+    def query_memberships(self, tree, anchors, relations, threshold=0.0, max_sources=None):
+        """The memberships ``(Q, N)`` of the answer set of the parsed structure ``tree`` (:func:`parse_query_structure`) for
+        checked inputs (:meth:`query_inputs`); the columns of ``anchors`` / ``relations`` are consumed depth-first, left to
+        right."""
+        at = {"e": 0, "r": 0}
+
+        def take(kind, table):
+            at[kind] += 1
+            return table[:, at[kind] - 1]
+
+        def run_ops(p, ops):
+            for op in ops:
+                p = self._project_sets(p, take("r", relations), threshold, max_sources) if op == "r" else 1 - p
+            return p
+
+        def walk(node):
+            kind = node[0]
+            if kind == "e":
+                p = torch.sigmoid(self._first_hop(take("e", anchors), take("r", relations)))
+                return run_ops(p, node[1][1:])
+            if kind == "ops":
+                return run_ops(walk(node[1]), node[2])
+            parts = [walk(child) for child in node[1]]
+            if kind == "i":
+                p = parts[0]
+                for other in parts[1:]:
+                    p = p * other
+                return p
+            rest = 1 - parts[0]
+            for other in parts[1:]:
+                rest = rest * (1 - other)
+            return 1 - rest
+
+        return walk(tree)
+
+    @torch.no_grad()
+    def answer_query(self, structure, anchors, relations, k=10, threshold=0.0, max_sources=None):
+        """The ``k`` best answers of multi-hop logical queries of ONE structure (an addition of this package: the 14 query
+        types of the BetaE benchmarks, answered as ULTRAQuery's "LP" variant does -- this frozen link predictor as the relation
+        projection over fuzzy sets, non-parametric fuzzy logic in between).  ``structure``: a name of ``QUERY_STRUCTURES`` or a
+        nested tuple in BetaE notation (:func:`parse_query_structure`); ``anchors`` int64 ``(Q, A)`` and ``relations`` int64
+        ``(Q, P)``, relations in ``[0, 2R)``, consumed depth-first, left to right.  The first projection after an anchor is the
+        single-source route of :meth:`answer` followed by ``sigmoid``; every later one is :meth:`project` of the current set
+        with the cut ``threshold`` / ``max_sources``; ``'n'`` is ``1 - p``; an intersection is the product of its branches,
+        left to right; a union ``1 - prod(1 - p_i)``.  The final set is never cut.  Returns ``(entities int64 (Q, k),
+        membership fp32 (Q, k))`` in the order ``functional.topk_keys`` defines (membership descending, ties by ascending entity);
+        slots whose membership is not positive hold ``-1`` / ``0.0``.  Known answers are NOT filtered: a multi-hop filter needs the
+        query traversed on the filter graph, which this call does not do."""
+        self._check_cut(max_sources)
+        tree, anchors, relations = self.query_inputs(structure, anchors, relations)
+        return self._answer_query_checked(tree, anchors, relations, k, threshold, max_sources)
+
+    def _answer_query_checked(self, tree, anchors, relations, k, threshold, max_sources):
+        from . import functional
+        k = int(k)
+        if not 1 <= k <= TOPK_MAX:
+            raise ValueError("answer_query: 1 to %d answers per query, got %d" % (TOPK_MAX, k))
+        if len(anchors) == 0:
+            return anchors.new_zeros(0, k), torch.zeros(0, k, device=anchors.device)
+        p = self.query_memberships(tree, anchors, relations, threshold, max_sources).float().contiguous()
+        ops = backend.get()
+        zero = torch.zeros(len(p), dtype=torch.int64, device=p.device)
+        value, index = (ops.topk_keys if ops.accepts(p) else functional.topk_keys)(p, k, None, zero, zero, 1)
+        listed = value > 0
+        return torch.where(listed, index, torch.full_like(index, -1)), torch.where(listed, value, torch.zeros_like(value))
 
     def training_indices(self, batch):
         """task.py:264-274: ``(B, 1 + num_negative)`` index grids, column 0 = the positive triple, the rest strict
