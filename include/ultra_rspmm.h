@@ -154,7 +154,9 @@ const char *ultra_rspmm_launch_record_fields(void);
  * chunks per wave (quad_kernel) would run, bit 3 the chunked kernels where one row per 16-lane group (rowgroup_kernel)
  * would run, bit 4 the wide-group forms of that kernel (32 / 64 lanes per row, column tiles of 128 / 256) on inputs small
  * enough to be cache-resident, bit 5 makes quad_kernel walk a label's column tiles one after the other where it would
- * work on several at once (small graphs), bit 6 walks the edge list of a plan that carries a dense form, bit 7 runs the weighted kernels where a plan carries marked words (packed_dead).  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
+ * work on several at once (small graphs), bit 6 walks the edge list of a plan that carries a dense form, bit 7 runs the weighted kernels where a plan carries marked words (packed_dead),
+ * bit 8 (256) runs the layer epilogue (ultra_combine_forward_f32) one wave per SIMD where the paired form, two waves per SIMD,
+ * would run (large inputs), bit 9 (512) runs the paired form at every size.  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
  * LDS-message form would run.  All paths return identical bits. */
 int ultra_rspmm_force_general_path(int on);
 

@@ -38,6 +38,8 @@ struct Knobs {
     bool no_concurrent_tiles = false;   // bit 5: quad_kernel walks a label's column tiles one after the other
     bool no_dense = false;              // bit 6: the edge list of a plan that carries a dense form (relgraph_dense.hip)
     bool no_dead_words = false;         // bit 7: the weighted kernels even where a plan carries marked words (packed_dead)
+    bool no_paired = false;             // bit 8: the layer epilogue never as combine_paired_kernel (one wave per SIMD instead)
+    bool force_paired = false;          // bit 9: combine_paired_kernel at every size (it runs large inputs only)
 };
 
 inline Knobs decode_knobs(int mask) {
@@ -50,6 +52,8 @@ inline Knobs decode_knobs(int mask) {
     k.no_concurrent_tiles = (mask & 32) != 0;
     k.no_dense = (mask & 64) != 0;
     k.no_dead_words = (mask & 128) != 0;
+    k.no_paired = (mask & 256) != 0;
+    k.force_paired = (mask & 512) != 0;
     return k;
 }
 

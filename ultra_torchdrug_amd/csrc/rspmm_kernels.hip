@@ -948,6 +948,209 @@ __global__ __launch_bounds__(kCbWaves * 64, PF ? 1 : 2) void combine_kernel(cons
     }
 }
 
+// combine_paired_kernel: combine_kernel<true, 0, false> with TWO waves per SIMD that both keep their register prefetch.
+// The one-wave form runs a tile's phases one after the other -- staging, 8 192 MFMA cycles, D -> LDS, LayerNorm, stores --
+// and the matrix pipe idles through the rest.  Measured (profiles/combine_paired_ab.json): 13.8 k -> 12.95 k cycles per tile
+// and SIMD, -4 % event-timed, -1.6 % on the headline step.  The second wave hides the waits at s_waitcnt; its vector work does
+// NOT run under its partner's GEMM (nor with the waves forced out of step, HISTORY), so a tile still costs the sum of its MFMA,
+// vector and LDS issue cycles.
+// What makes room: the upper half of the weight (outputs 32..63, `w1`) is read from an LDS image instead of registers, with
+// ds_read_b128 in the A fragments' own pattern (rows padded by one access width, conflict-free); the MFMA instruction, its
+// operands and the k order are combine_kernel's, so the bits are too.
+//   VGPRs: 64 weight (w0) + 64 prefetch + 32 accumulator + 32 LayerNorm row + fragments and addresses, at most 256 (two waves
+//          per SIMD), no scratch -- the build's resource remark is the check.
+//   LDS:   8 tiles x 16 896 B + the w1 image 16 896 B + gamma | beta 512 B + ticket 16 B = 152 592 B of kMaxLdsBytes.
+//   LDS reads per tile and wave: 16 KiB of A fragments + 16 KiB of w1; four SIMDs x 32 KiB at 256 B per clock are 512 of the
+//          8 192 cycles the tile's MFMAs take, 6 % (a full weight image would make it 10 %).
+// Tiles: workgroup b owns the contiguous range [n_tiles b / grid, n_tiles (b + 1) / grid); its waves draw from a ticket in
+// LDS (relaxed, workgroup scope, as quad_kernel's), one draw ahead of the tile in work so that the prefetch knows its tile.
+// Every tile is processed exactly once, by one wave, which has read it completely (the prefetch landed before the tile was
+// staged) before it stores it: `out` may be `update`.  The draw that finds the range empty prefetches the last row 16 times
+// (loads stay unconditional) and the loop ends.  No barrier after the one-off staging: the waves drift apart, which is the point.
+constexpr int kCpWaves = 8;
+constexpr int kCpW1Floats = 32 * kCbStride;
+constexpr int kCpLdsFloats = kCpWaves * kCbTileFloats + kCpW1Floats + 128 + 4;
+constexpr int kCpMinTilesPerGroup = 16;         // a workgroup per CU once every wave has two tiles
+static_assert(kCpLdsFloats * sizeof(float) <= (size_t)kMaxLdsBytes, "eight tiles and half the weight fit one CU's LDS");
+
+__global__ __launch_bounds__(kCpWaves * 64, 1) void combine_paired_kernel(const CombineParams p) {
+    extern __shared__ __attribute__((aligned(16))) float cb_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wl = uniform(threadIdx.x >> 6);
+    float *tile = cb_lds + wl * kCbTileFloats;
+    float *w1_lds = cb_lds + kCpWaves * kCbTileFloats;      // [32][kCbStride]: W[32 + j][0 .. 128)
+    float *gb = w1_lds + kCpW1Floats;
+    int *ticket = reinterpret_cast<int *>(gb + 128);
+    const int i = lane & 31, h = lane >> 5;
+    const long long n_tiles = (p.rows + kCbRows - 1) / kCbRows;
+    const long long lo = n_tiles * blockIdx.x / gridDim.x;
+    const int n_mine = (int)(n_tiles * (blockIdx.x + 1) / gridDim.x - lo);      // (host: below 2^31)
+
+    // B operand fragments of outputs 0..31: lane (j = l & 31, h): W[j][64 h + s], s = 0..63
+    float w0[64];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.weight + (long long)i * 128 + 64 * h + 4 * q);
+        w0[4 * q + 0] = a.x; w0[4 * q + 1] = a.y; w0[4 * q + 2] = a.z; w0[4 * q + 3] = a.w;
+    }
+    for (int j = threadIdx.x; j < 32 * 32; j += kCpWaves * 64)
+        *reinterpret_cast<f32x4 *>(w1_lds + (j >> 5) * kCbStride + 4 * (j & 31)) =
+            *reinterpret_cast<const f32x4 *>(p.weight + (long long)(32 + (j >> 5)) * 128 + 4 * (j & 31));
+    const float bias0 = p.bias[i], bias1 = p.bias[i + 32];
+    const int ln_row = lane >> 1, ln_half = lane & 1;
+    if (p.gamma != nullptr && threadIdx.x < 128) gb[threadIdx.x] = threadIdx.x < 64 ? p.gamma[threadIdx.x] : p.beta[threadIdx.x - 64];
+    if (threadIdx.x == 0) *ticket = 0;
+    __syncthreads();
+
+    const long long last = p.rows - 1;
+    f32x4 pa[8], pb[8];
+    auto fetch = [&](long long t) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            long long gr = t * kCbRows + r;
+            gr = gr < last ? gr : last;
+            pa[q] = *reinterpret_cast<const f32x4 *>(p.input + gr * 64 + c);
+            pb[q] = *reinterpret_cast<const f32x4 *>(p.update + gr * 64 + c);
+        }
+    };
+    auto draw = [&]() {
+        int t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return t;
+    };
+    int cur = uniform(draw());
+    if (cur >= n_mine) return;
+    fetch(lo + cur);
+    // Eight stores that store nothing (a descriptor of no bytes drops them), so that the loop is ENTERED as its back edge
+    // re-enters it: 16 loads in flight with 8 stores behind them.  vmcnt is in order and the compiler joins the two paths by
+    // the worse one; without these it waits at the top of every tile with vmcnt(0), i.e. for the write acknowledgements of the
+    // tile just stored (combine_kernel does), with them for the prefetched rows only.
+    {
+        const __amdgpu_buffer_rsrc_t rsrc_none = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0, 0x00020000);
+        const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu4, zero), rsrc_none, (4 * q + (lane >> 4)) * 256 + (lane & 15) * 16, 0, 0);
+    }
+    while (cur < n_mine) {
+        const long long row0 = (lo + cur) * kCbRows;
+        const int drawn = draw();
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            *reinterpret_cast<f32x4 *>(tile + r * kCbStride + c) = pa[q];
+            *reinterpret_cast<f32x4 *>(tile + r * kCbStride + 64 + c) = pb[q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const int nxt = uniform(drawn);
+        fetch(nxt < n_mine ? lo + nxt : n_tiles);      // in flight during the GEMM and the LayerNorm
+
+        // ---- GEMM: acc_t[r] = D[row = (r&3) + 8(r>>2) + 4h][out = i + 32 t]
+        // (the bias opaque per tile: as a loop invariant the compiler keeps both splatted accumulators, 32 VGPRs, for the
+        // life of the wave)
+        float b0 = bias0, b1 = bias1;
+        asm volatile("" : "+v"(b0), "+v"(b1));
+        f32x16 acc0, acc1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
+        // fragments one step ahead of their MFMAs and no further (the scheduling barrier): left alone, the compiler reads
+        // all 32 up front, 128 VGPRs, and spills
+        f32x4 av = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 64 * h);
+        f32x4 bv = *reinterpret_cast<const f32x4 *>(w1_lds + i * kCbStride + 64 * h);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            f32x4 an = av, bn = bv;
+            if (q < 15) {
+                an = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 64 * h + 4 * (q + 1));
+                bn = *reinterpret_cast<const f32x4 *>(w1_lds + i * kCbStride + 64 * h + 4 * (q + 1));
+            }
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, w0[4 * q + 0], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, w0[4 * q + 1], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, w0[4 * q + 2], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, w0[4 * q + 3], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            av = an; bv = bn;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // all A-fragment reads done before `update` is overwritten
+
+        // ---- D -> LDS over the (consumed) `update` half of the tile
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            tile[row * kCbStride + 64 + i] = acc0[r];
+            tile[row * kCbStride + 96 + i] = acc1[r];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+        // ---- LayerNorm + ReLU + shortcut: two lanes per row, 32 columns each, sums in column order (combine_kernel's)
+        float v[32];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const f32x4 d = *reinterpret_cast<const f32x4 *>(tile + ln_row * kCbStride + 64 + 32 * ln_half + 4 * q);
+            v[4 * q + 0] = d.x; v[4 * q + 1] = d.y; v[4 * q + 2] = d.z; v[4 * q + 3] = d.w;
+        }
+        if (p.gamma != nullptr) {
+            float s = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) s = s + v[c];
+            const float so = __shfl_xor(s, 1, 64);
+            const float mean = (ln_half == 0 ? s + so : so + s) * (1.0f / 64.0f);
+            float ss = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) { const float dlt = v[c] - mean; ss = ss + dlt * dlt; }
+            const float sso = __shfl_xor(ss, 1, 64);
+            const float var = (ln_half == 0 ? ss + sso : sso + ss) * (1.0f / 64.0f);
+            const float inv = 1.0f / sqrtf(var + p.eps);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const f32x4 gq = *reinterpret_cast<const f32x4 *>(gb + 32 * ln_half + 4 * q);
+                const f32x4 bq = *reinterpret_cast<const f32x4 *>(gb + 64 + 32 * ln_half + 4 * q);
+                v[4 * q + 0] = ((v[4 * q + 0] - mean) * inv) * gq.x + bq.x;
+                v[4 * q + 1] = ((v[4 * q + 1] - mean) * inv) * gq.y + bq.y;
+                v[4 * q + 2] = ((v[4 * q + 2] - mean) * inv) * gq.z + bq.z;
+                v[4 * q + 3] = ((v[4 * q + 3] - mean) * inv) * gq.w + bq.w;
+            }
+        }
+        if (p.relu) {
+#pragma unroll
+            for (int c = 0; c < 32; ++c) v[c] = !(v[c] <= 0.0f) ? v[c] : 0.0f;
+        }
+        if (p.shortcut) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const f32x4 x = *reinterpret_cast<const f32x4 *>(tile + ln_row * kCbStride + 32 * ln_half + 4 * q);
+                v[4 * q + 0] = v[4 * q + 0] + x.x; v[4 * q + 1] = v[4 * q + 1] + x.y;
+                v[4 * q + 2] = v[4 * q + 2] + x.z; v[4 * q + 3] = v[4 * q + 3] + x.w;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            f32x4 d;
+            d.x = v[4 * q + 0]; d.y = v[4 * q + 1]; d.z = v[4 * q + 2]; d.w = v[4 * q + 3];
+            *reinterpret_cast<f32x4 *>(tile + ln_row * kCbStride + 64 + 32 * ln_half + 4 * q) = d;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+        // ---- coalesced, unconditional buffer stores over a descriptor of exactly the tile's valid rows (combine_kernel)
+        const long long left = p.rows - row0;
+        const __amdgpu_buffer_rsrc_t rsrc_tile = __builtin_amdgcn_make_buffer_rsrc(
+            p.out + row0 * 64, 0, (int)(left < kCbRows ? left : kCbRows) * 256, 0x00020000);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            const f32x4 d = *reinterpret_cast<const f32x4 *>(tile + r * kCbStride + 64 + c);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu4, d), rsrc_tile, r * 256 + c * 4, 0, 0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // tile is rewritten by the next iteration
+        cur = nxt;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 static_assert(kBlock == kPlanBlock && kRgBlock == kPlanRgBlock, "plan_path.h states the workgroup sizes of its families");
@@ -1944,6 +2147,14 @@ static int combine_launch(const CombineParams &p, void *stream) {
     const int lds_max = (int)((kCbWaves * kCbTileFloats + 128 + kCbLdsQueries * 65) * sizeof(float));
     const size_t lds = (size_t)(kCbWaves * kCbTileFloats + 128 + (bnd_lds ? p.rpn * 65 : 0)) * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // the plain large-input form: two prefetching waves per SIMD (combine_paired_kernel); knob bit 8 keeps the one-wave
+    // kernel, bit 9 takes the paired one at every size
+    if (p.in_bnode == nullptr && p.z_out == nullptr && !g_knobs.no_paired && (prefetch || g_knobs.force_paired)) {
+        long long groups = n_tiles / kCpMinTilesPerGroup;
+        groups = groups < 1 ? 1 : (groups > di->n_cu ? di->n_cu : groups);
+        if (n_tiles / groups < 0x7fffff00LL)        // a workgroup's tickets are 32-bit
+            return launch_with_lds(combine_paired_kernel, p, (int)groups, kCpLdsFloats * sizeof(float), st, kCpWaves * 64);
+    }
     return with_bool(prefetch, [&](auto pf) {
         constexpr bool PF = decltype(pf)::value;
         auto go = [&](auto kern) { return launch_with_lds(kern, p, (int)blocks, lds, st, kCbWaves * 64, lds_max); };
