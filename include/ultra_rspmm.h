@@ -156,7 +156,8 @@ const char *ultra_rspmm_launch_record_fields(void);
  * enough to be cache-resident, bit 5 makes quad_kernel walk a label's column tiles one after the other where it would
  * work on several at once (small graphs), bit 6 walks the edge list of a plan that carries a dense form, bit 7 runs the weighted kernels where a plan carries marked words (packed_dead),
  * bit 8 (256) runs the layer epilogue (ultra_combine_forward_f32) one wave per SIMD where the paired form, two waves per SIMD,
- * would run (large inputs), bit 9 (512) runs the paired form at every size.  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
+ * would run (large inputs), bit 9 (512) runs the paired form at every size, bit 10 (1024) runs the score head
+ * (ultra_score_forward_f32) with the column-per-lane product and its LDS row phase where the row-per-lane form would run.  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
  * LDS-message form would run.  All paths return identical bits. */
 int ultra_rspmm_force_general_path(int on);
 
@@ -575,6 +576,7 @@ int ultra_linear_forward_f32(const float *input, const float *weight, const floa
  *     h[o]    = relu(c[b, o] + w1[o, :64] . hidden[n, b])          (chain k = 0, 32, 1, 33, ... from c)
  *     out     = b2 + sum_o h[o] w2[o]                              (o ascending)
  * -- the order oracle/rspmm_oracle.c restates (ABI 5; up to ABI 4 the 128-wide product ran per row).
+ * hidden, w1 and query_bias are read 16 bytes at a time: 16-byte aligned.
  */
 int ultra_score_forward_f32(const float *hidden, const float *query, const float *w1, const float *b1, const float *w2,
                             const float *b2, float *query_bias, float *out, int64_t n_node, int64_t batch, void *stream);

@@ -159,7 +159,8 @@ __global__ __launch_bounds__(128) void score_query_bias_kernel(const ScoreParams
     p.qbias[(long long)b * 128 + o] = acc;
 }
 
-__global__ __launch_bounds__(kCbWaves * 64, 1) void score_kernel(const ScoreParams p) {
+// score_kernel_lds (knob bit 10): the column-per-lane product, whose result crosses LDS before the per-row w2 dot
+__global__ __launch_bounds__(kCbWaves * 64, 1) void score_kernel_lds(const ScoreParams p) {
     constexpr int K = 64, N = 128, kWStride = K + 4, kTStride = N + 4;
     extern __shared__ __attribute__((aligned(16))) float dl_lds[];
     float *w_lds = dl_lds;                                         // [128][kWStride]: W1[:, :64]
@@ -267,6 +268,168 @@ __global__ __launch_bounds__(kCbWaves * 64, 1) void score_kernel(const ScorePara
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s), rsrc_out, live ? (unsigned)off : 0xffffffffu, 0, 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+}
+
+// v_permlane32_swap: lanes 32..63 of `a` change places with lanes 0..31 of `b`.  (The two results go through scalars:
+// __builtin_bit_cast applied to an ELEMENT of the returned vector reads element 0 whichever element is named.)
+__device__ __forceinline__ void half_swap(float &a, float &b) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), false, false);
+    const uint32_t first = sw[0], second = sw[1];
+    a = __builtin_bit_cast(float, first);
+    b = __builtin_bit_cast(float, second);
+}
+
+// score_kernel (the default form), row per lane: the product is issued as mfma(A = W1, B = rows), so lane (i, h) holds outputs
+// 32 tt + (r&3) + 8 (r>>2) + 4 h of ROW i in acc[tt][r] -- the same products in the same k order as mfma(A = rows, B = W1)
+// above, whose result is column per lane and crosses LDS before the per-row w2 dot (64 ds_write_b32, 64 ds_read_b128 and three
+// more full LDS waits per tile).  Here relu runs on the accumulators, 32 v_permlane32_swap on the pairs (acc[2p][r], acc[2p+1][r])
+// give lane i outputs [64p, 64p+32) and lane i+32 outputs [64p+32, 64p+64) of row i in a compile-time register order, and the
+// w2 chain (o ascending from b2) runs in four phases of 32 with the running sum handed across lane ^ 32 three times; the half
+// that does not hold the sum runs the same instructions on values that are discarded.
+// W1[:, :64] (128 registers, combine_kernel's way) and the lane's halves of w2 (64) live in registers; LDS holds c and the staged
+// 32 x 64 tiles only: 8 writes, 8 fragment reads and 16 seed reads of 16 bytes per tile and lane.
+// CMEM: c read from memory (batch > kScoreLdsBatch) -- a template parameter, not a branch: loads that MAY be in flight make the
+// compiler wait for the prefetch where the paths join (combine_kernel's note).
+//   Registers (the build's resource remark): 256 VGPRs + 84 AGPRs (CMEM: + 86), no scratch; one wave per SIMD.
+//   Measured (profiles/row_per_lane_ab.json): 132 -> 102 us event-timed at 465 k rows against score_kernel_lds.
+template <bool CMEM>
+__global__ __launch_bounds__(kCbWaves * 64, 1) void score_kernel(const ScoreParams p) {
+    constexpr int K = 64, kTStride = K + 4;
+    extern __shared__ __attribute__((aligned(16))) float dl_lds[];
+    float *c_lds = dl_lds;                                         // [kScoreLdsBatch][kScoreCStride]
+    const int lane = threadIdx.x & 63;
+    const int wl = uniform(threadIdx.x >> 6);
+    float *tile = c_lds + kScoreLdsBatch * kScoreCStride + wl * (32 * kTStride);     // [32][kTStride], wave private
+    const int i = lane & 31, h = lane >> 5;
+    // A operand fragments, lane (i, h): W1[i + 32 tt][32 h + s], s = 0..31;  w2r[pp][c] = w2[64 pp + 32 h + c]
+    float wr[4][32], w2r[2][32];
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(p.w1 + (long long)(i + 32 * tt) * 128 + 32 * h + 4 * q);
+            wr[tt][4 * q + 0] = a.x; wr[tt][4 * q + 1] = a.y; wr[tt][4 * q + 2] = a.z; wr[tt][4 * q + 3] = a.w;
+        }
+#pragma unroll
+    for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+        for (int c = 0; c < 32; ++c) w2r[pp][c] = p.w2[64 * pp + 32 * h + c];
+    if constexpr (!CMEM)
+        for (int idx = threadIdx.x; idx < p.batch * 128; idx += kCbWaves * 64) c_lds[(idx >> 7) * kScoreCStride + (idx & 127)] = p.qbias[idx];
+    __syncthreads();
+    const float b2 = p.b2[0];
+    // `out` as a buffer (host side: batch * n_node * 4 B < 4 GiB)
+    const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)(unsigned)(p.n_node * p.batch * 4), 0x00020000);
+
+    const long long rows = p.n_node * p.batch;
+    const long long n_tiles = (rows + 31) / 32;
+    const long long wave_global = (long long)blockIdx.x * kCbWaves + wl;
+    const long long wave_total = (long long)gridDim.x * kCbWaves;
+    if (wave_global >= n_tiles) return;
+    // one wave per SIMD: the NEXT tile's rows travel to registers while the matrix cores work on the current tile
+    const long long last = rows - 1;
+    f32x4 ph[8];
+    auto fetch = [&](long long t) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {                               // 32 rows x 64 floats of hidden, 4 rows per load
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            long long gr = t * 32 + r;
+            gr = gr < last ? gr : last;
+            ph[q] = *reinterpret_cast<const f32x4 *>(p.hidden + gr * 64 + c);
+        }
+    };
+    fetch(wave_global);
+    // One store that stores nothing (its offset is out of the descriptor's range), so that the loop is ENTERED as its back edge
+    // re-enters it, 8 loads in flight with one store behind them (combine_paired_kernel's note): vmcnt is in order, and
+    // without it every tile waits with vmcnt(0), i.e. for the acknowledgement of the previous tile's store.
+    __builtin_amdgcn_raw_buffer_store_b32(0u, rsrc_out, 0xffffffffu, 0, 0);
+    // (node0, q0) of a tile's first row, carried from tile to tile: a 64-bit division per tile on the scalar unit otherwise,
+    // and with one wave per SIMD nothing runs under it
+    const long long stride_rows = wave_total * 32;
+    const long long stride_nodes = stride_rows / p.batch;
+    const unsigned stride_q = (unsigned)(stride_rows - stride_nodes * p.batch);
+    long long node0 = wave_global * 32 / p.batch;
+    unsigned q0 = (unsigned)(wave_global * 32 - node0 * p.batch);
+    for (long long t = wave_global; t < n_tiles; t += wave_total) {
+        const long long row0 = t * 32;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            *reinterpret_cast<f32x4 *>(tile + r * kTStride + c) = ph[q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // accumulators start from the query's share: the lane's row i is query b = (q0 + i) % batch, its 64 seeds are 16 groups
+        // of four consecutive c[b][32 tt + 8 g + 4 h ..] (kScoreCStride keeps them 16-byte aligned).  CMEM: loaded BEFORE the
+        // prefetch is issued, so that the product waits for them and not for the prefetch behind them
+        const unsigned qq = q0 + (unsigned)i;                                              // < batch + 32
+        const unsigned b = p.batch >= 32 ? (qq >= (unsigned)p.batch ? qq - (unsigned)p.batch : qq) : qq % (unsigned)p.batch;
+        const float *c_row = CMEM ? p.qbias + (long long)b * 128 : c_lds + b * kScoreCStride;
+        f32x16 acc[4];
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 cv = *reinterpret_cast<const f32x4 *>(c_row + 32 * tt + 8 * g + 4 * h);
+                acc[tt][4 * g + 0] = cv.x; acc[tt][4 * g + 1] = cv.y; acc[tt][4 * g + 2] = cv.z; acc[tt][4 * g + 3] = cv.w;
+            }
+        // the next tile, UNCONDITIONALLY (past the end: the last row, eight times): behind a branch the compiler waits for every
+        // load that may be in flight where the paths join, and the prefetch becomes synchronous
+        fetch(t + wave_total);
+#pragma unroll
+        for (int q = 0; q < K / 8; ++q) {
+            const f32x4 bv = *reinterpret_cast<const f32x4 *>(tile + i * kTStride + (K / 2) * h + 4 * q);
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[tt][4 * q + 0], bv.x, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[tt][4 * q + 1], bv.y, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[tt][4 * q + 2], bv.z, acc[tt], 0, 0, 0);
+                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wr[tt][4 * q + 3], bv.w, acc[tt], 0, 0, 0);
+            }
+        }
+        // relu on the accumulators, then the half swaps: afterwards x[pp][4 g + j] is output 64 pp + 32 h + 8 g + j of row i and
+        // y[pp][4 g + j] is output 64 pp + 32 h + 8 g + 4 + j
+        float x[2][16], y[2][16];
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float lo = acc[2 * pp][r], hi = acc[2 * pp + 1][r];
+                x[pp][r] = !(lo <= 0.0f) ? lo : 0.0f;
+                y[pp][r] = !(hi <= 0.0f) ? hi : 0.0f;
+                half_swap(x[pp][r], y[pp][r]);
+            }
+        // second layer: o ascending fmaf chain from b2 (rowdot_kernel's order).  Phase (pp, half): the lanes of that half add
+        // outputs [64 pp + 32 half, + 32) of their row, then hand the sum to lane ^ 32; it ends in lanes 32..63
+        float s = b2;
+#pragma unroll
+        for (int ph2 = 0; ph2 < 4; ++ph2) {
+            const int pp = ph2 >> 1;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = __builtin_fmaf(x[pp][4 * g + j], w2r[pp][8 * g + j], s);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = __builtin_fmaf(y[pp][4 * g + j], w2r[pp][8 * g + 4 + j], s);
+            }
+            if (ph2 < 3) {
+                // lanes 32..63 of the first result hold the lower half's sum, lanes 0..31 of the second the upper half's
+                float from_lower = s, from_upper = s;
+                half_swap(from_lower, from_upper);
+                s = (ph2 & 1) == 0 ? from_lower : from_upper;
+            }
+        }
+        // one UNCONDITIONAL buffer store per tile, from the half that holds the sum (score_kernel_lds's note)
+        {
+            const unsigned step = p.batch >= 32 ? (qq >= (unsigned)p.batch ? 1u : 0u) : qq / (unsigned)p.batch;
+            const long long off = ((long long)b * p.n_node + node0 + step) * 4;
+            const bool live = lane >= 32 && row0 + i < rows;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s), rsrc_out, live ? (unsigned)off : 0xffffffffu, 0, 0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the fragment reads are done before the tile is rewritten
+        node0 += stride_nodes;
+        q0 += stride_q;
+        if (q0 >= (unsigned)p.batch) { q0 -= (unsigned)p.batch; ++node0; }
     }
 }
 
@@ -469,13 +632,18 @@ int ultra_score_forward_f32(const float *hidden, const float *query, const float
     ScoreParams p;
     p.hidden = hidden; p.query = query; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.qbias = query_bias; p.out = out;
     p.n_node = n_node; p.batch = (int)batch;
-    const size_t lds = (size_t)(128 * 68 + 128 + kScoreLdsBatch * kScoreCStride + kCbWaves * 32 * 132) * sizeof(float);
+    const bool rpl = !g_knobs.score_lds_rows;           // knob bit 10: the column-per-lane product with its LDS row phase
+    const size_t lds = rpl ? (size_t)(kScoreLdsBatch * kScoreCStride + kCbWaves * 32 * 68) * sizeof(float)
+                           : (size_t)(128 * 68 + 128 + kScoreLdsBatch * kScoreCStride + kCbWaves * 32 * 132) * sizeof(float);
     hipLaunchKernelGGL(score_query_bias_kernel, dim3((unsigned)batch), dim3(128), 0, static_cast<hipStream_t>(stream), p);
     const long long n_tiles = (n_node * batch + 31) / 32;
     long long blocks = (n_tiles + kCbWaves - 1) / kCbWaves;
     if (blocks > di->n_cu) blocks = di->n_cu;
     HIP_TRY(hipGetLastError());
-    return launch_with_lds(score_kernel, p, (int)blocks, lds, static_cast<hipStream_t>(stream), kCbWaves * 64, (int)lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!rpl) return launch_with_lds(score_kernel_lds, p, (int)blocks, lds, st, kCbWaves * 64, (int)lds);
+    if (batch > kScoreLdsBatch) return launch_with_lds(score_kernel<true>, p, (int)blocks, lds, st, kCbWaves * 64, (int)lds);
+    return launch_with_lds(score_kernel<false>, p, (int)blocks, lds, st, kCbWaves * 64, (int)lds);
 }
 
 int ultra_relation_project_f32(const float *relation, int64_t stride_b, int64_t stride_r, const float *const *w1,
