@@ -157,7 +157,8 @@ const char *ultra_rspmm_launch_record_fields(void);
  * work on several at once (small graphs), bit 6 walks the edge list of a plan that carries a dense form, bit 7 runs the weighted kernels where a plan carries marked words (packed_dead),
  * bit 8 (256) runs the layer epilogue (ultra_combine_forward_f32) one wave per SIMD where the paired form, two waves per SIMD,
  * would run (large inputs), bit 9 (512) runs the paired form at every size, bit 10 (1024) runs the score head
- * (ultra_score_forward_f32) with the column-per-lane product and its LDS row phase where the row-per-lane form would run.  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
+ * (ultra_score_forward_f32) with the column-per-lane product and its LDS row phase where the row-per-lane form would run,
+ * bit 11 (2048) does the same for the paired layer epilogue (combine_paired_kernel_lds where combine_paired_kernel would run).  Bit 0 also selects the L2-row form of the first-layer frontier kernel where the
  * LDS-message form would run.  All paths return identical bits. */
 int ultra_rspmm_force_general_path(int on);
 

@@ -271,15 +271,6 @@ __global__ __launch_bounds__(kCbWaves * 64, 1) void score_kernel_lds(const Score
     }
 }
 
-// v_permlane32_swap: lanes 32..63 of `a` change places with lanes 0..31 of `b`.  (The two results go through scalars:
-// __builtin_bit_cast applied to an ELEMENT of the returned vector reads element 0 whichever element is named.)
-__device__ __forceinline__ void half_swap(float &a, float &b) {
-    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), false, false);
-    const uint32_t first = sw[0], second = sw[1];
-    a = __builtin_bit_cast(float, first);
-    b = __builtin_bit_cast(float, second);
-}
-
 // score_kernel (the default form), row per lane: the product is issued as mfma(A = W1, B = rows), so lane (i, h) holds outputs
 // 32 tt + (r&3) + 8 (r>>2) + 4 h of ROW i in acc[tt][r] -- the same products in the same k order as mfma(A = rows, B = W1)
 // above, whose result is column per lane and crosses LDS before the per-row w2 dot (64 ds_write_b32, 64 ds_read_b128 and three

@@ -41,6 +41,7 @@ struct Knobs {
     bool no_paired = false;             // bit 8: the layer epilogue never as combine_paired_kernel (one wave per SIMD instead)
     bool force_paired = false;          // bit 9: combine_paired_kernel at every size (it runs large inputs only)
     bool score_lds_rows = false;        // bit 10: score_kernel<false>, the column-per-lane product with its LDS row phase
+    bool combine_lds_rows = false;      // bit 11: combine_paired_kernel_lds, the column-per-lane product with its LDS row phase
 };
 
 inline Knobs decode_knobs(int mask) {
@@ -56,6 +57,7 @@ inline Knobs decode_knobs(int mask) {
     k.no_paired = (mask & 256) != 0;
     k.force_paired = (mask & 512) != 0;
     k.score_lds_rows = (mask & 1024) != 0;
+    k.combine_lds_rows = (mask & 2048) != 0;
     return k;
 }
 

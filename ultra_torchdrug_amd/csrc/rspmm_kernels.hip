@@ -675,6 +675,15 @@ static_assert(kCbLdsQueries == kSparseMaxQueries, "const_fill_kernel lays out on
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// v_permlane32_swap: lanes 32..63 of `a` change places with lanes 0..31 of `b`.  (The two results go through scalars:
+// __builtin_bit_cast applied to an ELEMENT of the returned vector reads element 0 whichever element is named.)
+__device__ __forceinline__ void half_swap(float &a, float &b) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), false, false);
+    const uint32_t first = sw[0], second = sw[1];
+    a = __builtin_bit_cast(float, first);
+    b = __builtin_bit_cast(float, second);
+}
+
 struct CombineParams {
     const float *input;    // [rows, 64]
     const float *update;   // [rows, 64]
@@ -948,7 +957,8 @@ __global__ __launch_bounds__(kCbWaves * 64, PF ? 1 : 2) void combine_kernel(cons
     }
 }
 
-// combine_paired_kernel: combine_kernel<true, 0, false> with TWO waves per SIMD that both keep their register prefetch.
+// combine_paired_kernel_lds (knob bit 11, and every input of 4 GiB and more; the default is combine_paired_kernel below):
+// combine_kernel<true, 0, false> with TWO waves per SIMD that both keep their register prefetch.
 // The one-wave form runs a tile's phases one after the other -- staging, 8 192 MFMA cycles, D -> LDS, LayerNorm, stores --
 // and the matrix pipe idles through the rest.  Measured (profiles/combine_paired_ab.json): 13.8 k -> 12.95 k cycles per tile
 // and SIMD, -4 % event-timed, -1.6 % on the headline step.  The second wave hides the waits at s_waitcnt; its vector work does
@@ -959,7 +969,8 @@ __global__ __launch_bounds__(kCbWaves * 64, PF ? 1 : 2) void combine_kernel(cons
 // operands and the k order are combine_kernel's, so the bits are too.
 //   VGPRs: 64 weight (w0) + 64 prefetch + 32 accumulator + 32 LayerNorm row + fragments and addresses, at most 256 (two waves
 //          per SIMD), no scratch -- the build's resource remark is the check.
-//   LDS:   8 tiles x 16 896 B + the w1 image 16 896 B + gamma | beta 512 B + ticket 16 B = 152 592 B of kMaxLdsBytes.
+//   LDS:   8 tiles x 16 896 B + the w1 image 16 896 B + gamma | beta 512 B + ticket 16 B = 152 592 B of kMaxLdsBytes (the
+//          launch allocates 256 B more: the bias image of the row-per-lane form).
 //   LDS reads per tile and wave: 16 KiB of A fragments + 16 KiB of w1; four SIMDs x 32 KiB at 256 B per clock are 512 of the
 //          8 192 cycles the tile's MFMAs take, 6 % (a full weight image would make it 10 %).
 // Tiles: workgroup b owns the contiguous range [n_tiles b / grid, n_tiles (b + 1) / grid); its waves draw from a ticket in
@@ -969,11 +980,11 @@ __global__ __launch_bounds__(kCbWaves * 64, PF ? 1 : 2) void combine_kernel(cons
 // (loads stay unconditional) and the loop ends.  No barrier after the one-off staging: the waves drift apart, which is the point.
 constexpr int kCpWaves = 8;
 constexpr int kCpW1Floats = 32 * kCbStride;
-constexpr int kCpLdsFloats = kCpWaves * kCbTileFloats + kCpW1Floats + 128 + 4;
+constexpr int kCpLdsFloats = kCpWaves * kCbTileFloats + kCpW1Floats + 128 + 64 + 4;    // tiles, w1, gamma | beta, bias (row-per-lane form), ticket
 constexpr int kCpMinTilesPerGroup = 16;         // a workgroup per CU once every wave has two tiles
 static_assert(kCpLdsFloats * sizeof(float) <= (size_t)kMaxLdsBytes, "eight tiles and half the weight fit one CU's LDS");
 
-__global__ __launch_bounds__(kCpWaves * 64, 1) void combine_paired_kernel(const CombineParams p) {
+__global__ __launch_bounds__(kCpWaves * 64, 1) void combine_paired_kernel_lds(const CombineParams p) {
     extern __shared__ __attribute__((aligned(16))) float cb_lds[];
     const int lane = threadIdx.x & 63;
     const int wl = uniform(threadIdx.x >> 6);
@@ -1147,6 +1158,218 @@ __global__ __launch_bounds__(kCpWaves * 64, 1) void combine_paired_kernel(const 
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu4, d), rsrc_tile, r * 256 + c * 4, 0, 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // tile is rewritten by the next iteration
+        cur = nxt;
+    }
+}
+
+// combine_paired_kernel (the default form of the paired epilogue), row per lane: combine_paired_kernel_lds with the product
+// issued as mfma(A = weight fragment, B = row fragment) -- the same registers, the same ds_read_b128, the same products in the
+// same k order, so the same bits -- which leaves lane (i, h) with outputs 32 t + (r&3) + 8 (r>>2) + 4 h of ROW i in acc_t[r]
+// instead of a column of 32 rows.  16 v_permlane32_swap on the pairs (acc0[r], acc1[r]) give lane i columns 0..31 and lane
+// i + 32 columns 32..63 of row i (score_kernel's x / y layout: acc0[4 g + j] is column 32 H + 8 g + j, acc1[4 g + j] column
+// 32 H + 8 g + 4 + j, H = lane >> 5), and LayerNorm, relu and the shortcut run on the accumulators in the former order: 32
+// columns ascending from 0.0f per lane, the two halves added as lower + upper on both lanes.  What goes per tile and lane: 32
+// ds_write_b32 of D, a full LDS wait, 8 ds_read_b128 and the 32 registers they filled.
+// The result goes out as before: 8 ds_write_b128 into the tile's `update` half, a wait, 8 ds_read_b128 in row order and 8
+// coalesced buffer_store_b128 (8 row segments per instruction).  Stored row per lane from the accumulators (64 row segments per
+// instruction, no LDS pass) a launch measured about 3 us slower than this (HISTORY, "the layer epilogue, row per lane").
+// Prefetch: `input` and `update` through buffer descriptors over the whole tensors (host: rows * 256 B < 4 GiB), the tile's
+// byte base in the scalar offset, one per-lane offset for the life of the wave.  Rows past the end fail the range check: they
+// load 0, touch nothing and are never stored.  The draw that finds the range empty loads from the tensors' end, i.e. nothing.
+__global__ __launch_bounds__(kCpWaves * 64, 1) void combine_paired_kernel(const CombineParams p) {
+    extern __shared__ __attribute__((aligned(16))) float cb_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wl = uniform(threadIdx.x >> 6);
+    float *tile = cb_lds + wl * kCbTileFloats;
+    float *w1_lds = cb_lds + kCpWaves * kCbTileFloats;      // [32][kCbStride]: W[32 + j][0 .. 128)
+    float *gb = w1_lds + kCpW1Floats;
+    float *bias_lds = gb + 128;
+    int *ticket = reinterpret_cast<int *>(bias_lds + 64);
+    const int i = lane & 31, h = lane >> 5;
+    const long long n_tiles = (p.rows + kCbRows - 1) / kCbRows;
+    const long long lo = n_tiles * blockIdx.x / gridDim.x;
+    const int n_mine = (int)(n_tiles * (blockIdx.x + 1) / gridDim.x - lo);      // (host: below 2^31)
+
+    // A operand fragments of outputs 0..31: lane (j = l & 31, h): W[j][64 h + s], s = 0..63
+    float w0[64];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(p.weight + (long long)i * 128 + 64 * h + 4 * q);
+        w0[4 * q + 0] = a.x; w0[4 * q + 1] = a.y; w0[4 * q + 2] = a.z; w0[4 * q + 3] = a.w;
+    }
+    for (int j = threadIdx.x; j < 32 * 32; j += kCpWaves * 64)
+        *reinterpret_cast<f32x4 *>(w1_lds + (j >> 5) * kCbStride + 4 * (j & 31)) =
+            *reinterpret_cast<const f32x4 *>(p.weight + (long long)(32 + (j >> 5)) * 128 + 4 * (j & 31));
+    // the accumulators start from the bias of THEIR outputs, four consecutive ones per ds_read_b128 (as 32 registers for the
+    // life of the wave they spill)
+    if (threadIdx.x < 64) bias_lds[threadIdx.x] = p.bias[threadIdx.x];
+    if (p.gamma != nullptr && threadIdx.x < 128) gb[threadIdx.x] = threadIdx.x < 64 ? p.gamma[threadIdx.x] : p.beta[threadIdx.x - 64];
+    if (threadIdx.x == 0) *ticket = 0;
+    __syncthreads();
+
+    const uint32_t total_bytes = (uint32_t)(p.rows * 256);
+    const __amdgpu_buffer_rsrc_t rsrc_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.input), 0, (int)total_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_up = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.update), 0, (int)total_bytes, 0x00020000);
+    const uint32_t v_tile = (uint32_t)(lane >> 4) * 256u + (uint32_t)(lane & 15) * 16u;     // row (lane >> 4) of a 4-row, 1-KiB slab
+    f32x4 pa[8], pb[8];
+    auto fetch = [&](uint32_t base) {       // base: the tile's first byte (wave-uniform), total_bytes for no tile
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            pa[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, v_tile + 1024u * q, base, 0));
+            pb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_up, v_tile + 1024u * q, base, 0));
+        }
+    };
+    auto draw = [&]() {
+        int t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return t;
+    };
+    int cur = uniform(draw());
+    if (cur >= n_mine) return;
+    fetch((uint32_t)(lo + cur) * (uint32_t)(kCbRows * 256));
+    // Eight stores that store nothing, so that the loop is entered as its back edge re-enters it (combine_paired_kernel_lds's note)
+    {
+        const __amdgpu_buffer_rsrc_t rsrc_none = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0, 0x00020000);
+        const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu4, zero), rsrc_none, (4 * q + (lane >> 4)) * 256 + (lane & 15) * 16, 0, 0);
+    }
+    while (cur < n_mine) {
+        const long long row0 = (lo + cur) * kCbRows;
+        const int drawn = draw();
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            *reinterpret_cast<f32x4 *>(tile + r * kCbStride + c) = pa[q];
+            *reinterpret_cast<f32x4 *>(tile + r * kCbStride + 64 + c) = pb[q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const int nxt = uniform(drawn);
+        fetch(nxt < n_mine ? (uint32_t)(lo + nxt) * (uint32_t)(kCbRows * 256) : total_bytes);      // in flight during the GEMM and the LayerNorm
+
+        // ---- GEMM: acc_t[r] = D[out = 32 t + (r&3) + 8(r>>2) + 4h][row = i]
+        f32x16 acc0, acc1;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 b0 = *reinterpret_cast<const f32x4 *>(bias_lds + 8 * g + 4 * h);
+            const f32x4 b1 = *reinterpret_cast<const f32x4 *>(bias_lds + 32 + 8 * g + 4 * h);
+            acc0[4 * g + 0] = b0.x; acc0[4 * g + 1] = b0.y; acc0[4 * g + 2] = b0.z; acc0[4 * g + 3] = b0.w;
+            acc1[4 * g + 0] = b1.x; acc1[4 * g + 1] = b1.y; acc1[4 * g + 2] = b1.z; acc1[4 * g + 3] = b1.w;
+        }
+        // fragments one step ahead of their MFMAs and no further (the scheduling barrier): left alone, the compiler reads
+        // all 32 up front, 128 VGPRs, and spills
+        f32x4 av = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 64 * h);
+        f32x4 bv = *reinterpret_cast<const f32x4 *>(w1_lds + i * kCbStride + 64 * h);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            f32x4 an = av, bn = bv;
+            if (q < 15) {
+                an = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 64 * h + 4 * (q + 1));
+                bn = *reinterpret_cast<const f32x4 *>(w1_lds + i * kCbStride + 64 * h + 4 * (q + 1));
+            }
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[4 * q + 0], av.x, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, av.x, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[4 * q + 1], av.y, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, av.y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[4 * q + 2], av.z, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.z, av.z, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[4 * q + 3], av.w, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.w, av.w, acc1, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            av = an; bv = bn;
+        }
+
+        // ---- the half swaps: afterwards x[4 g + j] is column 32 H + 8 g + j of row i and y[4 g + j] column 32 H + 8 g + 4 + j
+        // (H = h, the lane's half: lane i owns columns 0..31, lane i + 32 columns 32..63)
+        float x[16], y[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            x[r] = acc0[r]; y[r] = acc1[r];
+            half_swap(x[r], y[r]);
+        }
+        // ---- LayerNorm + ReLU + shortcut on the accumulators, sums in column order (combine_kernel's)
+        if (p.gamma != nullptr) {
+            float s = 0.0f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = s + x[4 * g + j];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s = s + y[4 * g + j];
+            }
+            float s_lower = s, s_upper = s;         // after the swap, on both lanes: the lower half's sum and the upper half's
+            half_swap(s_lower, s_upper);
+            const float mean = (s_lower + s_upper) * (1.0f / 64.0f);
+            float ss = 0.0f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float dlt = x[4 * g + j] - mean; ss = ss + dlt * dlt; }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float dlt = y[4 * g + j] - mean; ss = ss + dlt * dlt; }
+            }
+            float ss_lower = ss, ss_upper = ss;
+            half_swap(ss_lower, ss_upper);
+            const float var = (ss_lower + ss_upper) * (1.0f / 64.0f);
+            const float inv = 1.0f / sqrtf(var + p.eps);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 gx = *reinterpret_cast<const f32x4 *>(gb + 32 * h + 8 * g);
+                const f32x4 gy = *reinterpret_cast<const f32x4 *>(gb + 32 * h + 8 * g + 4);
+                const f32x4 bx = *reinterpret_cast<const f32x4 *>(gb + 64 + 32 * h + 8 * g);
+                const f32x4 by = *reinterpret_cast<const f32x4 *>(gb + 64 + 32 * h + 8 * g + 4);
+                x[4 * g + 0] = ((x[4 * g + 0] - mean) * inv) * gx.x + bx.x;
+                x[4 * g + 1] = ((x[4 * g + 1] - mean) * inv) * gx.y + bx.y;
+                x[4 * g + 2] = ((x[4 * g + 2] - mean) * inv) * gx.z + bx.z;
+                x[4 * g + 3] = ((x[4 * g + 3] - mean) * inv) * gx.w + bx.w;
+                y[4 * g + 0] = ((y[4 * g + 0] - mean) * inv) * gy.x + by.x;
+                y[4 * g + 1] = ((y[4 * g + 1] - mean) * inv) * gy.y + by.y;
+                y[4 * g + 2] = ((y[4 * g + 2] - mean) * inv) * gy.z + by.z;
+                y[4 * g + 3] = ((y[4 * g + 3] - mean) * inv) * gy.w + by.w;
+            }
+        }
+        if (p.relu) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                x[r] = !(x[r] <= 0.0f) ? x[r] : 0.0f;
+                y[r] = !(y[r] <= 0.0f) ? y[r] : 0.0f;
+            }
+        }
+        if (p.shortcut) {       // the lane's half of its own input row, in the A fragments' conflict-free pattern
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 ix = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 32 * h + 8 * g);
+                const f32x4 iy = *reinterpret_cast<const f32x4 *>(tile + i * kCbStride + 32 * h + 8 * g + 4);
+                x[4 * g + 0] = x[4 * g + 0] + ix.x; x[4 * g + 1] = x[4 * g + 1] + ix.y;
+                x[4 * g + 2] = x[4 * g + 2] + ix.z; x[4 * g + 3] = x[4 * g + 3] + ix.w;
+                y[4 * g + 0] = y[4 * g + 0] + iy.x; y[4 * g + 1] = y[4 * g + 1] + iy.y;
+                y[4 * g + 2] = y[4 * g + 2] + iy.z; y[4 * g + 3] = y[4 * g + 3] + iy.w;
+            }
+        }
+
+        // ---- through the (consumed) `update` half of the tile, then coalesced, unconditional buffer stores over a descriptor
+        // of exactly the tile's valid rows (combine_kernel's note)
+        const long long left = p.rows - row0;
+        const __amdgpu_buffer_rsrc_t rsrc_tile = __builtin_amdgcn_make_buffer_rsrc(
+            p.out + row0 * 64, 0, (int)(left < kCbRows ? left : kCbRows) * 256, 0x00020000);
+        // (every A fragment read of `update` has been consumed by an MFMA whose result these values depend on)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 dx, dy;
+            dx.x = x[4 * g + 0]; dx.y = x[4 * g + 1]; dx.z = x[4 * g + 2]; dx.w = x[4 * g + 3];
+            dy.x = y[4 * g + 0]; dy.y = y[4 * g + 1]; dy.z = y[4 * g + 2]; dy.w = y[4 * g + 3];
+            *reinterpret_cast<f32x4 *>(tile + i * kCbStride + 64 + 32 * h + 8 * g) = dx;
+            *reinterpret_cast<f32x4 *>(tile + i * kCbStride + 64 + 32 * h + 8 * g + 4) = dy;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int r = 4 * q + (lane >> 4), c = (lane & 15) * 4;
+            const f32x4 d = *reinterpret_cast<const f32x4 *>(tile + r * kCbStride + 64 + c);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu4, d), rsrc_tile, r * 256 + c * 4, 0, 0);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of the tile is done before the next iteration rewrites it
         cur = nxt;
     }
 }
@@ -2148,12 +2371,17 @@ static int combine_launch(const CombineParams &p, void *stream) {
     const size_t lds = (size_t)(kCbWaves * kCbTileFloats + 128 + (bnd_lds ? p.rpn * 65 : 0)) * sizeof(float);
     hipStream_t st = static_cast<hipStream_t>(stream);
     // the plain large-input form: two prefetching waves per SIMD (combine_paired_kernel); knob bit 8 keeps the one-wave
-    // kernel, bit 9 takes the paired one at every size
+    // kernel, bit 9 takes the paired one at every size, bit 11 its former column-per-lane form (combine_paired_kernel_lds)
     if (p.in_bnode == nullptr && p.z_out == nullptr && !g_knobs.no_paired && (prefetch || g_knobs.force_paired)) {
         long long groups = n_tiles / kCpMinTilesPerGroup;
         groups = groups < 1 ? 1 : (groups > di->n_cu ? di->n_cu : groups);
         if (n_tiles / groups < 0x7fffff00LL)        // a workgroup's tickets are 32-bit
-            return launch_with_lds(combine_paired_kernel, p, (int)groups, kCpLdsFloats * sizeof(float), st, kCpWaves * 64);
+        {
+            // the row-per-lane form reads through 32-bit buffer offsets: rows * 256 B < 4 GiB; knob bit 11 keeps the former kernel
+            const bool row_per_lane = !g_knobs.combine_lds_rows && p.rows * 256 < (1LL << 32);
+            return launch_with_lds(row_per_lane ? combine_paired_kernel : combine_paired_kernel_lds, p, (int)groups,
+                                   kCpLdsFloats * sizeof(float), st, kCpWaves * 64);
+        }
     }
     return with_bool(prefetch, [&](auto pf) {
         constexpr bool PF = decltype(pf)::value;
