@@ -760,6 +760,17 @@ def test_sparse_first_layer_backward_survives_a_switch_to_the_full_d_relation_ke
                 assert bool(torch.isfinite(got[k]).all()), k
                 scale = want[k].abs().max().item()
                 assert (got[k] - want[k]).abs().max().item() <= 2e-5 * scale + 1e-9, k
+        # both flips once more with every allocation of the step poisoned and banded (tests/guarded_memory.py): what the junk
+        # tensors above reach by the allocator's favour, the guard reaches by construction
+        from guarded_memory import ALL_MODULES, guarded
+        for flip in (flip_switch, flip_knob):
+            with guarded(*ALL_MODULES, widest_row=32 * 64 * 4):
+                got = step(flip)
+            assert got.keys() == want.keys()
+            for k in want:
+                assert bool(torch.isfinite(got[k]).all()), k
+                scale = want[k].abs().max().item()
+                assert (got[k] - want[k]).abs().max().item() <= 2e-5 * scale + 1e-9, k
         # with the switch off from the start the forward does not take the sparse form at all
         UF.BOUNDARY_DRELATION = False
         try:
