@@ -406,6 +406,38 @@ int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd_host, const
                                            int64_t F, int64_t block, int sum_op, void *stream);
 
 /*
+ * The four statistics of aggregate_func = "pna" from ONE walk of the forward plan (csrc/pna.hip; DESIGN.md "Native PNA
+ * inference").  Replaces the four generalized_rspmm calls of the reference's ultra/layer.py:160-167 and :362-369 -- sum, sum over
+ * the squared operands, max, min -- which gather the same input[src] and relation[rel] rows four times.  Per edge (u -> v, r, w) of
+ * row v and per column, with x = input[u], q = relation[r]:
+ *     y  = w * (q MUL x)                sum[v] += y     max[v] = (y > max[v]) ? y : max[v]     min[v] = (y < min[v]) ? y : min[v]
+ *     y2 = w * ((q * q) MUL (x * x))    sq_sum[v] += y2
+ * (y2 squares the OPERANDS, not the message: the reference's rspmm branch, TransE included; w is skipped for unit-weight plans).
+ * Rows start from 0, 0, -FLT_MAX, FLT_MAX; the pieces of a split row start from the same values, go to the workspace and are
+ * combined in piece order by a second kernel.  The optional epilogue is the boundary of ultra_rspmm_forward_f32 (add_rows, dense)
+ * or of ultra_rspmm_forward_boundary_f32 (boundary_node / boundary_value / block, sparse; NULL / NULL / 0 for none), at most one
+ * of the two: with b the boundary element, sum + b, sq_sum + b * b, max(max, b), min(min, b).
+ * CONTRACT: every plane carries the bits of the corresponding ultra_rspmm_forward_f32 call on the same plan -- sq_sum those of the
+ * call on relation * relation and input * input (and add_rows * add_rows) -- for every plan this entry accepts, whichever kernel
+ * that call runs and whichever wave takes which chunk: all of them reduce a row, or a piece, strictly in plan order, and no
+ * operation here is contracted (-ffp-contract=off).  NaN and infinities behave as there.  (A plan with marked words, packed_dead,
+ * is walked with its weights, the form ultra_rspmm_forward_f32 documents for it.)
+ *   sum, sq_sum, max, min : [fwd->n_rows, F] each, written completely;  relation [n_rel, F];  input [n_src, F]
+ *   workspace             : ultra_rspmm_pna_workspace_bytes(fwd, F) = 4 x ultra_rspmm_workspace_bytes(fwd, F)
+ * The entry only enqueues -- no allocation, no host read, no memset node (see ultra_rspmm_frontier_f32) -- and all offsets are
+ * 64-bit (n_rows * F may pass 2^31).  Before any device work: ULTRA_ERR_NULL_POINTER, ULTRA_ERR_ABI and ULTRA_ERR_BAD_SHAPE as
+ * ultra_rspmm_forward_boundary_f32 (and for both boundary forms at once), ULTRA_ERR_BAD_OP for an unknown mul_op,
+ * ULTRA_ERR_WORKSPACE, and ULTRA_ERR_BAD_SHAPE for a plan that carries a dense form (fwd->dense != NULL: the relation graphs,
+ * whose sums run on the matrix cores in another documented order -- make the four calls there).
+ * Bytes moved at least: E * (4 F * 2 + 12) + 4 * 4 * n_rows * F.
+ */
+size_t ultra_rspmm_pna_workspace_bytes(const ultra_segments *fwd_host, int64_t F);
+int ultra_rspmm_pna_forward_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
+                                const float *add_rows, const int32_t *boundary_node, const float *boundary_value, int64_t block,
+                                float *sum, float *sq_sum, float *max, float *min, void *workspace, size_t workspace_bytes,
+                                int64_t n_src, int64_t n_rel, int64_t F, int mul_op, void *stream);
+
+/*
  * One layer of the path beam search behind TransferNBFNet.visualize (csrc/beam_search.hip; DESIGN.md "Explaining a
  * prediction").  Over the coalesced dst-CSR of the graph with inverse edges:
  *   row_ptr int32 [n_node + 1], src int32 [n_edges]   (rows = destination nodes, edges in coalesced order)
@@ -507,6 +539,34 @@ int ultra_combine_forward_boundary_f32(const int32_t *boundary_node, const float
                                        const float *update, const float *weight, const float *bias, const float *ln_weight,
                                        const float *ln_bias, float ln_eps, int relu, int shortcut, float *out, int64_t rows,
                                        int64_t dim, void *stream);
+
+/*
+ * The epilogue of a PNA layer over the four statistics of ultra_rspmm_pna_forward_f32 (dim must be 64; csrc/pna.hip):
+ *     out = [input +]  relu?( LayerNorm?( Linear_{832 -> 64}( cat[input, update] ) ) )
+ * with update = `_pna(mean, sq_mean, max, min, degree_out)` of the reference's ultra/layer.py:147-153, :172-178 -- twelve values
+ * per column -- never materialised.  Row i is (node i / n_query, query i % n_query); per row and column d, step by step as there:
+ *     mean = sum / degree      sq_mean = sq_sum / degree      std = sqrtf(fmaxf(sq_mean - mean * mean, pna_eps))
+ *     update[(d * 4 + s) * 3 + a] = (mean, max, min, std)[s] * (1, scale, inverse scale)[a]        (weight column 64 + that index)
+ *   input, sum, sq_sum, max, min, out : [rows, 64] fp32, 16-byte aligned; `out` must not alias any input
+ *   node_table : [ceil(rows / n_query)][3] = degree (degree_out + 1), scale (log(degree) / mean over the nodes of log(degree)), inverse
+ *                scale (1 / max(scale, 1e-2)) of each node -- computed by the caller, so the kernel needs no reduction over nodes
+ *   weight [64, 832] = nn.Linear.weight;  bias [64];  ln_weight / ln_bias [64] or both NULL;  relu, shortcut: 0 / 1
+ * Summation order.  The 832 columns are cut into 8 slices, slice w = input columns 8 w .. 8 w + 7 and the update columns of
+ * d = 8 w .. 8 w + 7.  A slice's product P_w is a chain of v_mfma_f32_32x32x2_f32 from 0.0f -- bit for bit fmaf(a, b, acc), one
+ * rounding per product -- over 52 steps of two columns each, the column of d = 8 w + j first and of d = 8 w + 4 + j second:
+ * j = 0..3 over the input columns, then (j, s, a) ascending, a fastest, over the update columns.  Then
+ *     z = ((bias + P_0) + P_1) + ... + P_7
+ * LayerNorm: sums of a thread's four consecutive outputs ((z0 + z1) + z2) + z3, then an xor butterfly over the row's 16 threads
+ * (distances 1, 2, 4, 8); mean = sum * (1 / 64); the variance from (z - mean)^2 the same way; (z - mean) * (1 / sqrtf(var + eps))
+ * * gamma + beta, unfused.  Exact-f32 matrix cores rather than a VALU chain: the same fp32 peak, one operand register per
+ * product, and the VALU stays free for the statistics' arithmetic.
+ * ULTRA_ERR_BAD_SHAPE for dim != 64, rows < 0, n_query < 1 or a misaligned pointer.  Only enqueues.
+ * Bytes moved at least: 4 * rows * 64 * (5 + 1) + 4 * 64 * 832.
+ */
+int ultra_pna_combine_forward_f32(const float *input, const float *sum, const float *sq_sum, const float *max, const float *min,
+                                  const float *node_table, int64_t n_query, const float *weight, const float *bias,
+                                  const float *ln_weight, const float *ln_bias, float ln_eps, float pna_eps, int relu,
+                                  int shortcut, float *out, int64_t rows, int64_t dim, void *stream);
 
 
 /*

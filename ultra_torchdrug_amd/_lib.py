@@ -159,6 +159,9 @@ SIGNATURES = {
     "ultra_rspmm_rotate_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]),
     "ultra_rspmm_rotate_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]),
     "ultra_rspmm_rotate_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
+    "ultra_rspmm_pna_workspace_bytes": (sz, [seg, i64]),
+    "ultra_rspmm_pna_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, vp]),
+    "ultra_pna_combine_forward_f32": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, f32, i32, i32, vp, i64, i64, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

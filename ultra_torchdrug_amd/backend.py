@@ -19,6 +19,11 @@ optional functions: a backend is an object with this complete interface
                                         ``accepts()`` is false gets ``functional.dense_set_boundary``, the same definition in
                                         torch ops)
 
+    pna_supported, pna_statistics, pna_node_table, pna_combine_forward
+                                       (reached ONLY on device tensors the backend accepts, in inference, with ``layer.PNA_NATIVE``
+                                        set: the one-walk statistics and the fused 13-wide epilogue of ``aggregate_func="pna"``;
+                                        every other backend and every other call keep the four ``generalized_rspmm`` calls)
+
 The parity tests install a second implementation of the same interface (``tests/oracle_ops.py``: the CPU oracle
 behind every operator) with :func:`use`, so that the SAME model code yields the oracle-side numbers; nothing under
 ``oracle/`` is imported from the package.

@@ -235,6 +235,85 @@ def rspmm_forward_csr(row_ptr, src, rel, weight, relation, input, sum="add", mul
     return out
 
 
+def pna_supported(csr):
+    """Whether :func:`pna_statistics` takes this adjacency: every plan but those that carry a dense form (the relation graphs,
+    whose sums run on the matrix cores in another documented order -- the four :func:`rspmm_forward` calls serve them)."""
+    return csr.fwd.dense is None
+
+
+def pna_statistics(csr, relation, input, mul="mul", add_rows=None, boundary=None):
+    """The four statistics of ``aggregate_func="pna"`` from one walk of the forward plan (``ultra_rspmm_pna_forward_f32``):
+    ``(4, n_rows, F)`` = sum, sum over the squared operands, max, min, each plane bit-identical to the :func:`rspmm_forward`
+    call it replaces (``ultra/layer.py:160-167,362-369``); ``add_rows`` / ``boundary = (node, value)`` fuse the boundary as
+    there: ``+ b``, ``+ b * b``, ``max(., b)``, ``min(., b)``.  Forward only, no autograd; HIP tensors only."""
+    if mul not in _lib.MUL_OPS:
+        raise ValueError("Can't find a rspmm operator for mul=`%s` (expected mul or add)" % mul)
+    _check_dense(csr, relation, input)
+    relation, input = relation.contiguous(), input.contiguous()
+    F = input.shape[1]
+    out = torch.empty(4, csr.shape[0], F, dtype=torch.float32, device=input.device)
+    add_rows, b_node, b_value = _check_boundary_epilogue(out[0], add_rows, boundary)
+    if not pna_supported(csr):
+        raise RuntimeError("pna_statistics: this adjacency carries a dense form (a relation graph); use four rspmm_forward calls")
+    if out.numel() == 0:
+        return out
+    seg = csr.fwd
+    n_ws = 4 * seg.workspace_rows * F
+    ws = torch.empty(n_ws, dtype=torch.float32, device=input.device) if n_ws else None
+    _launch(input.device, "ultra_rspmm_pna_forward_f32", seg.pointer, relation, input, add_rows, b_node, b_value,
+            b_value.shape[1] if b_value is not None else 0, out[0], out[1], out[2], out[3], ws, n_ws * 4, csr.shape[1],
+            csr.shape[2], F, _lib.MUL_OPS[mul])
+    return out
+
+
+def pna_node_table(degree_out):
+    """``(N, 3)`` fp32: degree, scale, inverse scale of every node, exactly as ``layer._pna`` computes them from
+    ``degree_out = graph.degree_out + 1`` (``ultra/layer.py:150-152``): ``log``, ``/ mean()``, ``1 / clamp(min=1e-2)``."""
+    degree = degree_out.reshape(-1, 1)
+    scale = degree.log()
+    scale = scale / scale.mean()
+    return torch.cat([degree, scale, 1 / scale.clamp(min=1e-2)], dim=-1).contiguous()
+
+
+def pna_combine_forward(input, statistics, node_table, weight, bias, ln_weight=None, ln_bias=None, ln_eps=1e-5, pna_eps=1e-6,
+                        relu=True, shortcut=False, out=None, n_query=None):
+    """Fused epilogue of a PNA layer, forward only (``ultra_pna_combine_forward_f32``): ``[input +] relu(LN(Linear(cat[input,
+    _pna(statistics)])))`` without the ``(N, B, 768)`` update tensor.  ``input`` ``(N, B, 64)``; ``statistics`` ``(4, N, B * 64)``
+    from :func:`pna_statistics` (or four ``(N, B * 64)`` tensors: sum, sq_sum, max, min, boundary included); ``node_table``
+    ``(N, 3)`` from :func:`pna_node_table`; ``weight`` ``(64, 832)``.  ``input`` may also be ``(rows, 64)`` with ``n_query`` given: row ``i``
+    is then (node ``i // n_query``, query ``i % n_query``) and ``node_table`` has ``ceil(rows / n_query)`` rows.  ``out``: an optional contiguous fp32 tensor of the input's shape to
+    write into; it must not share memory with ``input`` or a statistic (the kernel reads a row's tensors after other rows
+    have been written) -- that raises."""
+    planes = [t.contiguous() for t in statistics]
+    if n_query is None and input.dim() == 3:
+        n_query = input.shape[1]
+    rows = input.numel() // 64 if input.dim() >= 2 and input.shape[-1] == 64 else -1
+    if (rows < 0 or input.dim() not in (2, 3) or not n_query or n_query < 1 or (input.dim() == 3 and n_query != input.shape[1])
+            or tuple(weight.shape) != (64, 832) or len(planes) != 4 or any(t.numel() != input.numel() for t in planes)
+            or tuple(node_table.shape) != (-(-rows // n_query), 3) or tuple(bias.shape) != (64,)):
+        raise RuntimeError("pna_combine_forward handles 64 -> 64 layers with a (64, 832) weight: input (N, B, 64), four statistics of "
+                           "N * B * 64 elements, node_table (N, 3); got input %s, weight %s, node_table %s"
+                           % (tuple(input.shape), tuple(weight.shape), tuple(node_table.shape)))
+    tensors = [input, node_table, weight, bias] + planes + ([ln_weight, ln_bias] if ln_weight is not None else [])
+    if _not_fp32_on(input.device, tensors):
+        raise RuntimeError("pna_combine_forward needs fp32 tensors on one HIP device (no CPU fallback)")
+    input, node_table = input.contiguous(), node_table.contiguous()
+    if out is None:
+        out = torch.empty_like(input)
+    else:
+        if out.shape != input.shape or out.dtype != torch.float32 or out.device != input.device or not out.is_contiguous():
+            raise RuntimeError("pna_combine_forward: out must be a contiguous fp32 tensor of the input's shape on its device")
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * 4
+        if any(t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * 4 for t in [input] + planes):
+            raise RuntimeError("pna_combine_forward: out must not alias input or a statistic")
+    if out.numel() == 0:
+        return out
+    _launch(input.device, "ultra_pna_combine_forward_f32", input, *planes, node_table, int(n_query),
+            *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu)[:5], float(pna_eps), int(bool(relu)), int(bool(shortcut)),
+            out, input.numel() // 64, 64)
+    return out
+
+
 def frontier_supported(sum, mul, F):
     """The first-layer shortcut holds where a zero source row contributes exactly +-0: summed DistMult messages with a
     FINITE relation table (``inf * 0 = NaN`` in the full kernels; the caller tests the table, ``layer._frontier_tables_finite``)."""

@@ -11,6 +11,8 @@ unchanged.  The two reference classes repeat the same aggregation code; here it 
 :class:`_RelationalConvBase`.  ``forward = combine(input, message_and_aggregate(graph, input))`` is the contract
 of torchdrug's ``MessagePassingBase``.
 """
+import os
+
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -21,6 +23,11 @@ from . import backend
 # outside one row per query; with summed DistMult messages only the out-edges of those rows are visited.  Same bits as
 # the full kernel; the switch exists so that bench.py can report the step with and without it.
 FRONTIER_FIRST_LAYER = True
+
+# Native PNA inference (csrc/pna.hip; ULTRA_PNA_NATIVE=0 switches it off): on device tensors without grad the four statistics of
+# aggregate_func = "pna" come from ONE walk of the edges (`ops.pna_statistics`: the same bits as the four rspmm calls) and a
+# 64 -> 64 layer's epilogue runs fused over them (`ops.pna_combine_forward`: the same up to rounding).
+PNA_NATIVE = os.environ.get("ULTRA_PNA_NATIVE", "1") != "0"
 
 
 def _frontier_tables_finite(relation_input):
@@ -150,6 +157,8 @@ class _RelationalConvBase(nn.Module):
         fused = self._sum_layer(graph, input, shortcut, input_is_boundary, grad_tiles, grad_rows)
         if fused is not None:
             return fused
+        if self._pna_fusable(graph, input):
+            return self._pna_layer(graph, input, shortcut)
         update = self.message_and_aggregate(graph, input, input_is_boundary=input_is_boundary)
         if self._fusable(input, update):
             ln = self.layer_norm
@@ -216,6 +225,75 @@ class _RelationalConvBase(nn.Module):
                 and input.shape[-1] == 64 and self.output_dim == 64 and tuple(self.linear.weight.shape) == (64, 128)
                 and (self.activation is F.relu or not self.activation)
                 and (ln is None or (ln.elementwise_affine and ln.bias is not None)))
+
+    def _pna_fusable(self, graph, input):
+        """The fused PNA epilogue (``ops.pna_combine_forward``) covers the 64 -> 64 layer with its ``(64, 832)`` weight, relu or no
+        activation, an affine LayerNorm or none, in fp32 on the device without grad -- DistMult / TransE messages on a graph that
+        keeps the rspmm route, and a ``_pna`` that no instance attribute has replaced (tests hook it there)."""
+        ln = self.layer_norm
+        if not (PNA_NATIVE and self.aggregate_func in ("pna", "pna_nobound") and self.message_func in self.message2mul
+                and not graph.requires_grad and getattr(graph, "native_edge_weight", None) is None and "_pna" not in self.__dict__):
+            return False
+        if not (input.is_cuda and backend.get().accepts(input) and input.dtype == torch.float32 and input.dim() == 3
+                and input.shape[-1] == 64 and self.output_dim == 64 and tuple(self.linear.weight.shape) == (64, 832)
+                and self.linear.bias is not None and (self.activation is F.relu or not self.activation)
+                and (ln is None or (ln.elementwise_affine and ln.bias is not None))):
+            return False
+        parameters = [self.linear.weight, self.linear.bias] + ([ln.weight, ln.bias] if ln else [])
+        return self._no_grad(input, graph.boundary, *parameters)
+
+    def _pna_layer(self, graph, input, shortcut):
+        """``[input +] combine(input, message_and_aggregate(graph, input))`` of a PNA layer in inference without the ``(N, B, 768)``
+        update: statistics (one walk, or the four calls where the one-walk operator declines) -> fused epilogue."""
+        ops = backend.get()
+        relation_input = self._flat_relation_table(graph)
+        if not self._no_grad(relation_input):         # the autograd route
+            output = self.combine(input, self.message_and_aggregate(graph, input))
+            return output + input if shortcut else output
+        statistics = self._pna_statistics(graph, input.flatten(1), relation_input)
+        if statistics is None:
+            statistics = self._pna_four_calls(graph, input.flatten(1), relation_input)
+        ln = self.layer_norm
+        table = ops.pna_node_table(graph.degree_out.unsqueeze(-1) + 1)
+        return ops.pna_combine_forward(input, statistics, table, self.linear.weight, self.linear.bias,
+                                       ln.weight if ln else None, ln.bias if ln else None, ln.eps if ln else 1e-5,
+                                       pna_eps=self.eps, relu=self.activation is F.relu, shortcut=shortcut)
+
+    def _flat_relation_table(self, graph):
+        tables = getattr(graph, "relation_tables", None)       # all layers' tables from one launch (model.bellmanford)
+        if tables is not None and id(self) in tables:
+            return tables[id(self)]
+        return self._relation_table(graph, len(graph.query)).flatten(1)    # (R, B*D)
+
+    def _pna_statistics(self, graph, input, relation_input):
+        """``(sum, sq_sum, max, min)`` of the PNA aggregation over ``(N, B*D)`` inputs, boundary included, from the one-walk
+        operator -- or ``None`` where it does not apply (``PNA_NATIVE`` off, host tensors, grad, per-edge leaf weights, a plan in
+        its dense form) and the caller makes the four rspmm calls.  The same bits either way."""
+        ops = backend.get()
+        boundary = graph.boundary.flatten(1)
+        if not (PNA_NATIVE and input.is_cuda and ops.accepts(input) and input.dtype == torch.float32
+                and self._no_grad(input, relation_input, boundary) and getattr(graph, "native_edge_weight", None) is None
+                and self.message_func in self.message2mul and ops.pna_supported(graph.relcsr)):
+            return None
+        bound_args = {}
+        if not self.aggregate_func.endswith("_nobound"):
+            sparse_bound = getattr(graph, "boundary_sparse", None)
+            bound_args = dict(add_rows=boundary) if sparse_bound is None else dict(boundary=sparse_bound)
+        return ops.pna_statistics(graph.relcsr, relation_input, input, self.message2mul[self.message_func], **bound_args)
+
+    def _pna_four_calls(self, graph, input, relation_input):
+        """The same four statistics as the reference spells them (``ultra/layer.py:160-170,362-372``): four rspmm calls, the
+        boundary applied by ATen."""
+        rspmm, adjacency, mul = backend.get().generalized_rspmm, graph.relcsr, self.message2mul[self.message_func]
+        sum = rspmm(adjacency, relation_input, input, sum="add", mul=mul)
+        sq_sum = rspmm(adjacency, relation_input ** 2, input ** 2, sum="add", mul=mul)
+        max = rspmm(adjacency, relation_input, input, sum="max", mul=mul)
+        min = rspmm(adjacency, relation_input, input, sum="min", mul=mul)
+        if not self.aggregate_func.endswith("_nobound"):
+            boundary = graph.boundary.flatten(1)
+            sum, sq_sum = sum + boundary, sq_sum + boundary ** 2
+            max, min = torch.max(max, boundary), torch.min(min, boundary)
+        return sum, sq_sum, max, min
 
     # ---- O(E) definition, used for rotate / graphs that require grad (layer.py:52-109, :232-296) ---------
     def message(self, graph, input):
@@ -343,13 +421,10 @@ class _RelationalConvBase(nn.Module):
                 if bound:
                     update = torch.max(update, boundary)
         else:
-            sum = rspmm(adjacency, relation_input, input, sum="add", mul=mul)
-            sq_sum = rspmm(adjacency, relation_input ** 2, input ** 2, sum="add", mul=mul)
-            max = rspmm(adjacency, relation_input, input, sum="max", mul=mul)
-            min = rspmm(adjacency, relation_input, input, sum="min", mul=mul)
-            if bound:
-                sum, sq_sum = sum + boundary, sq_sum + boundary ** 2
-                max, min = torch.max(max, boundary), torch.min(min, boundary)
+            statistics = self._pna_statistics(graph, input, relation_input)      # one walk of the edges, boundary fused
+            if statistics is None:
+                statistics = self._pna_four_calls(graph, input, relation_input)
+            sum, sq_sum, max, min = statistics
             update = self._pna(sum / degree_out, sq_sum / degree_out, max, min, degree_out)
         return update.view(len(update), batch_size, -1)
 
