@@ -368,6 +368,22 @@ int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd_host, const float 
                                     int64_t n_rel, int64_t F, int sum_op, int mul_op, void *stream);
 
 /*
+ * The same gradient per query block of `block` columns (TransferNBFNet.edge_gradients_batch: the queries of a batch are
+ * independent column blocks, and only this contraction over the columns would mix them):
+ *     d_weight[b][e] = the sum of ultra_rspmm_backward_weight_f32 restricted to columns b * block .. (b + 1) * block - 1
+ * d_weight is fp32 [F / block][n_edges], query-major, written completely; min / max masking and the unit-weight form as there.
+ * The order is fixed: one wave per edge walks the blocks; within a block lane l accumulates columns l, l + 64, ... of the block
+ * in ascending order, then the __shfl_down tree 32, 16, 8, 4, 2, 1.  Slice [b] is therefore bit for bit what
+ * ultra_rspmm_backward_weight_f32 returns on a contiguous copy of that block's columns (F = block).
+ * Errors, all before any device work: ULTRA_ERR_ABI for a foreign plan; ULTRA_ERR_BAD_SHAPE for F <= 0, block <= 0 or
+ * F % block != 0; ULTRA_ERR_BAD_OP for an unknown op; ULTRA_ERR_NULL_POINTER as in ultra_rspmm_backward_weight_f32.  A plan
+ * without edges returns ULTRA_OK.
+ */
+int ultra_rspmm_backward_weight_blocks_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
+                                           const float *output, const float *output_grad, float *d_weight, int64_t n_rel,
+                                           int64_t F, int64_t block, int sum_op, int mul_op, void *stream);
+
+/*
  * rspmm with RotatE messages (layer.message for message_func = "rotate", /root/reference/ultra/layer.py:69-75, :256-262):
  * each query block of `block` columns (even) is `block / 2` complex pairs, real part in column c = b * block + d, imaginary part
  * in c + block / 2 (d < block / 2), and the message of an edge is w * (input[src] (complex *) relation[rel]) per pair:
@@ -404,6 +420,16 @@ int ultra_rspmm_rotate_backward_f32(const ultra_segments *by_src_host, const ult
 int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
                                            const float *output, const float *output_grad, float *d_weight, int64_t n_rel,
                                            int64_t F, int64_t block, int sum_op, void *stream);
+
+/* The same gradient per query block: d_weight fp32 [F / block][n_edges], query-major, written completely;
+ *     d_weight[b][e] = the sum above over the block / 2 pairs of query block b alone.
+ * `block` is the (even) query width of the rotate entries.  One wave per edge walks the blocks in the order
+ * ultra_rspmm_rotate_backward_weight_f32 takes on that block's columns alone (lane l sums pairs l, l + 64, ... of the block, then
+ * the __shfl_down tree from 32; block / 2 <= 32: lanes 0 .. 31 hold the pairs and the tree starts at 16), so slice [b] equals
+ * that entry on a contiguous copy of block b's columns (F = block) bit for bit.  Errors as there, all before any device work. */
+int ultra_rspmm_rotate_backward_weight_blocks_f32(const ultra_segments *fwd_host, const float *relation, const float *input,
+                                                  const float *output, const float *output_grad, float *d_weight,
+                                                  int64_t n_rel, int64_t F, int64_t block, int sum_op, void *stream);
 
 /*
  * The four statistics of aggregate_func = "pna" from ONE walk of the forward plan (csrc/pna.hip; DESIGN.md "Native PNA
@@ -453,6 +479,18 @@ int ultra_rspmm_pna_forward_f32(const ultra_segments *fwd_host, const float *rel
 int ultra_beam_search_step_f32(const int32_t *row_ptr, const int32_t *src, const float *edge_grad, const float *input,
                                int64_t n_node, int64_t n_edges, int64_t tail, int64_t K, float *distance,
                                int32_t *back_edge, int32_t *back_rank, void *stream);
+
+/*
+ * The same step for n_query queries over one graph in one launch (TransferNBFNet.visualize_batch):
+ *   edge_grad fp32 [n_query][n_edges], input fp32 [n_query][n_node][K], tails int32 [n_query] IN DEVICE MEMORY (no host read)
+ *   distance / back_edge / back_rank [n_query][n_node][K], written completely
+ * Query b's slices are exactly what ultra_beam_search_step_f32 gives for (edge_grad[b], input[b], tails[b]): the same row code,
+ * the query a second grid dimension, 64-bit offsets into the batched arrays, lanes per row from the mean degree as there.  A
+ * tail outside [0, n_node) masks no edge.  1 <= K <= 32 and 1 <= n_query <= 65535, else ULTRA_ERR_BAD_SHAPE.
+ */
+int ultra_beam_search_step_batch_f32(const int32_t *row_ptr, const int32_t *src, const float *edge_grad, const float *input,
+                                     const int32_t *tails, int64_t n_node, int64_t n_edges, int64_t n_query, int64_t K,
+                                     float *distance, int32_t *back_edge, int32_t *back_rank, void *stream);
 
 /*
  * Hop distances from many sources: bit-parallel multi-source BFS (csrc/hop_distance.hip).

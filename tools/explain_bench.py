@@ -19,6 +19,20 @@ tensor is 25.6 GB.  Reported:
     rows) against its byte floor: three rows of ``F`` floats (input, relation, output gradient), the three index words and the
     ``d_weight`` word per edge, ``E (12 F + 16)``.
 Prints one JSON object; a workload that fails records the error instead of a result.
+
+    python tools/explain_bench.py --batch [B] [--workloads S-fb15k237] [--messages distmult] [--beams 10] [--json PATH]
+
+``--batch`` (``B`` = 16 when not given): the batched explanation instead of the above.  Per workload and message function, in ONE
+run and alternating (three alternations of the two legs; each figure the median of 5 calls after 2 warm-up calls of its own, device
+events around the call, which ends in a synchronise):
+  * ``looped``: ``B`` ``visualize`` calls, one per triple;  ``batched``: ONE ``visualize_batch`` of the same ``B`` triples;
+  * per leg ``ms_per_triple`` and its split: ``gradient_ms_per_triple`` (``edge_gradients`` x B / ``edge_gradients_batch``) and
+    ``search_ms_per_triple`` (the rest: beam search, path assembly, host sort);
+  * ``ratio``: batched over looped time per triple (below 1: the batch is faster), per alternation and of the medians;
+  * ``batched_peak_extra_bytes`` beside ``B * E * 64 * 4``, one batched message tensor;  ``same_paths``: how many of the ``B``
+    results name the same paths as their single-triple call (the batched score head may differ from it in the last bits).
+Written to ``profiles/explain_batch_bench.json`` unless ``--json`` names another file.  Activation memory grows with ``B``: on
+S-stress use ``--batch 2`` or leave the workload out.
 """
 import argparse
 import ctypes
@@ -166,6 +180,71 @@ def run(workload, dev, reps, beams_k, message="distmult", materialised=False):
     return rec
 
 
+def _event_ms(fn):
+    """Device time of ``fn()`` between two events; the call is followed by a synchronise."""
+    stream = torch.cuda.current_stream()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record(stream)
+    out = fn()
+    b.record(stream)
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def _median_ms(fn, reps=5, warmup=2):
+    for _ in range(warmup):
+        _event_ms(fn)
+    times = sorted(_event_ms(fn)[0] for _ in range(reps))
+    return times[len(times) // 2]
+
+
+def run_batch(workload, dev, n_query, beams_k, message="distmult", alternations=3):
+    rec = {"workload": workload, "message": message, "B": n_query, "num_beam": beams_k, "timing": "device events; median of 5 "
+           "after 2 warm-ups per figure; %d alternations of the two legs in one run" % alternations}
+    graph, model, _ = build(workload, dev, message)
+    model.num_beam, model.path_topk = beams_k, 10
+    csr = model._undirected(graph).relcsr
+    _ = csr.csr_arrays, csr.fwd, csr.by_src, csr.by_rel
+    rec["N"], rec["E"] = graph.num_node, csr.n_edges
+    rel = torch.randn(n_query, 2 * graph.num_relation, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    rows = torch.arange(n_query, device=dev) * (len(graph.edge_list) // n_query)         # spread over the edge list
+    h, t, r = (graph.edge_list[rows, c] for c in range(3))
+    rec["triples"] = torch.stack([h, t, r], 1).tolist()
+    one = lambda b: ([rel[b:b + 1]], h[b:b + 1], t[b:b + 1], r[b:b + 1])
+    legs = {
+        "looped": (lambda: [model.edge_gradients(graph, *one(b)) for b in range(n_query)],
+                   lambda: [model.visualize(graph, *one(b)) for b in range(n_query)]),
+        "batched": (lambda: model.edge_gradients_batch(graph, [rel], h, t, r),
+                    lambda: model.visualize_batch(graph, [rel], h, t, r)),
+    }
+    rounds = []
+    for _ in range(alternations):
+        entry = {}
+        for name, (gradients, whole) in legs.items():
+            g_ms, v_ms = _median_ms(gradients), _median_ms(whole)
+            entry[name] = {"ms_per_triple": v_ms / n_query, "gradient_ms_per_triple": g_ms / n_query,
+                           "search_ms_per_triple": (v_ms - g_ms) / n_query}
+        entry["ratio"] = entry["batched"]["ms_per_triple"] / entry["looped"]["ms_per_triple"]
+        rounds.append(entry)
+    rec["alternations"] = rounds
+    median = lambda xs: sorted(xs)[len(xs) // 2]
+    for name in legs:
+        rec[name] = {key: median([e[name][key] for e in rounds]) for key in rounds[0][name]}
+    rec["ratio"] = rec["batched"]["ms_per_triple"] / rec["looped"]["ms_per_triple"]
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    batched = legs["batched"][1]()
+    torch.cuda.synchronize()
+    rec["batched_peak_extra_bytes"] = int(torch.cuda.max_memory_allocated() - base)
+    rec["one_batched_message_tensor_bytes"] = n_query * csr.n_edges * 64 * 4
+    looped = legs["looped"][1]()
+    rec["same_paths"] = sum(int(a[0] == b[0]) for a, b in zip(batched, looped))
+    rec["n_paths"] = [len(p) for p, _ in batched]
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="S-fb15k237,S-stress")
@@ -174,7 +253,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--beams", type=int, default=10)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--batch", type=int, nargs="?", const=16, default=None,
+                    help="time B looped visualize calls against one visualize_batch (B = 16 when no value is given)")
     args = ap.parse_args()
+    if args.batch is not None and args.batch < 1:
+        raise SystemExit("--batch needs a positive number of triples")
     import ultra_torchdrug_amd as U
     U.require_library()
     if not torch.cuda.is_available():
@@ -182,6 +265,25 @@ def main():
     dev = torch.device("cuda:0")
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     from ultra_torchdrug_amd.layer import _RelationalConvBase
+    if args.batch is not None:
+        out["batch"] = args.batch
+        for workload in args.workloads.split(","):
+            for message in args.messages.split(","):
+                try:
+                    out["results"].append(run_batch(workload, dev, args.batch, args.beams, message))
+                except Exception as err:        # (out of memory: activation memory grows with B): recorded, not hidden
+                    out["results"].append({"workload": workload, "message": message, "B": args.batch,
+                                           "error": "%s: %s" % (type(err).__name__, err)})
+                torch.cuda.empty_cache()
+                print(json.dumps(out["results"][-1]), file=sys.stderr, flush=True)
+        text = json.dumps(out, indent=1)
+        print(text)
+        path = args.json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                         "explain_batch_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+        return
     legs = [(w, m, False) for w in args.workloads.split(",") for m in args.messages.split(",")]
     legs += [(w, m, True) for w in args.materialised.split(",") if w for m in args.messages.split(",")]
     native_edge_grad = _RelationalConvBase.native_edge_grad

@@ -88,7 +88,9 @@ SIGNATURES = {
     "ultra_rspmm_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]),
     "ultra_rspmm_backward_accumulate_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, i32, vp]),
     "ultra_rspmm_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]),
+    "ultra_rspmm_backward_weight_blocks_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]),
     "ultra_beam_search_step_f32": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]),
+    "ultra_beam_search_step_batch_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]),
     "ultra_hop_distance_workspace": (sz, [i64]),
     "ultra_hop_distance": (i32, [vp, vp, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, i32, vp, sz, vp]),
     "ultra_rspmm_backward_active_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp, i64, vp, vp]),
@@ -159,6 +161,7 @@ SIGNATURES = {
     "ultra_rspmm_rotate_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i32, vp]),
     "ultra_rspmm_rotate_backward_f32": (i32, [seg, seg, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, i64, i32, vp]),
     "ultra_rspmm_rotate_backward_weight_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
+    "ultra_rspmm_rotate_backward_weight_blocks_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]),
     "ultra_rspmm_pna_workspace_bytes": (sz, [seg, i64]),
     "ultra_rspmm_pna_forward_f32": (i32, [seg, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, i64, i64, i64, i32, vp]),
     "ultra_pna_combine_forward_f32": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, f32, f32, i32, i32, vp, i64, i64, vp]),

@@ -7,6 +7,9 @@ optional functions: a backend is an object with this complete interface
     accepts(tensor) -> bool            tensors this backend computes on (HIP library: ``tensor.is_cuda``)
     generalized_rspmm, rspmm_forward, rspmm_sum_plus, rspmm_frontier, frontier_supported, first_layer_forward, sum_layer,
     remove_triples, rotate_rspmm (with ``edge_weight=``, as generalized_rspmm), rotate_rspmm_forward, rotate_rspmm_backward_weight
+    rspmm_backward_weight_blocks, rotate_rspmm_backward_weight_blocks, beam_search_step_batch   (the per-query twins of
+                                       rspmm_backward_weight / rotate_rspmm_backward_weight / beam_search_step behind
+                                       ``edge_gradients_batch`` / ``visualize_batch``)
     combine, linear_supported, linear_forward, relation_project, relation_project_train, score_all_entities
     filtered_rank, filtered_rank_keys, strict_negatives, statistics, bce_adversarial_loss, candidate_tiles, candidate_rows,
     score_candidates_supported, score_candidates

@@ -1,5 +1,5 @@
-// beam_search.hip -- one step of the path beam search behind TransferNBFNet.visualize (a translation unit of
-// libultra_rspmm.so; C ABI: ultra_beam_search_step_f32 in include/ultra_rspmm.h).
+// beam_search.hip -- one step of the path beam search behind TransferNBFNet.visualize / visualize_batch (a translation unit
+// of libultra_rspmm.so; C ABI: ultra_beam_search_step_f32 and ultra_beam_search_step_batch_f32 in include/ultra_rspmm.h).
 //
 // For every destination row v of the coalesced dst-CSR, the K best of the row's (in-edge, source beam) candidates
 //     m = input[u, k] + g[e]          (e = u -> v, u != tail, m finite; one f32 add)
@@ -45,14 +45,12 @@ __device__ __forceinline__ bool near_equal(float a, float b) {
     return d <= tol;
 }
 
+// One destination row of one query: the row code of both kernels below (`grad`, `input` and the outputs are the query's own).
 template <int G, int KMAX>
-__global__ __launch_bounds__(kThreads) void beam_step_kernel(const int32_t *__restrict__ row_ptr,
-                                                             const int32_t *__restrict__ src,
-                                                             const float *__restrict__ grad,
-                                                             const float *__restrict__ input, long long n_node,
-                                                             long long n_edges, long long tail, int K,
-                                                             float *__restrict__ distance, int32_t *__restrict__ back_edge,
-                                                             int32_t *__restrict__ back_rank) {
+__device__ __forceinline__ void beam_row(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ src,
+                                         const float *__restrict__ grad, const float *__restrict__ input, long long n_node,
+                                         long long n_edges, long long tail, int K, float *__restrict__ distance,
+                                         int32_t *__restrict__ back_edge, int32_t *__restrict__ back_rank) {
     const long long v = ((long long)blockIdx.x * kThreads + threadIdx.x) / G;
     const int lane = (int)(threadIdx.x % G);
     if (v >= n_node) return;            // whole groups leave together (G divides the block)
@@ -145,6 +143,35 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(const int32_t *__re
     }
 }
 
+template <int G, int KMAX>
+__global__ __launch_bounds__(kThreads) void beam_step_kernel(const int32_t *__restrict__ row_ptr,
+                                                             const int32_t *__restrict__ src,
+                                                             const float *__restrict__ grad,
+                                                             const float *__restrict__ input, long long n_node,
+                                                             long long n_edges, long long tail, int K,
+                                                             float *__restrict__ distance, int32_t *__restrict__ back_edge,
+                                                             int32_t *__restrict__ back_rank) {
+    beam_row<G, KMAX>(row_ptr, src, grad, input, n_node, n_edges, tail, K, distance, back_edge, back_rank);
+}
+
+// The same step for n_query queries over one graph: blockIdx.y is the query, whose slices of the batched arrays start at
+// 64-bit offsets (q * n_edges, q * n_node * K); its tail comes from device memory.  B groups stand on every row at once, so
+// the tail of a hub row is shared by the batch instead of paid once per query.
+template <int G, int KMAX>
+__global__ __launch_bounds__(kThreads) void beam_step_batch_kernel(const int32_t *__restrict__ row_ptr,
+                                                                   const int32_t *__restrict__ src,
+                                                                   const float *__restrict__ grad,
+                                                                   const float *__restrict__ input,
+                                                                   const int32_t *__restrict__ tails, long long n_node,
+                                                                   long long n_edges, int K, float *__restrict__ distance,
+                                                                   int32_t *__restrict__ back_edge,
+                                                                   int32_t *__restrict__ back_rank) {
+    const long long q = blockIdx.y;
+    const long long eo = q * n_edges, no = q * n_node * K;
+    beam_row<G, KMAX>(row_ptr, src, grad + eo, input + no, n_node, n_edges, (long long)tails[q], K, distance + no,
+                      back_edge + no, back_rank + no);
+}
+
 template <int G>
 int launch_g(const int32_t *row_ptr, const int32_t *src, const float *grad, const float *input, long long n_node,
              long long n_edges, long long tail, int K, float *distance, int32_t *back_edge, int32_t *back_rank,
@@ -155,6 +182,25 @@ int launch_g(const int32_t *row_ptr, const int32_t *src, const float *grad, cons
 #define ULTRA_BEAM_LAUNCH(KM)                                                                                           \
     hipLaunchKernelGGL((beam_step_kernel<G, KM>), grid, block, 0, s, row_ptr, src, grad, input, n_node, n_edges, tail, \
                        K, distance, back_edge, back_rank)
+    if (K <= 4) ULTRA_BEAM_LAUNCH(4);
+    else if (K <= 8) ULTRA_BEAM_LAUNCH(8);
+    else if (K <= 16) ULTRA_BEAM_LAUNCH(16);
+    else ULTRA_BEAM_LAUNCH(32);
+#undef ULTRA_BEAM_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+template <int G>
+int launch_batch_g(const int32_t *row_ptr, const int32_t *src, const float *grad, const float *input, const int32_t *tails,
+                   long long n_node, long long n_edges, long long n_query, int K, float *distance, int32_t *back_edge,
+                   int32_t *back_rank, hipStream_t s) {
+    const long long blocks = (n_node * G + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffffll) return ULTRA_ERR_BAD_SHAPE;
+    const dim3 grid((unsigned)blocks, (unsigned)n_query), block(kThreads);
+#define ULTRA_BEAM_LAUNCH(KM)                                                                                             \
+    hipLaunchKernelGGL((beam_step_batch_kernel<G, KM>), grid, block, 0, s, row_ptr, src, grad, input, tails, n_node,     \
+                       n_edges, K, distance, back_edge, back_rank)
     if (K <= 4) ULTRA_BEAM_LAUNCH(4);
     else if (K <= 8) ULTRA_BEAM_LAUNCH(8);
     else if (K <= 16) ULTRA_BEAM_LAUNCH(16);
@@ -183,4 +229,24 @@ extern "C" int ultra_beam_search_step_f32(const int32_t *row_ptr, const int32_t 
     if (mean >= 24)
         return launch_g<32>(row_ptr, src, edge_grad, input, n_node, n_edges, tail, (int)K, distance, back_edge, back_rank, s);
     return launch_g<16>(row_ptr, src, edge_grad, input, n_node, n_edges, tail, (int)K, distance, back_edge, back_rank, s);
+}
+
+extern "C" int ultra_beam_search_step_batch_f32(const int32_t *row_ptr, const int32_t *src, const float *edge_grad,
+                                                const float *input, const int32_t *tails, int64_t n_node, int64_t n_edges,
+                                                int64_t n_query, int64_t K, float *distance, int32_t *back_edge,
+                                                int32_t *back_rank, void *stream) {
+    if (K < 1 || K > 32 || n_query < 1 || n_query > 65535 || n_node < 0 || n_edges < 0 || n_edges > 0x7fffffffll ||
+        n_node > 0x7fffffffll)
+        return ULTRA_ERR_BAD_SHAPE;                  // (the query is the grid's y dimension)
+    if (n_node == 0) return ULTRA_OK;
+    if (row_ptr == nullptr || input == nullptr || tails == nullptr || distance == nullptr || back_edge == nullptr ||
+        back_rank == nullptr || (n_edges > 0 && (src == nullptr || edge_grad == nullptr)))
+        return ULTRA_ERR_NULL_POINTER;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long mean = n_edges / n_node;         // lanes per row: as the single step
+    if (mean >= 48)
+        return launch_batch_g<64>(row_ptr, src, edge_grad, input, tails, n_node, n_edges, n_query, (int)K, distance, back_edge, back_rank, s);
+    if (mean >= 24)
+        return launch_batch_g<32>(row_ptr, src, edge_grad, input, tails, n_node, n_edges, n_query, (int)K, distance, back_edge, back_rank, s);
+    return launch_batch_g<16>(row_ptr, src, edge_grad, input, tails, n_node, n_edges, n_query, (int)K, distance, back_edge, back_rank, s);
 }

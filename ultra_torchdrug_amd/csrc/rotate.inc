@@ -400,3 +400,71 @@ int launch_rotate_weight_grad(const ultra_segments *fwd, const float *relation, 
         });
     });
 }
+
+// rotate_weight_grad_kernel per query block (ultra_rspmm_rotate_backward_weight_blocks_f32): d_weight[b][e] = the sum above
+// over the `half` pairs of query block b alone, query-major, every entry written.  One wave per edge -- ids and weight are read
+// once -- walking the blocks in the order rotate_weight_grad_kernel takes on that block's columns alone, so that slice [b]
+// carries its bits: lane l sums pairs l, l + 64, ... of the block, then the __shfl_down tree from 32.  TWO (half <= 32, as
+// there): one block per 32-lane half of the wave -- blocks 2 i and 2 i + 1 together, a 128-byte half row per load and half
+// -- and the tree stops at offset 16.  (The trip count is the wave's: an odd last block leaves the upper half idle, not out.)
+template <int SUM, bool UNIT_W, bool TWO>
+__global__ __launch_bounds__(256) void rotate_weight_grad_blocks_kernel(const int32_t *row, const int32_t *src, const int32_t *rel,
+                                                                        const float *weight, const float *relation,
+                                                                        const float *input, const float *output,
+                                                                        const float *grad, float *d_weight, long long F,
+                                                                        int half, long long n_blocks, long long n_edges) {
+    constexpr int G = TWO ? 32 : 64;                 // lanes per block
+    constexpr int STEP = TWO ? 2 : 1;                // blocks per wave and trip
+    const int lane = threadIdx.x & 63;
+    const int sub = TWO ? (lane >> 5) : 0;
+    const int l = lane & (G - 1);
+    const long long waves_total = ((long long)gridDim.x * blockDim.x) >> 6;
+    long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    for (; e < n_edges; e += waves_total) {
+        const long long v = row[e], u = src[e], r = rel[e];
+        float wk = 1.0f;
+        if constexpr (!UNIT_W) wk = weight[e];
+        for (long long b0 = 0; b0 < n_blocks; b0 += STEP) {
+            const long long bq = b0 + sub;
+            const bool live = bq < n_blocks;
+            float acc = 0.0f;
+            if (live) {
+                for (int pair = l; pair < half; pair += G) {
+                    const long long cre = bq * (2 * half) + pair;
+                    const long long cim = cre + half;
+                    float yr, yi;
+                    rotate_message(input[u * F + cre], input[u * F + cim], relation[r * F + cre], relation[r * F + cim], yr, yi);
+                    float gr = grad[v * F + cre], gi = grad[v * F + cim];
+                    if constexpr (SUM != ULTRA_SUM_ADD) {
+                        float mr = yr, mi = yi;
+                        if constexpr (!UNIT_W) { mr = wk * yr; mi = wk * yi; }
+                        gr = gr * ((output[v * F + cre] == mr) ? 1.0f : 0.0f);
+                        gi = gi * ((output[v * F + cim] == mi) ? 1.0f : 0.0f);
+                    }
+                    const float a = gr * yr, b = gi * yi;
+                    acc = acc + (a + b);
+                }
+            }
+#pragma unroll
+            for (int off = G / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+            if (l == 0 && live) d_weight[bq * n_edges + e] = acc;
+        }
+    }
+}
+
+template <int SUM>
+int launch_rotate_weight_grad_blocks(const ultra_segments *fwd, const float *relation, const float *input, const float *output,
+                                     const float *grad, float *d_weight, long long F, int half, hipStream_t s) {
+    const bool two = half <= 32, unit = fwd->weight == nullptr;
+    long long blocks = (fwd->n_edges + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    return with_bool(unit, [&](auto uw) {
+        return with_bool(two, [&](auto tw) -> int {
+            hipLaunchKernelGGL((rotate_weight_grad_blocks_kernel<SUM, decltype(uw)::value, decltype(tw)::value>), dim3((int)blocks),
+                               dim3(256), 0, s, fwd->row, fwd->node_a, fwd->rel, fwd->weight, relation, input, output, grad, d_weight,
+                               F, half, F / (2 * half), (long long)fwd->n_edges);
+            HIP_TRY(hipGetLastError());
+            return ULTRA_OK;
+        });
+    });
+}

@@ -649,6 +649,43 @@ __global__ __launch_bounds__(256) void weight_grad_kernel(const int32_t *row, co
     }
 }
 
+// weight_grad_kernel per query block: d_weight[b][e] = the sum above over columns b * block .. (b + 1) * block - 1 alone
+// (ultra_rspmm_backward_weight_blocks_f32).  Still one wave per edge -- ids and weight are read once -- walking the blocks;
+// within a block lane l takes columns l, l + 64, ... of the block, then the same __shfl_down tree: slice [b] carries the bits
+// weight_grad_kernel gives on a contiguous copy of the block's columns.
+template <int SUM, int MUL, bool UNIT_W>
+__global__ __launch_bounds__(256) void weight_grad_blocks_kernel(const int32_t *row, const int32_t *src, const int32_t *rel,
+                                                                 const float *weight, const float *relation,
+                                                                 const float *input, const float *output, const float *grad,
+                                                                 float *d_weight, long long F, long long block,
+                                                                 long long n_blocks, long long n_edges) {
+    const int lane = threadIdx.x & 63;
+    const long long waves_total = ((long long)gridDim.x * blockDim.x) >> 6;
+    long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    for (; e < n_edges; e += waves_total) {
+        const int v = row[e], u = src[e], r = rel[e];
+        float wk = 1.0f;
+        if constexpr (!UNIT_W) wk = weight[e];
+        for (long long b = 0; b < n_blocks; ++b) {
+            const long long c0 = b * block;
+            float acc = 0.0f;
+            for (long long f = lane; f < block; f += 64) {
+                const float m = binary<MUL>(relation[(long long)r * F + c0 + f], input[(long long)u * F + c0 + f]);
+                float g = grad[(long long)v * F + c0 + f];
+                if constexpr (SUM != ULTRA_SUM_ADD) {
+                    float y = m;
+                    if constexpr (!UNIT_W) y = wk * m;
+                    g = g * ((output[(long long)v * F + c0 + f] == y) ? 1.0f : 0.0f);
+                }
+                acc = acc + g * m;
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+            if (lane == 0) d_weight[b * n_edges + e] = acc;
+        }
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // combine_kernel: the dense epilogue of one Bellman-Ford layer, fused.
@@ -2282,6 +2319,34 @@ int ultra_rspmm_backward_weight_f32(const ultra_segments *fwd, const float *rela
     });
 }
 
+int ultra_rspmm_backward_weight_blocks_f32(const ultra_segments *fwd, const float *relation, const float *input,
+                                           const float *output, const float *output_grad, float *d_weight, int64_t n_rel,
+                                           int64_t F, int64_t block, int sum_op, int mul_op, void *stream) {
+    int rc = check_segments(fwd);
+    if (rc) return rc;
+    (void)n_rel;
+    if (F <= 0 || block <= 0 || F % block != 0) return ULTRA_ERR_BAD_SHAPE;
+    if (sum_op < 0 || sum_op > 2 || mul_op < 0 || mul_op > 1) return ULTRA_ERR_BAD_OP;
+    if (fwd->n_edges == 0) return ULTRA_OK;
+    if (relation == nullptr || input == nullptr || output_grad == nullptr || d_weight == nullptr)
+        return ULTRA_ERR_NULL_POINTER;
+    if (sum_op != ULTRA_SUM_ADD && output == nullptr) return ULTRA_ERR_NULL_POINTER;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool unit = fwd->weight == nullptr;
+    long long blocks = (fwd->n_edges + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    return with_sum_mul(sum_op, mul_op, [&](auto sum, auto mul) {
+        return with_bool(unit, [&](auto uw) -> int {
+            hipLaunchKernelGGL((weight_grad_blocks_kernel<decltype(sum)::value, decltype(mul)::value, decltype(uw)::value>),
+                               dim3((int)blocks), dim3(256), 0, s, fwd->row, fwd->node_a, fwd->rel, fwd->weight, relation, input,
+                               output, output_grad, d_weight, (long long)F, (long long)block, (long long)(F / block),
+                               (long long)fwd->n_edges);
+            HIP_TRY(hipGetLastError());
+            return ULTRA_OK;
+        });
+    });
+}
+
 // rspmm with rotate messages (rotate.inc)
 int ultra_rspmm_rotate_forward_f32(const ultra_segments *fwd, const float *relation, const float *input,
                                    const float *add_rows, const int32_t *boundary_node, const float *boundary_value,
@@ -2352,6 +2417,25 @@ int ultra_rspmm_rotate_backward_weight_f32(const ultra_segments *fwd, const floa
     const int half = (int)(block / 2);
     return with_sum(sum_op, [&](auto sum) {
         return launch_rotate_weight_grad<decltype(sum)::value>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
+    });
+}
+
+int ultra_rspmm_rotate_backward_weight_blocks_f32(const ultra_segments *fwd, const float *relation, const float *input,
+                                                  const float *output, const float *output_grad, float *d_weight,
+                                                  int64_t n_rel, int64_t F, int64_t block, int sum_op, void *stream) {
+    int rc = check_segments(fwd);
+    if (rc) return rc;
+    (void)n_rel;
+    if (F <= 0 || F > 0x7ffffffeLL || block <= 0 || block % 2 != 0 || F % block != 0) return ULTRA_ERR_BAD_SHAPE;
+    if (sum_op < 0 || sum_op > 2) return ULTRA_ERR_BAD_OP;
+    if (fwd->n_edges == 0) return ULTRA_OK;
+    if (relation == nullptr || input == nullptr || output_grad == nullptr || d_weight == nullptr)
+        return ULTRA_ERR_NULL_POINTER;
+    if (sum_op != ULTRA_SUM_ADD && output == nullptr) return ULTRA_ERR_NULL_POINTER;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int half = (int)(block / 2);
+    return with_sum(sum_op, [&](auto sum) {
+        return launch_rotate_weight_grad_blocks<decltype(sum)::value>(fwd, relation, input, output, output_grad, d_weight, F, half, s);
     });
 }
 

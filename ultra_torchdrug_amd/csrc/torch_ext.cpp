@@ -22,6 +22,7 @@
 //   ultra_mi::rspmm_bwd(row_ptr, src, rel, w?, relation, input, output, output_grad, sum_op, mul_op)
 //       -> (d_relation, d_input)
 //   ultra_mi::beam_search_step(row_ptr, src, edge_grad, input, tail) -> (distance, back_edge, back_rank)
+//   ultra_mi::beam_search_step_batch(row_ptr, src, edge_grad (B, E), input (B, N, K), tails (B,)) -> the same, per query
 //       one layer of the path beam search of TransferNBFNet.visualize (CUDA and CPU keys)
 //   ultra_mi::hop_distance(row_ptr, src, w?, sources, num_iters, targets?) -> Tensor
 //       hop distances from many sources, int32 (N, B) or -- with targets (B, K) -- int32 (B, K) (CUDA and CPU keys)
@@ -1015,20 +1016,9 @@ inline bool beam_near_equal(float a, float b) {
     return d <= tol;
 }
 
-std::tuple<Tensor, Tensor, Tensor> beam_search_step_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
-                                                        const Tensor &input, int64_t tail) {
-    for (const Tensor *t : {&row_ptr, &src, &edge_grad, &input})
-        TORCH_CHECK(t->device().is_cpu(), "ultra_mi (CPU): beam_search_step: all tensors must share a device");
-    const BeamArgs a = check_beam(row_ptr, src, edge_grad, input, tail);
-    const int64_t N = a.n_node, K = a.K;
-    Tensor distance = at::empty({N, K}, input.options());
-    Tensor back_edge = at::empty({N, K}, row_ptr.options()), back_rank = at::empty({N, K}, row_ptr.options());
-    if (N == 0) return {distance, back_edge, back_rank};
-    const Tensor rp_t = row_ptr.contiguous(), s_t = src.contiguous(), g_t = edge_grad.contiguous(), x_t = input.contiguous();
-    const int *rp = rp_t.data_ptr<int>(), *sp = s_t.data_ptr<int>();
-    const float *gp = g_t.data_ptr<float>(), *xp = x_t.data_ptr<float>();
-    float *dp = distance.data_ptr<float>();
-    int *bep = back_edge.data_ptr<int>(), *brp = back_rank.data_ptr<int>();
+// the CPU row kernel: one query's step over raw arrays (beam_search_step and, per query, beam_search_step_batch)
+void beam_rows_cpu(const int *rp, const int *sp, const float *gp, const float *xp, int64_t N, int64_t K, int64_t tail, float *dp,
+                   int *bep, int *brp) {
     at::parallel_for(0, N, 64, [&](int64_t v0, int64_t v1) {
         struct Cand { float v; int64_t e; int k, prev; };
         std::vector<Cand> kept;
@@ -1075,6 +1065,20 @@ std::tuple<Tensor, Tensor, Tensor> beam_search_step_cpu(const Tensor &row_ptr, c
             }
         }
     });
+}
+
+std::tuple<Tensor, Tensor, Tensor> beam_search_step_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
+                                                        const Tensor &input, int64_t tail) {
+    for (const Tensor *t : {&row_ptr, &src, &edge_grad, &input})
+        TORCH_CHECK(t->device().is_cpu(), "ultra_mi (CPU): beam_search_step: all tensors must share a device");
+    const BeamArgs a = check_beam(row_ptr, src, edge_grad, input, tail);
+    const int64_t N = a.n_node, K = a.K;
+    Tensor distance = at::empty({N, K}, input.options());
+    Tensor back_edge = at::empty({N, K}, row_ptr.options()), back_rank = at::empty({N, K}, row_ptr.options());
+    if (N == 0) return {distance, back_edge, back_rank};
+    const Tensor rp_t = row_ptr.contiguous(), s_t = src.contiguous(), g_t = edge_grad.contiguous(), x_t = input.contiguous();
+    beam_rows_cpu(rp_t.data_ptr<int>(), s_t.data_ptr<int>(), g_t.data_ptr<float>(), x_t.data_ptr<float>(), N, K, tail,
+                  distance.data_ptr<float>(), back_edge.data_ptr<int>(), back_rank.data_ptr<int>());
     return {distance, back_edge, back_rank};
 }
 
@@ -1093,6 +1097,76 @@ std::tuple<Tensor, Tensor, Tensor> beam_search_step_hip(const Tensor &row_ptr, c
                                             K, distance.data_ptr<float>(), back_edge.data_ptr<int>(),
                                             back_rank.data_ptr<int>(), current_stream(input)),
                  "ultra_beam_search_step_f32");
+    return {distance, back_edge, back_rank};
+}
+
+// ------------------------------------------------------------------------------------------ beam_search_step_batch
+// The same step for B queries over one graph (include/ultra_rspmm.h, ultra_beam_search_step_batch_f32): edge_grad (B, E), input
+// (B, N, K), tails int32 (B,); query b's slices are beam_search_step's for (edge_grad[b], input[b], tails[b]), bit for bit on both
+// keys.  The checks are those of beam_search_step, made ONCE per call: the CSR and the tails in one reduction and one host read.
+BeamArgs check_beam_batch(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad, const Tensor &input,
+                          const Tensor &tails) {
+    TORCH_CHECK(input.dim() == 3, "ultra_mi::beam_search_step_batch: input must be (B, N, K), got ", input.sizes());
+    const int64_t B = input.size(0), n_node = input.size(1), K = input.size(2), n_edges = src.numel();
+    TORCH_CHECK_VALUE(B >= 1 && B <= 65535, "ultra_mi::beam_search_step_batch: the number of queries must lie in [1, 65535], got ", B);
+    TORCH_CHECK_VALUE(K >= 1 && K <= 32, "ultra_mi::beam_search_step_batch: the number of beams must lie in [1, 32], got ", K);
+    TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.numel() == n_node + 1 && src.dim() == 1 && edge_grad.dim() == 2 &&
+                    edge_grad.size(0) == B && edge_grad.size(1) == n_edges && tails.dim() == 1 && tails.numel() == B,
+                "ultra_mi::beam_search_step_batch: row_ptr (N + 1,), src (E,), edge_grad (B, E), input (B, N, K), tails (B,) expected");
+    TORCH_CHECK(row_ptr.scalar_type() == at::kInt && src.scalar_type() == at::kInt && tails.scalar_type() == at::kInt,
+                "ultra_mi::beam_search_step_batch: int32 row_ptr / src / tails");
+    TORCH_CHECK(edge_grad.scalar_type() == at::kFloat && input.scalar_type() == at::kFloat,
+                "ultra_mi::beam_search_step_batch: fp32 edge_grad / input");
+    for (const Tensor *t : {&row_ptr, &src, &edge_grad, &tails})
+        TORCH_CHECK(t->device() == input.device(), "ultra_mi::beam_search_step_batch: all tensors must share a device");
+    TORCH_CHECK(n_node < INT32_MAX && n_edges < INT32_MAX, "ultra_mi::beam_search_step_batch: graph too large for int32 indices");
+    // bit 0: malformed CSR, bit 1: a tail out of range -- one reduction, one host read
+    const Tensor rp = row_ptr.to(at::kLong);
+    Tensor bad_tail = (tails < 0).any() | (tails >= n_node).any();
+    Tensor bad_csr = (rp[0] != 0) | (rp[n_node] != n_edges);
+    if (n_node > 0) bad_csr = bad_csr | (rp.narrow(0, 1, n_node) < rp.narrow(0, 0, n_node)).any();
+    if (n_edges > 0) bad_csr = bad_csr | (src < 0).any() | (src >= n_node).any();
+    const int64_t code = (bad_csr.to(at::kLong) + bad_tail.to(at::kLong) * 2).item<int64_t>();
+    TORCH_CHECK((code & 1) == 0, "ultra_mi::beam_search_step_batch: malformed CSR (row_ptr must run from 0 to E without decreasing, src "
+                "must lie in [0, N))");
+    TORCH_CHECK((code & 2) == 0, "ultra_mi::beam_search_step_batch: a tail lies outside [0, ", n_node, ")");
+    return {n_node, n_edges, K};
+}
+
+std::tuple<Tensor, Tensor, Tensor> beam_search_step_batch_cpu(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
+                                                              const Tensor &input, const Tensor &tails) {
+    for (const Tensor *t : {&row_ptr, &src, &edge_grad, &input, &tails})
+        TORCH_CHECK(t->device().is_cpu(), "ultra_mi (CPU): beam_search_step_batch: all tensors must share a device");
+    const BeamArgs a = check_beam_batch(row_ptr, src, edge_grad, input, tails);
+    const int64_t B = input.size(0), N = a.n_node, K = a.K, E = a.n_edges;
+    Tensor distance = at::empty({B, N, K}, input.options());
+    Tensor back_edge = at::empty({B, N, K}, row_ptr.options()), back_rank = at::empty({B, N, K}, row_ptr.options());
+    if (N == 0) return {distance, back_edge, back_rank};
+    const Tensor rp_t = row_ptr.contiguous(), s_t = src.contiguous(), g_t = edge_grad.contiguous(), x_t = input.contiguous();
+    const Tensor t_t = tails.contiguous();
+    for (int64_t b = 0; b < B; ++b)
+        beam_rows_cpu(rp_t.data_ptr<int>(), s_t.data_ptr<int>(), g_t.data_ptr<float>() + b * E, x_t.data_ptr<float>() + b * N * K,
+                      N, K, (int64_t)t_t.data_ptr<int>()[b], distance.data_ptr<float>() + b * N * K,
+                      back_edge.data_ptr<int>() + b * N * K, back_rank.data_ptr<int>() + b * N * K);
+    return {distance, back_edge, back_rank};
+}
+
+std::tuple<Tensor, Tensor, Tensor> beam_search_step_batch_hip(const Tensor &row_ptr, const Tensor &src, const Tensor &edge_grad,
+                                                              const Tensor &input, const Tensor &tails) {
+    check_dense(input, "input", at::kFloat, input);
+    const BeamArgs a = check_beam_batch(row_ptr, src, edge_grad, input, tails);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+    const int64_t B = input.size(0), N = a.n_node, K = a.K;
+    Tensor distance = at::empty({B, N, K}, input.options());
+    Tensor back_edge = at::empty({B, N, K}, row_ptr.options()), back_rank = at::empty({B, N, K}, row_ptr.options());
+    if (N == 0) return {distance, back_edge, back_rank};
+    const Tensor rp = row_ptr.contiguous(), s = src.contiguous(), g = edge_grad.contiguous(), x = input.contiguous();
+    const Tensor t = tails.contiguous();
+    check_status(ultra_beam_search_step_batch_f32(rp.data_ptr<int>(), a.n_edges ? s.data_ptr<int>() : nullptr,
+                                                  a.n_edges ? g.data_ptr<float>() : nullptr, x.data_ptr<float>(),
+                                                  t.data_ptr<int>(), N, a.n_edges, B, K, distance.data_ptr<float>(),
+                                                  back_edge.data_ptr<int>(), back_rank.data_ptr<int>(), current_stream(input)),
+                 "ultra_beam_search_step_batch_f32");
     return {distance, back_edge, back_rank};
 }
 
@@ -1241,6 +1315,7 @@ TORCH_LIBRARY(ultra_mi, m) {
     m.def("rspmm_plan_bwd(Tensor? by_src, Tensor? by_rel, Tensor relation, Tensor input, Tensor? output, Tensor output_grad, "
           "Tensor(a!)? d_input, bool accumulate, int n_src, int n_dst, int sum_op, int mul_op) -> Tensor");
     m.def("beam_search_step(Tensor row_ptr, Tensor src, Tensor edge_grad, Tensor input, int tail) -> (Tensor, Tensor, Tensor)");
+    m.def("beam_search_step_batch(Tensor row_ptr, Tensor src, Tensor edge_grad, Tensor input, Tensor tails) -> (Tensor, Tensor, Tensor)");
     m.def("hop_distance(Tensor row_ptr, Tensor src, Tensor? w, Tensor sources, int num_iters, Tensor? targets) -> Tensor");
     m.def("abi_version() -> int", []() -> int64_t { return ultra_rspmm_abi_version(); });
     m.def("rspmm_rotate_fwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, int block, "
@@ -1277,6 +1352,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("rspmm_fwd", rspmm_fwd_hip);
     m.impl("rspmm_bwd", rspmm_bwd_hip);
     m.impl("beam_search_step", beam_search_step_hip);
+    m.impl("beam_search_step_batch", beam_search_step_batch_hip);
     m.impl("hop_distance", hop_distance_hip);
 }
 
@@ -1286,6 +1362,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CPU, m) {
     m.impl("rspmm_fwd", rspmm_fwd_cpu);
     m.impl("rspmm_bwd", rspmm_bwd_cpu);
     m.impl("beam_search_step", beam_search_step_cpu);
+    m.impl("beam_search_step_batch", beam_search_step_batch_cpu);
     m.impl("hop_distance", hop_distance_cpu);
 }
 

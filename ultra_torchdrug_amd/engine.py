@@ -863,6 +863,24 @@ def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None
     return torch.cat(entities), torch.cat(scores)
 
 
+def explain(task, triples, batch_size=16, head=False):
+    """``task.explain`` over any number of triples (``(n, 3)`` rows of (h, t, r) in the current context): range-checked once
+    (:func:`validate_triples`), explained ``batch_size`` at a time (the last chunk is ragged), results in input order -- a list of
+    ``n`` ``(paths, weights)`` pairs, each chunk equal to ``task.explain`` of its rows.  Activation memory grows with
+    ``batch_size``: one ``(N, batch_size, D)`` tensor per layer is kept for the backward."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("explain: batch_size must be positive, got %d" % batch_size)
+    triples = torch.as_tensor(triples, device=task.device).long()
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("explain takes (n, 3) rows of (h, t, r), got %s" % (tuple(triples.shape),))
+    validate_triples(task, triples)
+    results = []
+    for i in range(0, len(triples), batch_size):
+        results.extend(task.explain(triples[i:i + batch_size], head=head))
+    return results
+
+
 @torch.no_grad()
 def answer_query(task, structure, anchors, relations, k=10, batch_size=16, **cut):
     """``task.answer_query`` over any number of queries of ONE structure: the ids are parsed and range-checked once, then the

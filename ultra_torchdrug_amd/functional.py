@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -734,6 +734,24 @@ def rspmm_backward_weight(csr, relation, input, output, output_grad, sum="add", 
         return d_w
     _launch(input.device, "ultra_rspmm_backward_weight_f32", csr.fwd.pointer, relation, input, output, output_grad, d_w,
             csr.shape[2], input.shape[1], sum_op, mul_op)
+    return d_w
+
+
+def rspmm_backward_weight_blocks(csr, relation, input, output, output_grad, sum="add", mul="mul", block=64):
+    """:func:`rspmm_backward_weight` per query block of ``block`` columns: fp32 ``(F / block, n_edges)``, row ``b`` the gradient
+    summed over columns ``b * block .. (b + 1) * block - 1`` alone -- bit for bit :func:`rspmm_backward_weight` on a contiguous
+    copy of those columns (``ultra_rspmm_backward_weight_blocks_f32``: one wave per edge walks the blocks)."""
+    sum_op, mul_op = _ops(sum, mul)
+    block, F = int(block), input.shape[1]
+    if block <= 0 or F <= 0 or F % block:
+        raise RuntimeError("rspmm_backward_weight_blocks: a positive block width that divides F = %d expected, got %d" % (F, block))
+    relation, input, output_grad = relation.contiguous(), input.contiguous(), output_grad.contiguous()
+    output = output.contiguous() if output is not None else None
+    d_w = torch.empty(F // block, csr.n_edges, dtype=torch.float32, device=input.device)       # written completely
+    if csr.n_edges == 0:
+        return d_w
+    _launch(input.device, "ultra_rspmm_backward_weight_blocks_f32", csr.fwd.pointer, relation, input, output, output_grad, d_w,
+            csr.shape[2], F, block, sum_op, mul_op)
     return d_w
 
 
@@ -1562,8 +1580,15 @@ class _RSPMMFunction(torch.autograd.Function):
         # query block b of grad_out (what scatter_add_'s backward would gather from the dense gradient)
         # edge_weight: fp32 (csr.n_edges,) weights of the COALESCED edges (forward-plan order) that replace csr's own; its
         # gradient is rspmm_backward_weight's d_w (TransferNBFNet.visualize: per-layer edge gradients without an (E, F) tensor)
+        # a 2-D edge_weight (B, E): one weight vector per query block of F / B columns, every row EQUAL to the coalesced weights
+        # (the caller's precondition) -- the forward runs on row 0, the gradient is rspmm_backward_weight_blocks' (B, E)
+        ctx.weight_blocks = None
         if edge_weight is not None:
-            csr = csr.with_coalesced_weights(edge_weight.detach())
+            if edge_weight.dim() == 2:
+                ctx.weight_blocks = edge_weight.shape[0]
+                csr = csr.with_coalesced_weights(edge_weight.detach()[0])
+            else:
+                csr = csr.with_coalesced_weights(edge_weight.detach())
         boundary = None if b_node is None else (b_node, b_value.detach())
         out = rspmm_forward(csr, relation, input, sum, mul, add_rows=add_rows, boundary=boundary)
         ctx.has_add_rows = add_rows is not None
@@ -1596,7 +1621,11 @@ class _RSPMMFunction(torch.autograd.Function):
             d_value = _boundary_value_grad(output_grad, ctx.b_node)
         d_edge = None
         if len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]:
-            d_edge = rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul)
+            if ctx.weight_blocks is not None:
+                d_edge = rspmm_backward_weight_blocks(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul,
+                                                      input.shape[1] // ctx.weight_blocks)
+            else:
+                d_edge = rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.mul)
         return d_sparse, d_relation, d_input, None, None, None, d_add, None, d_value, d_edge
 
 
@@ -1781,16 +1810,22 @@ def sum_layer(csr, relation, input, boundary_dense, boundary_sparse, mul, weight
                                    ln_eps, relu, shortcut, input_is_boundary, grad_tiles, grad_rows)
 
 
-def _check_edge_weight(csr, sparse_leaf, edge_weight, input):
+def _check_edge_weight(csr, sparse_leaf, edge_weight, input, block=None):
+    """The 2-D form ``(B, E)`` needs ``B`` to divide ``F``; ``block`` (rotate): the query width, ``B * block == F``."""
     if edge_weight is None:
         return
     if sparse_leaf is not None:
         raise RuntimeError("give the edge weights either as the values of a sparse tensor that requires grad or as "
                            "edge_weight, not both")
-    if (edge_weight.dtype != torch.float32 or tuple(edge_weight.shape) != (csr.n_edges,)
+    batched = (edge_weight.dim() == 2 and edge_weight.shape[0] >= 1 and edge_weight.shape[1] == csr.n_edges
+               and input.shape[1] % edge_weight.shape[0] == 0
+               and (block is None or input.shape[1] == edge_weight.shape[0] * block))
+    if (edge_weight.dtype != torch.float32 or (tuple(edge_weight.shape) != (csr.n_edges,) and not batched)
             or edge_weight.device != input.device):
-        raise RuntimeError("edge_weight must be fp32 (%d,) -- one weight per coalesced edge -- on %s, got %s %s on %s"
-                           % (csr.n_edges, input.device, edge_weight.dtype, tuple(edge_weight.shape), edge_weight.device))
+        raise RuntimeError("edge_weight must be fp32 (%d,) -- one weight per coalesced edge -- or (B, %d) with equal rows, one per "
+                           "query block of F / B columns, on %s, got %s %s on %s"
+                           % (csr.n_edges, csr.n_edges, input.device, edge_weight.dtype, tuple(edge_weight.shape),
+                              edge_weight.device))
 
 
 def rspmm_sum_plus(sparse, relation, input, add_rows, mul="mul", boundary=None, edge_weight=None):
@@ -1827,6 +1862,9 @@ def generalized_rspmm(sparse, relation, input, sum="add", mul="mul", edge_weight
     ``edge_weight`` (MI355X only; an extension): fp32 ``(n_edges,)`` weights of the COALESCED edges in forward-plan order
     (``RelCSR.dst / src / rel_id``) used instead of the adjacency's own; differentiable -- its gradient is
     :func:`rspmm_backward_weight` (duplicate triples of a COO input share one coalesced edge, ``RelCSR.edge_of_input``).
+    A 2-D ``edge_weight`` ``(B, n_edges)`` is one weight vector per query block of ``F / B`` columns; PRECONDITION: every row
+    equals the coalesced weights in use.  The forward runs on row 0 (the bits of the 1-D form) and the gradient is the ``(B,
+    n_edges)`` result of :func:`rspmm_backward_weight_blocks` (``TransferNBFNet.edge_gradients_batch``).
     """
     _ops(sum, mul)
     csr, sparse_leaf = _as_relcsr(sparse)
@@ -1922,6 +1960,21 @@ def rotate_rspmm_backward_weight(csr, relation, input, output, output_grad, sum=
     return d_w
 
 
+def rotate_rspmm_backward_weight_blocks(csr, relation, input, output, output_grad, sum="add", block=64):
+    """:func:`rotate_rspmm_backward_weight` per query block: fp32 ``(F / block, n_edges)``, row ``b`` the gradient over the pairs
+    of query block ``b`` alone -- bit for bit :func:`rotate_rspmm_backward_weight` on a contiguous copy of that block's columns
+    (``ultra_rspmm_rotate_backward_weight_blocks_f32``)."""
+    sum_op, block = _rotate_ops(csr, relation, input, sum, block, True)
+    relation, input, output_grad = relation.contiguous(), input.contiguous(), output_grad.contiguous()
+    output = output.contiguous() if output is not None else None
+    d_w = torch.empty(input.shape[1] // block, csr.n_edges, dtype=torch.float32, device=input.device)   # written completely
+    if csr.n_edges == 0:
+        return d_w
+    _launch(input.device, "ultra_rspmm_rotate_backward_weight_blocks_f32", csr.fwd.pointer, relation, input, output, output_grad,
+            d_w, csr.shape[2], input.shape[1], block, sum_op)
+    return d_w
+
+
 class _RotateFunction(torch.autograd.Function):
     """Autograd of :func:`rotate_rspmm` on device tensors; ``add_rows`` / ``(b_node, b_value)`` / ``edge_weight`` as in
     :class:`_RSPMMFunction`."""
@@ -1930,8 +1983,14 @@ class _RotateFunction(torch.autograd.Function):
     def forward(ctx, relation, input, csr, sum, block, add_rows=None, b_node=None, b_value=None, edge_weight=None):
         # edge_weight: fp32 (csr.n_edges,) weights of the COALESCED edges (forward-plan order) that replace csr's own; its
         # gradient is rotate_rspmm_backward_weight's d_w
+        # (B, E): one weight vector per query block, rows equal; the gradient is rotate_rspmm_backward_weight_blocks' (B, E)
+        ctx.weight_blocks = None
         if edge_weight is not None:
-            csr = csr.with_coalesced_weights(edge_weight.detach())
+            if edge_weight.dim() == 2:
+                ctx.weight_blocks = edge_weight.shape[0]
+                csr = csr.with_coalesced_weights(edge_weight.detach()[0])
+            else:
+                csr = csr.with_coalesced_weights(edge_weight.detach())
         boundary = None if b_node is None else (b_node, b_value.detach())
         out = rotate_rspmm_forward(csr, relation, input, sum, block, add_rows=add_rows, boundary=boundary)
         ctx.csr, ctx.sum, ctx.block = csr, sum, block
@@ -1950,7 +2009,10 @@ class _RotateFunction(torch.autograd.Function):
             d_value = _boundary_value_grad(output_grad, ctx.b_node)
         d_edge = None
         if len(ctx.needs_input_grad) > 8 and ctx.needs_input_grad[8]:
-            d_edge = rotate_rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.block)
+            if ctx.weight_blocks is not None:
+                d_edge = rotate_rspmm_backward_weight_blocks(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.block)
+            else:
+                d_edge = rotate_rspmm_backward_weight(ctx.csr, relation, input, out, output_grad, ctx.sum, ctx.block)
         return d_relation, d_input, None, None, None, d_add, None, d_value, d_edge
 
 
@@ -1967,7 +2029,8 @@ def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, bo
     Extension (device tensors, ``sum="add"``): ``add_rows`` / ``boundary = (node, value)`` -- the epilogue ``+ boundary`` inside
     the kernel, differentiable in ``add_rows`` / ``value`` (see :func:`rspmm_forward`).  ``edge_weight`` (MI355X only): fp32
     ``(n_edges,)`` weights of the COALESCED edges in forward-plan order used instead of the adjacency's own, as in
-    :func:`generalized_rspmm`; differentiable -- its gradient is :func:`rotate_rspmm_backward_weight`."""
+    :func:`generalized_rspmm`; differentiable -- its gradient is :func:`rotate_rspmm_backward_weight` (2-D ``(F / block,
+    n_edges)`` with equal rows: :func:`rotate_rspmm_backward_weight_blocks`, as there)."""
     if sum not in _lib.SUM_OPS:
         raise ValueError("Can't find a rotate rspmm operator for sum=`%s` (expected add, min or max)" % sum)
     csr, sparse_leaf = _as_relcsr(sparse)
@@ -1977,7 +2040,7 @@ def rotate_rspmm(sparse, relation, input, sum="add", block=64, add_rows=None, bo
     if (add_rows is not None or boundary is not None) and sum != "add":
         raise RuntimeError("rotate_rspmm: the fused boundary is for sum aggregation (max: torch.max after the call)")
     sum_op, block = _rotate_ops(csr, relation, input, sum, block, False)
-    _check_edge_weight(csr, sparse_leaf, edge_weight, input)
+    _check_edge_weight(csr, sparse_leaf, edge_weight, input, block)
     if not input.is_cuda:
         if edge_weight is not None:
             raise RuntimeError("rotate_rspmm: edge_weight runs on an MI355X (HIP) device only")
@@ -2003,6 +2066,17 @@ def beam_search_step(row_ptr, src, edge_grad, input, tail):
     if input.dim() != 2 or not 1 <= input.shape[1] <= BEAM_MAX:
         raise ValueError("beam_search_step: input must be (N, K) with 1 <= K <= %d, got %s" % (BEAM_MAX, tuple(input.shape)))
     return _torch_ext.load().beam_search_step(row_ptr, src, edge_grad, input, int(tail))
+
+
+def beam_search_step_batch(row_ptr, src, edge_grad, input, tails):
+    """:func:`beam_search_step` for ``B`` queries over one graph in one launch (``torch.ops.ultra_mi.beam_search_step_batch``):
+    ``edge_grad`` fp32 ``(B, E)``, ``input`` fp32 ``(B, N, K)``, ``tails`` int32 ``(B,)`` on the tensors' device (never read on
+    the host beyond the one validity check).  Returns ``(distance, back_edge, back_rank)``, each ``(B, N, K)``; query ``b``'s
+    slices are exactly :func:`beam_search_step` on ``(edge_grad[b], input[b], tails[b])``."""
+    if input.dim() != 3 or input.shape[0] < 1 or not 1 <= input.shape[2] <= BEAM_MAX:
+        raise ValueError("beam_search_step_batch: input must be (B, N, K) with B >= 1 and 1 <= K <= %d, got %s"
+                         % (BEAM_MAX, tuple(input.shape)))
+    return _torch_ext.load().beam_search_step_batch(row_ptr, src, edge_grad, input, tails)
 
 
 HOP_ITERS = 100      # the reference's num_iters (ultra/model.py:302): the cap is part of the definition

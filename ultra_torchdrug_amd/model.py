@@ -113,13 +113,16 @@ class TransferNBFNet(nn.Module):
         relation = torch.zeros(len(edge_list), 1, dtype=torch.long, device=graph.device)
         return Graph(torch.cat([edge_list, relation], dim=-1), edge_weight, graph.num_node, 1)
 
-    def bellmanford(self, graph, h_index, r_index, separate_grad=False, want_feature=True, grad_candidates=None, boundary=None):
+    def bellmanford(self, graph, h_index, r_index, separate_grad=False, want_feature=True, grad_candidates=None, boundary=None,
+                    edge_grad_per_query=False):
         """model.py:101-143.  Returns ``node_feature`` of shape ``(num_node, batch, feature_dim)``; with
         ``want_feature=False`` only its two parts (``hidden``: last layer output, ``query``) -- the fused score
         kernel reads them directly and the ``cat`` of model.py:134-138 is never materialised.
         ``separate_grad=True``: every layer on its own clone of the graph with the materialised message route (model.py:120).
         ``separate_grad="native"``: every layer gets its own leaf edge-weight tensor, ``step_graph.edge_grad_leaf``
         (:meth:`_edge_grad_graph`), for :meth:`visualize`.
+        ``edge_grad_per_query`` (with ``separate_grad="native"``, :meth:`edge_gradients_batch`): that leaf is ``(batch, E)``, one
+        weight vector per query.
         ``boundary`` (:meth:`project`): a ready ``(num_node, batch, input_dim)`` boundary condition -- a fuzzy set of sources per
         query -- in place of the one-hot rows at ``h_index``, which is then not read (pass ``None``); the layers get it in its
         dense form only, so no shortcut that rests on a one-row boundary is taken."""
@@ -176,7 +179,10 @@ class TransferNBFNet(nn.Module):
                 self.last_cuts = ([layer_input] + [late_graph.relation_tables[id(c)] for c in list(self.layers)[cut:]]
                                   + [query_late])
             if separate_grad == "native":
-                step_graph = self._edge_grad_graph(graph, conv, query, boundary)
+                if edge_grad_per_query:
+                    step_graph = self._edge_grad_graph(graph, conv, query, boundary, n_query=bs)
+                else:
+                    step_graph = self._edge_grad_graph(graph, conv, query, boundary)
             elif separate_grad:
                 step_graph = graph.clone()
                 step_graph.query, step_graph.boundary = query, boundary
@@ -201,7 +207,7 @@ class TransferNBFNet(nn.Module):
         return {"node_feature": output, "step_graphs": step_graphs}
 
     @staticmethod
-    def _edge_grad_graph(graph, conv, query, boundary):
+    def _edge_grad_graph(graph, conv, query, boundary, n_query=None):
         """The step graph of one layer under ``bellmanford(separate_grad="native")``.  On the device, for the layers that
         have it (``conv.native_edge_grad(graph, boundary)``: sum / max of DistMult / TransE / rotate messages, and their mean on
         a unit-weight graph), a shallow copy of ``graph`` whose ``native_edge_weight`` -- a leaf copy of the COALESCED weights
@@ -210,11 +216,15 @@ class TransferNBFNet(nn.Module):
         shortcut, no ``(E, D)`` message tensor.  Otherwise (``pna``; ``mean`` on a weighted graph; rotate of an odd width or
         not in fp32; CPU tensors) a clone on the materialised message route (layer.py ``message`` / ``aggregate``) whose
         ``edge_weight`` is a leaf, one entry per ORIGINAL edge.  ``edge_grad_leaf`` names the leaf, ``edge_grad_coalesced``
-        its order."""
+        its order.  ``n_query`` (:meth:`edge_gradients_batch`, native layers only): the leaf is ``(n_query, E)``, the coalesced
+        weights once per query, whose gradient the operators return per query block."""
         if backend.get().accepts(boundary) and conv.native_edge_grad(graph, boundary):
             import copy
             step = copy.copy(graph)
-            step.native_edge_weight = graph.relcsr.weight.detach().clone().requires_grad_()
+            weight = graph.relcsr.weight.detach()
+            if n_query is not None:
+                weight = weight.expand(n_query, weight.shape[0])
+            step.native_edge_weight = weight.clone().requires_grad_()
             step.edge_grad_leaf, step.edge_grad_coalesced = step.native_edge_weight, True
             return step
         step = graph.clone()
@@ -301,6 +311,152 @@ class TransferNBFNet(nn.Module):
             g = torch.zeros_like(leaf) if g is None else g.detach()
             edge_grads.append(g if step.edge_grad_coalesced else self._coalesced_edge_grad(csr, g))
         return (edge_grads, (h, t, r)) if with_ids else edge_grads
+
+    def visualize_batch(self, graph, rel_query_list, h_index, t_index, r_index):
+        """:meth:`visualize` for ``B`` triples at once: a list of ``B`` ``(paths, weights)`` pairs, each in the format (and, for a
+        triple explained alone, with the values) :meth:`visualize` returns.  ``rel_query_list``: the relation representations
+        with one row per triple, as :meth:`forward` takes them; ``h_index`` / ``t_index`` / ``r_index``: ``(B,)``.  One forward and
+        one backward hold every triple's edge gradients (:meth:`edge_gradients_batch`), ``functional.beam_search_step_batch`` runs
+        once per layer for all of them (``beams[b, h_b, 0] = 0``), the ``B x L x take`` chains are followed on the device and
+        leave in one copy; the final sort runs per triple on the host."""
+        from . import functional
+        num_beam = int(self.num_beam)
+        if not 1 <= num_beam <= functional.BEAM_MAX:
+            raise ValueError("visualize_batch: num_beam must lie in [1, %d], got %d" % (functional.BEAM_MAX, num_beam))
+        edge_grads, (h, t, _) = self.edge_gradients_batch(graph, rel_query_list, h_index, t_index, r_index, with_ids=True)
+        graph = self._undirected(graph)
+        csr = graph.relcsr
+        row_ptr, src, _, _ = csr.csr_arrays
+        n_query = len(h)
+        with torch.no_grad():
+            dev = row_ptr.device
+            rows = torch.arange(n_query, device=dev)
+            heads, tails = torch.tensor(h, device=dev), torch.tensor(t, device=dev)
+            tails32 = tails.to(torch.int32)
+            beams = torch.full((n_query, graph.num_node, num_beam), float("-inf"), device=dev)
+            beams[rows, heads, 0] = 0
+            steps = []
+            for g in edge_grads:
+                beams, back_edge, back_rank = functional.beam_search_step_batch(row_ptr, src, g.to(torch.float32).contiguous(),
+                                                                                beams, tails32)
+                steps.append((beams[rows, tails], back_edge, back_rank))
+            return self._assemble_paths_batch(csr, steps, tails, int(self.path_topk))
+
+    def _native_edge_grad_stack(self, graph, dtype):
+        """Whether every layer takes the native route of :meth:`_edge_grad_graph` on ``graph`` (with inverse edges)."""
+        probe = torch.empty(0, dtype=dtype, device=self.device)
+        return (backend.get().accepts(probe) and not graph.requires_grad
+                and all(conv.native_edge_grad(graph, probe) for conv in self.layers))
+
+    def edge_gradients_batch(self, graph, rel_query_list, h_index, t_index, r_index, with_ids=False):
+        """:meth:`edge_gradients` for ``B`` triples: one fp32 ``(B, E_coalesced)`` tensor per layer, row ``b`` the gradient of the
+        score of triple ``b`` alone.  The queries of a batch are independent column blocks of every kernel of the stack, so where
+        every layer has the native route (:meth:`_edge_grad_graph`) ONE ``bellmanford(separate_grad="native")`` over the ``B``
+        queries and ONE ``torch.autograd.grad`` of ``sum_b score_b`` hold all of them: each layer's leaf is the coalesced weight
+        vector once per query, ``(B, E)``, and the operators return its gradient per query block
+        (``functional.rspmm_backward_weight_blocks`` / ``rotate_rspmm_backward_weight_blocks``).  A single row scores its feature in
+        the vector form :meth:`edge_gradients` uses: its result is that call's, bit for bit.  If any layer is off the native
+        route (``pna``; ``mean`` on a weighted graph; rotate of an odd width or not in fp32; ``graph.requires_grad``; CPU
+        tensors) the result is the stack of ``B`` :meth:`edge_gradients` calls -- the same numbers, nothing accelerated.
+        No parameter's ``.grad`` moves, nor the module's mode.  ``with_ids``: also the host id lists ``(h, t, r)``."""
+        dev = self.device
+        h_index, t_index, r_index = (torch.as_tensor(x, device=dev).reshape(-1).long() for x in (h_index, t_index, r_index))
+        n_query = h_index.numel()
+        if n_query < 1 or t_index.numel() != n_query or r_index.numel() != n_query:
+            raise ValueError("edge_gradients_batch explains B >= 1 triples: got %d heads, %d tails, %d relations"
+                             % (h_index.numel(), t_index.numel(), r_index.numel()))
+        if not graph.num_relation:
+            raise ValueError("visualize needs a relational graph")
+        h, t, r = torch.stack([h_index, t_index, r_index]).tolist()      # one host read for the whole batch
+        for hb, tb, rb in zip(h, t, r):
+            if not (0 <= hb < graph.num_node and 0 <= tb < graph.num_node and 0 <= rb < 2 * graph.num_relation):
+                raise IndexError("visualize: h, t must lie in [0, %d) and r in [0, %d): got (%d, %d, %d)"
+                                 % (graph.num_node, 2 * graph.num_relation, hb, tb, rb))
+        for rel in rel_query_list:
+            if rel.dim() == 3 and rel.shape[0] != n_query:
+                raise ValueError("edge_gradients_batch: relation representations of %d rows for %d triples" % (rel.shape[0], n_query))
+        und = self._undirected(graph)
+        if not self._native_edge_grad_stack(und, rel_query_list[0].dtype):
+            per_triple = [self.edge_gradients(graph, [rel[b:b + 1] if rel.dim() == 3 else rel for rel in rel_query_list],
+                                              h_index[b:b + 1], t_index[b:b + 1], r_index[b:b + 1]) for b in range(n_query)]
+            edge_grads = [torch.stack([g[i] for g in per_triple]) for i in range(len(self.layers))]
+            return (edge_grads, (h, t, r)) if with_ids else edge_grads
+        self.query = rel_query_list[0]
+        if len(rel_query_list) > 1:
+            assert len(rel_query_list) == len(self.layers) + 1
+            for i, conv in enumerate(self.layers):
+                conv.relation = rel_query_list[i + 1]
+        else:
+            for conv in self.layers:
+                conv.relation = rel_query_list[0]
+        graph = und
+
+        with torch.enable_grad():
+            output = self.bellmanford(graph, h_index, r_index, separate_grad="native", want_feature=self.concat_hidden,
+                                      edge_grad_per_query=True)
+            rows = torch.arange(n_query, device=dev)
+            if self.concat_hidden:
+                feature = output["node_feature"][t_index, rows]
+            else:
+                feature = torch.cat([output["hidden"][t_index, rows], output["query"]], dim=-1)
+            if n_query == 1:
+                feature = feature[0]            # the vector form of edge_gradients: its bits
+            score = self.mlp(feature).squeeze(-1).sum()
+            step_graphs = output["step_graphs"]
+            leaves = [g.edge_grad_leaf for g in step_graphs]
+            grads = torch.autograd.grad(score, leaves, allow_unused=True)
+        del output, feature, score
+        edge_grads = [torch.zeros_like(leaf) if g is None else g.detach() for g, leaf in zip(grads, leaves)]
+        return (edge_grads, (h, t, r)) if with_ids else edge_grads
+
+    @staticmethod
+    def _assemble_paths_batch(csr, steps, t, topk):
+        """:meth:`_assemble_paths` for ``B`` triples: ``steps[i] = (beams[b, t_b] (B, K), back_edge (B, N, K), back_rank (B, N,
+        K))``, ``t`` int64 ``(B,)`` on the device.  All ``B x L x take`` chains are followed on the device and leave in ONE copy;
+        the sort of at most ``L * topk`` paths runs per triple on the host.  Returns the list of ``(paths, weights)``."""
+        src, dst, rel = csr.src, csr.dst, csr.rel_id
+        n_layer, n_query = len(steps), t.shape[0]
+        if n_layer == 0 or topk <= 0:
+            return [((), ()) for _ in range(n_query)]
+        K = steps[0][0].shape[1]
+        take = min(topk, K)
+        dev = src.device
+        rows = torch.arange(n_query, device=dev)
+        col = rows[:, None]
+        hops = torch.full((n_query, n_layer, take, n_layer), -1, dtype=torch.long, device=dev)   # edge positions, hop order
+        values = torch.stack([s[0][:, :take] for s in steps], dim=1)                              # (B, L, take), descending
+        for i, (_, back_edge, back_rank) in enumerate(steps):
+            e = back_edge[rows, t, :take].long()
+            p = back_rank[rows, t, :take].long()
+            hops[:, i, :, i] = e
+            for j in range(i - 1, -1, -1):
+                node = src[e.clamp(min=0)]
+                p_safe = p.clamp(min=0)
+                e = steps[j][1][col, node, p_safe].long()
+                p = steps[j][2][col, node, p_safe].long()
+                hops[:, i, :, j] = e
+        safe = hops.clamp(min=0)
+        triples = torch.stack([src[safe], dst[safe], rel[safe]], dim=-1)                          # (B, L, take, L, 3)
+        packed = torch.cat([values.double().view(torch.int64).flatten(), triples.flatten()]).cpu()
+        n_val = n_query * n_layer * take
+        values = packed[:n_val].view(torch.float64).view(n_query, n_layer, take).tolist()
+        triples = packed[n_val:].view(n_query, n_layer, take, n_layer, 3).tolist()
+        results = []
+        for b in range(n_query):
+            weights, paths = [], []
+            for i in range(n_layer):
+                for k in range(take):
+                    d = values[b][i][k]
+                    if d == float("-inf"):
+                        break
+                    paths.append([tuple(x) for x in triples[b][i][k][:i + 1]])
+                    weights.append(d / (i + 1))
+            if not paths:
+                results.append(((), ()))
+                continue
+            weights, paths = zip(*sorted(zip(weights, paths), reverse=True)[:topk])
+            results.append((paths, weights))
+        return results
 
     @staticmethod
     def _coalesced_edge_grad(csr, grad):

@@ -469,6 +469,22 @@ class KnowledgeGraphCompletion(nn.Module):
             h, t, r = t, h, r + self.fact_graph.num_relation
         return self.model.visualize(self.fact_graph, rel_inputs, h, t, r)
 
+    def explain(self, triples, head=False):
+        """:meth:`visualize` for a batch: ``triples`` int64 ``(B, 3)`` rows of ``(h, t, r)`` in the current context, ``r`` in
+        ``[0, R)``.  The relation representations of all ``r`` come from one call without gradient; one forward, one backward and
+        one beam-search launch per layer explain the whole batch (``TransferNBFNet.visualize_batch``).  ``head=True`` explains
+        the queries ``(t, r + R, h)`` -- for every row: there is no per-row flag.  Returns the list of ``B`` ``(paths, weights)``
+        pairs."""
+        triples = torch.as_tensor(triples, device=self.device).long()
+        if triples.dim() != 2 or triples.shape[1] != 3 or triples.shape[0] < 1:
+            raise ValueError("explain takes (B, 3) rows of (h, t, r) with B >= 1, got %s" % (tuple(triples.shape),))
+        h, t, r = triples.unbind(-1)
+        with torch.no_grad():
+            rel_inputs = self.relation_representations(r)
+        if head:
+            h, t, r = t, h, r + self.fact_graph.num_relation
+        return self.model.visualize_batch(self.fact_graph, rel_inputs, h, t, r)
+
     def answer_queries(self, anchor, relation, head=False):
         """The range-checked queries of :meth:`answer` in tail form: ``(anchor, query relation in [0, 2R), base relation)``,
         each int64 ``(Q,)`` on the task's device -- ``head=True`` asks ``(anchor, relation + R, ?)``
