@@ -148,6 +148,10 @@ int ultra_rspmm_event_elapsed_ms(void *start_event, void *stop_event, float *ms_
 int ultra_rspmm_launch_records_clear(void);
 int ultra_rspmm_launch_records(int32_t *rows_host, int max_rows);
 const char *ultra_rspmm_launch_record_fields(void);
+/* Test aid: the kernel the last layer-epilogue forward of THIS thread launched (ultra_combine_forward_f32 and its boundary
+ * form; they run no plan and write no record above).  0: none yet; 1: combine_kernel, one wave per SIMD; 2: combine_paired_kernel,
+ * the row-per-lane form that reads through 32-bit buffer offsets; 3: combine_paired_kernel_lds, whose addresses are 64-bit. */
+int ultra_combine_forward_last_form(void);
 
 /* Test/bench knob (process-wide): bit 0 forces the general kernel where the packed fast paths apply, bit 1 keeps
  * them from staging a small gathered matrix in LDS, bit 2 selects one chunk per wave (packed_kernel) where four

@@ -479,6 +479,12 @@ def test_wide_id_variants_match_oracle(oracle, case):
         assert _same(d_x.cpu().numpy(), d_x_o) and _same(d_rel.cpu().numpy(), d_rel_o), m
 
 
+def epilogue_gradient_bound(scale):
+    """The bar of the epilogue's backward against fp64 autograd: 2e-5 of the gradient's largest entry (fp32 reductions over up
+    to 65k rows) plus an absolute 1e-6.  tests/test_address_width_gpu.py holds the same gradients at 2^24 rows to it."""
+    return 2e-5 * scale + 1e-6
+
+
 @pytest.mark.parametrize("rows", [1, 33, 1000, 65536 + 7])
 @pytest.mark.parametrize("ln,relu,shortcut", [(True, True, True), (False, True, False), (True, False, False)])
 def test_fused_combine_backward_matches_autograd_of_the_reference_formulation(rows, ln, relu, shortcut):
@@ -525,7 +531,7 @@ def test_fused_combine_backward_matches_autograd_of_the_reference_formulation(ro
     for name, g, w in zip(names, gpu, want):
         scale = w.abs().max().item() + 1e-12
         err = (g.grad.cpu().double() - w).abs().max().item()
-        assert err <= 2e-5 * scale + 1e-6, "%s: err %.3g vs scale %.3g" % (name, err, scale)
+        assert err <= epilogue_gradient_bound(scale), "%s: err %.3g vs scale %.3g" % (name, err, scale)
 
 
 @pytest.mark.parametrize("shape", [(64, 64, True), (64, 64, False), (128, 128, True), (128, 1, False)])

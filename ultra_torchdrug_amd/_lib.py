@@ -73,6 +73,7 @@ SIGNATURES = {
     "ultra_rspmm_launch_records_clear": (i32, []),
     "ultra_rspmm_launch_records": (i32, [vp, i32]),
     "ultra_rspmm_launch_record_fields": (ctypes.c_char_p, []),
+    "ultra_combine_forward_last_form": (i32, []),
     "ultra_rspmm_force_general_path": (i32, [i32]),
     "ultra_rspmm_reserve_cus": (i32, [i32]),
     "ultra_rspmm_workspace_bytes": (sz, [seg, i64]),
@@ -245,6 +246,14 @@ def launch_records():
     count = int(lib.ultra_rspmm_launch_records(ctypes.cast(rows, vp), 8))
     kept = min(count, 8)
     return count, [dict(zip(names, rows[i * len(names):(i + 1) * len(names)])) for i in range(kept)]
+
+
+COMBINE_FORMS = {0: None, 1: "combine_kernel", 2: "combine_paired_kernel", 3: "combine_paired_kernel_lds"}
+
+
+def combine_forward_last_form():
+    """Name of the kernel the last layer-epilogue forward of THIS thread launched (``ultra_combine_forward_last_form``)."""
+    return COMBINE_FORMS[int(load().ultra_combine_forward_last_form())]
 
 
 def device_info(device=0):

@@ -2440,6 +2440,10 @@ int ultra_rspmm_rotate_backward_weight_blocks_f32(const ultra_segments *fwd, con
 }
 
 
+// the form the thread's last epilogue forward took (ultra_combine_forward_last_form): 1 combine_kernel, 2 combine_paired_kernel,
+// 3 combine_paired_kernel_lds
+static thread_local int g_combine_form = 0;
+
 static int combine_launch(const CombineParams &p, void *stream) {
     DeviceInfo *di = nullptr;
     int rc = current_device_info(&di);
@@ -2463,10 +2467,12 @@ static int combine_launch(const CombineParams &p, void *stream) {
         {
             // the row-per-lane form reads through 32-bit buffer offsets: rows * 256 B < 4 GiB; knob bit 11 keeps the former kernel
             const bool row_per_lane = !g_knobs.combine_lds_rows && p.rows * 256 < (1LL << 32);
+            g_combine_form = row_per_lane ? 2 : 3;
             return launch_with_lds(row_per_lane ? combine_paired_kernel : combine_paired_kernel_lds, p, (int)groups,
                                    kCpLdsFloats * sizeof(float), st, kCpWaves * 64);
         }
     }
+    g_combine_form = 1;
     return with_bool(prefetch, [&](auto pf) {
         constexpr bool PF = decltype(pf)::value;
         auto go = [&](auto kern) { return launch_with_lds(kern, p, (int)blocks, lds, st, kCbWaves * 64, lds_max); };
@@ -2476,6 +2482,8 @@ static int combine_launch(const CombineParams &p, void *stream) {
         return go(combine_kernel<PF, 0>);
     });
 }
+
+int ultra_combine_forward_last_form(void) { return g_combine_form; }
 
 int ultra_combine_forward_f32(const float *input, const float *update, const float *weight, const float *bias,
                               const float *ln_weight, const float *ln_bias, float ln_eps, int relu, int shortcut,

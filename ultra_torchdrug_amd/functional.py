@@ -1485,6 +1485,53 @@ def _combine_backward_fused(input_c, update_c, epilogue, grad_out, z, grads, til
             tiles.numel() if tiles is not None else 0, rows, 64)
 
 
+# The one-pass backward addresses its rows through 32-bit buffer offsets: ``(rows + a tile) * 256 B < 4 GiB``
+# (csrc/combine_fused_bwd.inc; the entry returns ULTRA_ERR_BAD_SHAPE beyond).  Above it the three-kernel form, whose addresses
+# are 64-bit, runs whatever ULTRA_COMBINE_BWD says.
+FUSED_BACKWARD_MAX_ROWS = (1 << 24) - 64
+
+
+def _combine_backward_split(input_c, update_c, weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut, grad_out, grads=None,
+                            needs=(True,) * 6):
+    """The three-kernel epilogue backward (csrc/combine_train.inc): d_z and the per-wave partial parameter sums,
+    ``d_input | d_update`` from d_z -- written into ``grads[0]`` and ``grads[1]`` (:func:`_epilogue_gradients`) where the caller
+    brings them and wants both --, the partial sums added.  ``needs``: which of the six gradients the caller wants; the others
+    come back as ``None``.  Returns the six."""
+    dev = input_c.device
+    rows = input_c.numel() // 64
+    has_ln = ln_weight is not None
+    n_ln, n_wg = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().ultra_combine_backward_waves(dev.index or 0, rows, ctypes.byref(n_ln), ctypes.byref(n_wg)))
+    d_z = torch.empty(rows, 64, dtype=torch.float32, device=dev)
+    dg_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
+    db_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
+    dw_p = torch.empty(n_wg.value, 64 * 128, dtype=torch.float32, device=dev)
+    dbias_p = torch.empty(n_wg.value, 64, dtype=torch.float32, device=dev) if needs[3] else None
+    _launch(dev, "ultra_combine_backward_f32", input_c, update_c, *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu),
+            grad_out, d_z, dg_p, db_p, dw_p, dbias_p, rows, 64)
+    d_input = d_update = d_weight = d_bias = d_g = d_b = None
+    if needs[0] and needs[1]:       # both activation gradients: one pass over d_z instead of two GEMMs
+        d_input, d_update = (torch.empty_like(input_c), torch.empty_like(update_c)) if grads is None else (grads[0], grads[1])
+        _launch(dev, "ultra_combine_dxdu_f32", d_z, weight.contiguous(), grad_out if shortcut else None, d_input, d_update,
+                rows, 64)
+    elif needs[0]:
+        if shortcut:        # d_input = grad_out + d_z . W[:, :64] in one GEMM call (beta = 1)
+            d_input = torch.addmm(grad_out.view(rows, 64), d_z, weight[:, :64]).view_as(input_c)
+        else:
+            d_input = torch.mm(d_z, weight[:, :64]).view_as(input_c)
+    if needs[1] and d_update is None:
+        d_update = torch.mm(d_z, weight[:, 64:]).view_as(update_c)
+    if needs[2]:
+        d_weight = dw_p.sum(0).view(64, 128)
+    if needs[3]:
+        d_bias = dbias_p.sum(0)
+    if has_ln and needs[4]:
+        d_g = dg_p.sum(0)
+    if has_ln and needs[5]:
+        d_b = db_p.sum(0)
+    return d_input, d_update, d_weight, d_bias, d_g, d_b
+
+
 class _CombineFunction(torch.autograd.Function):
     """Fused epilogue with a fused backward (training).  Forward = ``combine_forward``; only the layer's inputs are
     saved.  Backward: ``libultra_rspmm`` recomputes z, applies the ReLU mask and LayerNorm-backward and reduces
@@ -1505,50 +1552,22 @@ class _CombineFunction(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         input_c, update_c = input.contiguous(), update.contiguous()
         rows = input.numel() // 64
-        dev = input.device
-        if os.environ.get("ULTRA_COMBINE_BWD", "fused") == "fused":
-            # the one-pass form (_combine_backward_fused).  ULTRA_COMBINE_BWD=split: the three-kernel form.
-            has_ln = ln_weight is not None
+        needs = ctx.needs_input_grad
+        has_ln = ln_weight is not None
+        if os.environ.get("ULTRA_COMBINE_BWD", "fused") == "fused" and rows <= FUSED_BACKWARD_MAX_ROWS:
+            # the one-pass form (_combine_backward_fused).  ULTRA_COMBINE_BWD=split, and every input beyond that form's 32-bit
+            # offsets: the three-kernel form.
             grads = _epilogue_gradients(input_c, update_c, has_ln)
             _combine_backward_fused(input_c, update_c, _epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut), grad_out,
                                     z, grads)
             d_input, d_update, d_weight, d_bias, d_g, d_b = grads
-            needs = ctx.needs_input_grad
             return (d_input.view_as(input) if needs[0] else None, d_update.view_as(update) if needs[1] else None,
                     d_weight if needs[2] else None, d_bias if needs[3] else None, d_g if (has_ln and needs[4]) else None,
                     d_b if (has_ln and needs[5]) else None, None, None, None)
-        n_ln, n_wg = ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(_lib.load().ultra_combine_backward_waves(dev.index or 0, rows, ctypes.byref(n_ln), ctypes.byref(n_wg)))
-        d_z = torch.empty(rows, 64, dtype=torch.float32, device=dev)
-        has_ln = ln_weight is not None
-        dg_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
-        db_p = torch.empty(n_ln.value, 64, dtype=torch.float32, device=dev) if has_ln else None
-        dw_p = torch.empty(n_wg.value, 64 * 128, dtype=torch.float32, device=dev)
-        dbias_p = torch.empty(n_wg.value, 64, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
-        _launch(dev, "ultra_combine_backward_f32", input_c, update_c, *_epilogue(weight, bias, ln_weight, ln_bias, ln_eps, relu),
-                grad_out, d_z, dg_p, db_p, dw_p, dbias_p, rows, 64)
-        needs = ctx.needs_input_grad
-        d_input = d_update = d_weight = d_bias = d_g = d_b = None
-        if needs[0] and needs[1]:       # both activation gradients: one pass over d_z instead of two GEMMs
-            d_input, d_update = torch.empty_like(input_c), torch.empty_like(update_c)
-            _launch(dev, "ultra_combine_dxdu_f32", d_z, weight.contiguous(), grad_out if shortcut else None, d_input, d_update,
-                    rows, 64)
-            d_input, d_update = d_input.view_as(input), d_update.view_as(update)
-        elif needs[0]:
-            if shortcut:        # d_input = grad_out + d_z . W[:, :64] in one GEMM call (beta = 1)
-                d_input = torch.addmm(grad_out.view(rows, 64), d_z, weight[:, :64]).view_as(input)
-            else:
-                d_input = torch.mm(d_z, weight[:, :64]).view_as(input)
-        if needs[1] and d_update is None:
-            d_update = torch.mm(d_z, weight[:, 64:]).view_as(update)
-        if needs[2]:
-            d_weight = dw_p.sum(0).view(64, 128)
-        if needs[3]:
-            d_bias = dbias_p.sum(0)
-        if has_ln and needs[4]:
-            d_g = dg_p.sum(0)
-        if has_ln and needs[5]:
-            d_b = db_p.sum(0)
+        d_input, d_update, d_weight, d_bias, d_g, d_b = _combine_backward_split(
+            input_c, update_c, weight, bias, ln_weight, ln_bias, ln_eps, relu, shortcut, grad_out, needs=needs[:6])
+        d_input = d_input.view_as(input) if d_input is not None else None
+        d_update = d_update.view_as(update) if d_update is not None else None
         return d_input, d_update, d_weight, d_bias, d_g, d_b, None, None, None
 
 
@@ -1764,8 +1783,13 @@ class _SumLayerFunction(torch.autograd.Function):
                               dtype=torch.float32, device=dev)
             _launch(dev, "ultra_first_layer_epilogue_backward_f32", input_c, update_c, grad_out, row_list, list_count,
                     row_list.numel(), *epilogue, *grads, ws1, ws1.numel() * 4, rows)
-        else:
+        elif rows <= FUSED_BACKWARD_MAX_ROWS:
             _combine_backward_fused(input_c, update_c, epilogue, grad_out, z, grads, tiles)
+        else:
+            # beyond the one-pass form's 32-bit offsets: the three-kernel form over every row (`tiles` is a promise of zeros
+            # outside them, which the full computation keeps), d_input | d_update into the same tensors
+            _, _, d_weight, d_bias, d_g, d_b = _combine_backward_split(input_c, update_c, weight, bias, ln_weight, ln_bias, ln_eps,
+                                                                       relu, shortcut, grad_out, grads)
         # the edge gradient accumulates into the epilogue's d_input (same buffer) inside the rspmm backward
         flat_du = d_update.flatten(1)
         if ctx.boundary_rows_only and needs[2]:
