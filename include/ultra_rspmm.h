@@ -553,6 +553,50 @@ int ultra_hop_distance(const int32_t *row_ptr, const int32_t *src, const float *
 int ultra_set_boundary_f32(const float *member, int64_t n_query, int64_t n_node, int64_t row_stride, const float *floor,
                            const float *query, int64_t dim, float *boundary, int32_t *count, void *stream);
 
+/*
+ * Exact (crisp) answer sets of logical queries (csrc/query_exact.hip; an addition of this package).
+ * A batch of n_query entity sets over n_node entities is PACKED: bits uint64 [n_node][W], W = (n_query + 63) / 64, bit q % 64 of
+ * bits[v][q / 64] = "entity v is in set q".  Intersection, union and complement are &, | and ~ of such arrays.
+ *
+ * ultra_sets_project: one relation projection of every set, over the coalesced dst-CSR of a graph WITH inverse edges
+ * (RelCSR.csr_arrays):
+ *   row_ptr int32 [n_node + 1], src int32 [n_edges], rel int32 [n_edges] in [0, n_rel)   (edge e of row v runs src[e] -> v)
+ *   w fp32 [n_edges] or NULL          an edge whose weight is exactly 0.0f DOES NOT EXIST, as in ultra_hop_distance; NULL = all exist
+ *   bits uint64 [n_node][W]           the sets; bits of columns >= n_query may hold anything
+ *   relation int64 [n_query]          the relation each set is projected along; one outside [0, n_rel) gives the empty set
+ *   out uint64 [n_node][W]            written completely; must not be `bits` (ULTRA_ERR_BAD_SHAPE)
+ * Definition:  out[v] bit q  =  OR over the edges e of row v with rel[e] == relation[q] and w[e] != 0  of  bits[src[e]] bit q;
+ * bits of columns >= n_query are 0 in out.  OR is associative, commutative and idempotent: every schedule gives the same bits.
+ * workspace: ultra_sets_project_workspace(n_rel, n_query) = 8 * n_rel * W bytes (ULTRA_ERR_WORKSPACE when smaller), the
+ * per-relation column masks, zeroed by a kernel of the entry and filled with integer atomicOr.
+ * The entry only enqueues -- two small launches, one pull over the CSR in which a lane group walks the first 1024 edges of its
+ * row, and, when n_edges > 1024, one launch over the edge array in pieces of 1024 that ORs the rest of longer rows into the stored
+ * words with integer atomicOr; no allocation, no host read, capturable.  All index arithmetic is 64-bit.  Row bounds are clamped to [0, n_edges]; an edge whose source or relation is out of range is skipped.
+ * ULTRA_ERR_BAD_SHAPE for a negative size, n_node >= 2^31 - 1, n_edges >= 2^31, n_rel >= 2^31 or n_query > 16 776 960;
+ * ULTRA_ERR_NULL_POINTER for a NULL row_ptr / bits / relation / out / workspace (src / rel when n_edges > 0), all before any
+ * device work.  n_query == 0 or n_node == 0: nothing to write, ULTRA_OK.
+ * Bytes moved at least: 12 * n_edges (16 with weights) + 8 * W * (n_edges + n_node).
+ *
+ * ultra_sets_rank: the filtered rank of many targets per query.
+ *   pred fp32 [n_query] rows of n_node scores, row q at pred + q * row_stride (row_stride >= n_node)
+ *   excluded uint64 [n_node][W] or NULL        the entities left out of query q's ranking (NULL: none)
+ *   target_ptr int64 [n_query + 1]             targets of query q: target_entity[target_ptr[q] .. target_ptr[q + 1])
+ *   target_entity int64 [n_target], rank int64 [n_target], written completely when target_ptr covers [0, n_target)
+ * Definition:  rank[t] = 1 + #{ v in [0, n_node) : bit (v, q_t) of excluded clear and pred[q_t][v] >= pred[q_t][target_entity[t]] }
+ * -- the comparison of ultra_filtered_rank_keys (ultra/task.py:311): pessimistic on ties, false for a NaN on either side.  A
+ * target that is not excluded counts itself.  A target outside [0, n_node) has no rank: 0.  target_ptr is clamped to [0, n_target].
+ * One launch, no (n_target, n_node) temporary, no allocation, no host read, capturable; integer counts, one owner per target:
+ * every schedule gives the same ranks.  ULTRA_ERR_BAD_SHAPE for a negative size, n_query >= 2^31, n_node >= 2^31 - 1 or
+ * row_stride < n_node; ULTRA_ERR_NULL_POINTER for a NULL pred / target_ptr / target_entity / rank, before any device work.
+ * Bytes moved at least, per block of 256 targets of a query: 12 * n_node.
+ */
+size_t ultra_sets_project_workspace(int64_t n_rel, int64_t n_query);
+int ultra_sets_project(const int32_t *row_ptr, const int32_t *src, const int32_t *rel, const float *w, int64_t n_node,
+                       int64_t n_edges, int64_t n_rel, const uint64_t *bits, const int64_t *relation, int64_t n_query,
+                       uint64_t *out, void *workspace, size_t workspace_bytes, void *stream);
+int ultra_sets_rank(const float *pred, int64_t n_query, int64_t n_node, int64_t row_stride, const uint64_t *excluded,
+                    const int64_t *target_ptr, const int64_t *target_entity, int64_t n_target, int64_t *rank, void *stream);
+
 
 /*
  * Dense epilogue of one Bellman-Ford layer, fused (dim must be 64, the shipped architecture):

@@ -146,3 +146,82 @@ def task_from_split_dir(path, checkpoint=None, device="cpu", **task_kwargs):
     splits = {name.split(".")[0]: triples[bounds[i]:bounds[i + 1]] for i, name in enumerate(SPLIT_FILES)}
     task.checkpoint_keys = (missing, unexpected)
     return task, splits
+
+
+def sample_queries(graph, structure, n_query, generator=None):
+    """``n_query`` logical queries of one structure grounded on ``graph`` -- a graph WITH inverse edges, such as
+    ``task.message_graph()`` or ``graph.undirected(add_inverse=True)`` -- so that each has an answer by construction (DESIGN.md
+    section 18; host-side and small: a Python loop per query).  Returns ``(anchors int64 (Q, A), relations int64 (Q, P), targets
+    int64 (Q,))`` on the CPU, columns in the order ``task.answer_query`` consumes them.
+
+    A query is grounded backwards from a target entity drawn uniformly.  ``('e', ops)``: ``ops`` are walked in reverse and every
+    ``'r'`` picks, uniformly, one edge of non-zero weight that ENDS in the current node, records its relation and moves to its
+    start; the node reached is the anchor.  ``((node, ...), ops)``: ``ops`` are walked back the same way, then the inner node is
+    grounded at the node reached.  Every branch of an intersection or union is grounded at the same node, except a branch whose
+    ops hold an ``'n'``: that one is grounded at a node drawn independently.  A node without an in-edge is a dead end: the target
+    is drawn again, at most 100 times, then ``RuntimeError``.  The draw is a function of the generator's state alone.  A query
+    without ``'n'`` contains its target in its exact answers on ``graph``."""
+    from .task import parse_query_structure
+    tree, n_anchor, n_relation = parse_query_structure(structure)
+    n_node, n_query = graph.num_node, int(n_query)
+    edges = graph.edge_list[graph.edge_weight != 0].cpu()
+    order = torch.argsort(edges[:, 1], stable=True)
+    tail_of, rel_of = edges[order, 0].tolist(), edges[order, 2].tolist()
+    start = torch.searchsorted(edges[order, 1].contiguous(), torch.arange(n_node + 1)).tolist()
+
+    def draw(n):
+        return int(torch.randint(0, n, (1,), generator=generator))
+
+    class DeadEnd(Exception):
+        pass
+
+    def walk_back(at, ops, relations):
+        """``relations`` of the ``'r'`` in ``ops`` (forward order) are appended; returns the node in front of ``ops``."""
+        found = []
+        for op in reversed(ops):
+            if op != "r":
+                continue
+            lo, hi = start[at], start[at + 1]
+            if hi == lo:
+                raise DeadEnd()
+            e = lo + draw(hi - lo)
+            found.append(rel_of[e])
+            at = tail_of[e]
+        relations.extend(reversed(found))
+        return at
+
+    def ground(node, at, anchors, relations):
+        """Appends the anchors and relations of ``node`` (depth-first, left to right) grounded at entity ``at``."""
+        kind = node[0]
+        if kind == "e":
+            anchors.append(walk_back(at, node[1], relations))
+        elif kind == "ops":
+            mine = []                                     # the inner node's relations come first
+            at = walk_back(at, node[2], mine)
+            ground(node[1], at, anchors, relations)
+            relations.extend(mine)
+        else:
+            for child in node[1]:
+                negated = "n" in (child[1] if child[0] == "e" else child[2] if child[0] == "ops" else ())
+                ground(child, draw(n_node) if negated else at, anchors, relations)
+
+    anchors = torch.zeros(n_query, n_anchor, dtype=torch.int64)
+    relations = torch.zeros(n_query, n_relation, dtype=torch.int64)
+    targets = torch.zeros(n_query, dtype=torch.int64)
+    if n_query and n_node < 1:
+        raise RuntimeError("sample_queries: the graph has no nodes")
+    for q in range(n_query):
+        for _ in range(100):
+            target, a, r = draw(n_node), [], []
+            try:
+                ground(tree, target, a, r)
+            except DeadEnd:
+                continue
+            break
+        else:
+            raise RuntimeError("sample_queries: 100 targets in a row led to a node without an in-edge (%d nodes, %d edges)"
+                               % (n_node, len(edges)))
+        anchors[q] = torch.tensor(a, dtype=torch.int64)
+        relations[q] = torch.tensor(r, dtype=torch.int64)
+        targets[q] = target
+    return anchors, relations, targets

@@ -882,12 +882,13 @@ def explain(task, triples, batch_size=16, head=False):
 
 
 @torch.no_grad()
-def answer_query(task, structure, anchors, relations, k=10, batch_size=16, **cut):
+def answer_query(task, structure, anchors, relations, k=10, batch_size=16, filtered=False, **cut):
     """``task.answer_query`` over any number of queries of ONE structure: the ids are parsed and range-checked once, then the
     queries run ``batch_size`` at a time (the last chunk is ragged: nothing is padded, a set projection costs what its queries
     cost) and everything runs eager -- a whole query is not captured in a hipGraph.  ``cut``: ``threshold`` / ``max_sources`` of
     ``task.project``.  Queries are independent columns of every kernel on the route, so each chunk equals ``task.answer_query``
-    of the same rows.  Returns ``(entities int64 (Q, k), membership fp32 (Q, k))``."""
+    of the same rows.  ``filtered``: as in ``task.answer_query``, the exact answers on the filter graph are left out.  Returns
+    ``(entities int64 (Q, k), membership fp32 (Q, k))``."""
     unknown = set(cut) - {"threshold", "max_sources"}
     if unknown:
         raise TypeError("answer_query: unknown arguments %s" % sorted(unknown))
@@ -897,11 +898,63 @@ def answer_query(task, structure, anchors, relations, k=10, batch_size=16, **cut
     if batch_size < 1:
         raise ValueError("answer_query: batch_size must be positive, got %d" % batch_size)
     tree, anchors, relations = task.query_inputs(structure, anchors, relations)
-    parts = [task._answer_query_checked(tree, anchors[i:i + batch_size], relations[i:i + batch_size], k, threshold, max_sources)
+    parts = [task._answer_query_checked(tree, anchors[i:i + batch_size], relations[i:i + batch_size], k, threshold, max_sources,
+                                        filtered)
              for i in range(0, len(anchors), batch_size)]
     if not parts:
-        return task._answer_query_checked(tree, anchors, relations, k, threshold, max_sources)
+        return task._answer_query_checked(tree, anchors, relations, k, threshold, max_sources, filtered)
     return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+@torch.no_grad()
+def evaluate_queries(task, structure, anchors, relations, batch_size=16, threshold=0.0, max_sources=None, return_ranks=False):
+    """Filtered ranking metrics of logical queries of ONE structure over their HARD answers.  With
+    ``easy`` = the exact answers on the fact graph and ``full`` = those on the filter graph (``task.query_answer_bits``, all
+    queries at once, 64 per machine word): ``hard = full & ~easy`` are the answers that need a held-out edge, and every hard
+    answer is ranked by its membership (``task.query_memberships``, ``batch_size`` queries at a time, with the cut ``threshold``
+    / ``max_sources``) among the entities outside ``excluded = easy | full`` and itself -- ``functional.set_ranks``, pessimistic
+    on ties.  Per query with at least one hard answer: the mean over its hard answers of ``1 / rank``, ``rank`` and ``rank <=
+    K``; the result is the mean of those over such queries, in float64 from the integer ranks: ``{"mrr", "mr", "hits@1",
+    "hits@3", "hits@10", "num_queries", "num_evaluated", "num_hard_answers"}`` (the metrics are NaN when no query has a hard
+    answer).  ``return_ranks``: also ``(query int64 (T,), entity int64 (T,), rank int64 (T,))``, ordered by query, then entity.
+    The hard answers are listed with ``nonzero``: one host read, so this call is not captured."""
+    from . import functional
+    task._check_cut(max_sources)
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("evaluate_queries: batch_size must be positive, got %d" % batch_size)
+    tree, anchors, relations = task.query_inputs(structure, anchors, relations)
+    n_query, n_node, dev = len(anchors), task.num_entity, anchors.device
+    if n_query:
+        easy = task.query_answer_bits(tree, anchors, relations, "fact")
+        full = task.query_answer_bits(tree, anchors, relations, "filter")
+        hard = functional.unpack_sets(full & ~easy, n_query)
+        query, entity = hard.nonzero(as_tuple=True)                               # ordered by query, then entity
+        count = hard.sum(dim=1)
+    else:
+        query = entity = count = torch.zeros(0, dtype=torch.int64, device=dev)
+    if len(query):
+        scores = torch.cat([task.query_memberships(tree, anchors[i:i + batch_size], relations[i:i + batch_size], threshold,
+                                                   max_sources).float() for i in range(0, n_query, batch_size)])
+        target_ptr = torch.cat([count[:1] * 0, count.cumsum(0)])
+        rank = functional.set_ranks(scores, easy | full, target_ptr, entity)
+    else:
+        rank = query
+    ranks, owner, per_query = rank.cpu(), query.cpu(), count.cpu()
+    evaluated = per_query > 0
+    n_evaluated = int(evaluated.sum())
+
+    def mean_of(values):
+        if n_evaluated == 0:
+            return float("nan")
+        sums = torch.zeros(n_query, dtype=torch.float64).index_add_(0, owner, values.double())
+        return float((sums[evaluated] / per_query[evaluated].double()).mean())
+
+    result = {"mrr": mean_of(1.0 / ranks.double()), "mr": mean_of(ranks)}
+    for k in (1, 3, 10):
+        result["hits@%d" % k] = mean_of(ranks <= k)
+    result.update(num_queries=n_query, num_evaluated=n_evaluated, num_hard_answers=int(len(ranks)))
+    return (result, (query, entity, rank)) if return_ranks else result
 
 
 # engine.evaluate scores distinct queries instead of triples when the shard holds at most this share of distinct queries

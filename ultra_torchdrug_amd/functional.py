@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -2174,3 +2174,181 @@ def hop_distance(csr, sources, num_iters=HOP_ITERS, targets=None, poll=None):
             targets.contiguous() if targets is not None else None, per_source, None if targets is not None else out,
             out if targets is not None else None, int(poll), ws, ws_bytes)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- exact (crisp) sets
+# A batch of Q entity sets over N entities, packed: int64 ``bits (N, W)``, ``W = ceil(Q / 64)``; bit ``q % 64`` of
+# ``bits[v, q // 64]`` says "v is in set q" (``include/ultra_rspmm.h``).  Bits of columns ``>= Q`` are
+# always 0.  Intersection and union are ``&`` and ``|``; a complement is ``~bits & column_mask(Q)``.
+SET_WORD = 64
+SET_PROJECT_SEGMENT = 1024  # edges of a row its lane group walks in ultra_sets_project; the rest goes to the tail launch (kSeg)
+SET_RANK_TARGETS = 256      # targets a block of ultra_sets_rank takes at once (kTargets of csrc/query_exact.hip)
+SET_RANK_TILE = 1024        # entities per LDS tile of ultra_sets_rank (kTile)
+
+
+def _bit_values(device):
+    return torch.ones(SET_WORD, dtype=torch.int64, device=device) << torch.arange(SET_WORD, device=device)
+
+
+def column_mask(n_query, device=None):
+    """int64 ``(W,)``: the bits of the columns ``< n_query`` of every word -- what a complement is ANDed with."""
+    n_query = int(n_query)
+    words = (n_query + SET_WORD - 1) // SET_WORD
+    mask = torch.full((words,), -1, dtype=torch.int64, device=device)
+    if n_query % SET_WORD:
+        mask[-1] = (1 << (n_query % SET_WORD)) - 1
+    return mask
+
+
+def pack_sets(member):
+    """bool ``(Q, N)`` memberships as packed sets int64 ``(N, W)``."""
+    if member.dim() != 2 or member.dtype != torch.bool:
+        raise RuntimeError("pack_sets: member must be bool (Q, N), got %s %s" % (member.dtype, tuple(member.shape)))
+    n_query, n_node = member.shape
+    words = (n_query + SET_WORD - 1) // SET_WORD
+    padded = torch.zeros(n_node, words * SET_WORD, dtype=torch.int64, device=member.device)
+    padded[:, :n_query] = member.t()
+    # distinct powers of two: the int64 sum is the OR (bit 63 is the sign bit, and wraps to it exactly)
+    return (padded.view(n_node, words, SET_WORD) * _bit_values(member.device)).sum(dim=2)
+
+
+def unpack_sets(bits, n_query):
+    """Packed sets int64 ``(N, W)`` as bool ``(Q, N)``."""
+    n_query = int(n_query)
+    if bits.dim() != 2 or bits.dtype != torch.int64 or bits.shape[1] != (n_query + SET_WORD - 1) // SET_WORD:
+        raise RuntimeError("unpack_sets: %d sets are int64 (N, %d), got %s %s"
+                           % (n_query, (n_query + SET_WORD - 1) // SET_WORD, bits.dtype, tuple(bits.shape)))
+    each = (bits.unsqueeze(-1) >> torch.arange(SET_WORD, device=bits.device)) & 1
+    return each.view(bits.shape[0], -1)[:, :n_query].t().bool()
+
+
+def seed_sets(nodes, n_node):
+    """One-hot packed sets: set ``q`` = ``{nodes[q]}``, ``nodes`` int64 ``(Q,)`` in ``[0, n_node)``.  Nodes may repeat across
+    queries: every (word, bit) is added at most once, so the accumulate-add of distinct powers of two is the OR, exactly."""
+    if nodes.dim() != 1 or nodes.dtype != torch.int64:
+        raise RuntimeError("seed_sets: nodes must be int64 (Q,), got %s %s" % (nodes.dtype, tuple(nodes.shape)))
+    n_query, n_node = nodes.numel(), int(n_node)
+    words = (n_query + SET_WORD - 1) // SET_WORD
+    bits = torch.zeros(n_node * words, dtype=torch.int64, device=nodes.device)
+    if n_query:
+        if not (nodes.is_cuda and torch.cuda.is_current_stream_capturing()) and (int(nodes.min()) < 0 or int(nodes.max()) >= n_node):
+            raise RuntimeError("seed_sets: nodes outside [0, %d)" % n_node)
+        q = torch.arange(n_query, device=nodes.device)
+        bits.index_add_(0, nodes * words + q // SET_WORD, _bit_values(nodes.device)[q % SET_WORD])
+    return bits.view(n_node, words)
+
+
+def _exact_csr(csr, n_relation):
+    if isinstance(csr, RelCSR):
+        return csr.csr_arrays + (csr.shape[2],)
+    if isinstance(csr, (tuple, list)) and len(csr) == 4 and n_relation is not None:
+        return tuple(csr) + (int(n_relation),)
+    raise TypeError("project_sets_exact: csr must be a RelCSR, or a (row_ptr, src, rel, w) tuple with n_relation given, got %s"
+                    % type(csr).__name__)
+
+
+def dense_project_sets_exact(csr, bits, relation, n_relation=None):
+    """:func:`project_sets_exact` in torch ops (the host twin of the same definition): a ``(Q, E)`` boolean per call."""
+    row_ptr, src, rel, w, n_rel = _exact_csr(csr, n_relation)
+    n_node, n_query = row_ptr.numel() - 1, relation.numel()
+    member = unpack_sets(bits, n_query)                                                  # (Q, N)
+    dst = torch.repeat_interleave(torch.arange(n_node, device=row_ptr.device), row_ptr.long().diff())
+    passes = member[:, src.long()] & (rel.long().unsqueeze(0) == relation.unsqueeze(1))  # (Q, E)
+    if w is not None:
+        passes = passes & (w != 0).unsqueeze(0)
+    reached = torch.zeros(n_query, n_node, dtype=torch.int32, device=row_ptr.device)
+    reached.index_add_(1, dst, passes.to(torch.int32))
+    return pack_sets(reached > 0)
+
+
+def project_sets_exact(csr, bits, relation, n_relation=None):
+    """One relation projection of packed crisp sets (``ultra_sets_project``, ``csrc/query_exact.hip``; the contract is in
+    ``include/ultra_rspmm.h``).
+
+    ``csr``: a :class:`RelCSR`, or ``(row_ptr int32 (N + 1,), src int32 (E,), rel int32 (E,), w fp32 (E,) | None)`` with
+    ``n_relation`` -- the coalesced dst-CSR of a graph with inverse edges (:attr:`RelCSR.csr_arrays`); ``bits`` int64 ``(N,
+    W)``; ``relation`` int64 ``(Q,)`` in ``[0, n_relation)``.  Returns int64 ``(N, W)``: entity ``v`` is in set ``q`` of the
+    result iff some edge ``u -> v`` of relation ``relation[q]`` and non-zero weight leaves a member ``u`` of set ``q``.  Bits of
+    columns ``>= Q`` come out 0 whatever ``bits`` holds there.  Two small launches, one pull over the CSR and one launch for the
+    tails of rows longer than 1024 edges; the values are not read while the stream is being captured.  CPU tensors take :func:`dense_project_sets_exact`."""
+    row_ptr, src, rel, w, n_rel = _exact_csr(csr, n_relation)
+    given = [t for t in (row_ptr, src, rel, w, bits, relation) if t is not None]
+    if any(not isinstance(t, torch.Tensor) or t.device != row_ptr.device for t in given):
+        raise RuntimeError("project_sets_exact: all tensors must share a device")
+    if (row_ptr.dtype != torch.int32 or src.dtype != torch.int32 or rel.dtype != torch.int32 or row_ptr.dim() != 1
+            or src.dim() != 1 or not row_ptr.numel() or rel.shape != src.shape):
+        raise RuntimeError("project_sets_exact: row_ptr (N + 1,), src (E,) and rel (E,) must be int32")
+    n_node, n_edges = row_ptr.numel() - 1, src.numel()
+    if w is not None and (w.dtype != torch.float32 or tuple(w.shape) != (n_edges,)):
+        raise RuntimeError("project_sets_exact: w must be fp32 (E,)")
+    if relation.dtype != torch.int64 or relation.dim() != 1:
+        raise RuntimeError("project_sets_exact: relation must be int64 (Q,)")
+    n_query = relation.numel()
+    words = (n_query + SET_WORD - 1) // SET_WORD
+    if bits.dtype != torch.int64 or tuple(bits.shape) != (n_node, words):
+        raise RuntimeError("project_sets_exact: %d sets over %d entities are int64 (%d, %d), got %s %s"
+                           % (n_query, n_node, n_node, words, bits.dtype, tuple(bits.shape)))
+    if n_rel < 0:
+        raise RuntimeError("project_sets_exact: n_relation must not be negative, got %d" % n_rel)
+    capturing = row_ptr.is_cuda and torch.cuda.is_current_stream_capturing()
+    if not capturing and n_query and (int(relation.min()) < 0 or int(relation.max()) >= n_rel):
+        raise RuntimeError("project_sets_exact: relations outside [0, %d)" % n_rel)
+    if not row_ptr.is_cuda:
+        return dense_project_sets_exact((row_ptr, src, rel, w), bits, relation, n_rel)
+    out = torch.empty(n_node, words, dtype=torch.int64, device=row_ptr.device)
+    if out.numel() == 0:
+        return out
+    ws_bytes = int(_lib.load().ultra_sets_project_workspace(n_rel, n_query))
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=row_ptr.device)
+    _launch(row_ptr.device, "ultra_sets_project", row_ptr.contiguous(), src.contiguous() if n_edges else None,
+            rel.contiguous() if n_edges else None, w.contiguous() if (w is not None and n_edges) else None, n_node, n_edges,
+            n_rel, bits.contiguous(), relation.contiguous(), n_query, out, ws, ws_bytes)
+    return out
+
+
+def dense_set_ranks(pred, excluded_bits, target_ptr, target_entity):
+    """:func:`set_ranks` in torch ops (the host twin of the same definition): a ``(T, N)`` boolean per call."""
+    n_query, n_node = pred.shape
+    query = torch.repeat_interleave(torch.arange(n_query, device=pred.device), target_ptr.diff())
+    counted = pred[query] >= pred[query, target_entity].unsqueeze(1)                     # (T, N); false for a NaN
+    if excluded_bits is not None:
+        counted = counted & ~unpack_sets(excluded_bits, n_query)[query]
+    return 1 + counted.sum(dim=1)
+
+
+def set_ranks(pred, excluded_bits, target_ptr, target_entity):
+    """Filtered ranks of many targets per query (``ultra_sets_rank``, ``csrc/query_exact.hip``; the contract is in
+    ``include/ultra_rspmm.h``): ``pred`` fp32 ``(Q, N)`` (the rows may be strided, not overlap), ``excluded_bits`` int64 ``(N,
+    W)`` packed sets or ``None``, ``target_ptr`` int64 ``(Q + 1,)`` ascending from 0 to ``T``, ``target_entity`` int64 ``(T,)``:
+    the targets of query ``q`` are ``target_entity[target_ptr[q]:target_ptr[q + 1]]``.  Returns int64 ``(T,)``,
+    ``rank[t] = 1 + #{v : v not excluded for q_t and pred[q_t, v] >= pred[q_t, target_entity[t]]}``: pessimistic on ties, false for
+    NaN (``ultra/task.py:311``), and a target that is not excluded counts itself.  One launch, no ``(T, N)`` temporary; the
+    values are not read while the stream is being captured.  CPU tensors take :func:`dense_set_ranks`."""
+    if pred.dim() != 2 or pred.dtype != torch.float32 or (pred.shape[1] > 1 and pred.stride(1) != 1):
+        raise RuntimeError("set_ranks: pred must be fp32 (Q, N) with contiguous rows")
+    n_query, n_node = pred.shape
+    if n_query > 1 and pred.stride(0) < n_node:
+        raise RuntimeError("set_ranks: the rows of pred overlap")
+    words = (n_query + SET_WORD - 1) // SET_WORD
+    if excluded_bits is not None and (excluded_bits.dtype != torch.int64 or tuple(excluded_bits.shape) != (n_node, words)
+                                      or excluded_bits.device != pred.device):
+        raise RuntimeError("set_ranks: excluded_bits must be int64 (%d, %d) on %s" % (n_node, words, pred.device))
+    if (target_ptr.dtype != torch.int64 or tuple(target_ptr.shape) != (n_query + 1,) or target_entity.dtype != torch.int64
+            or target_entity.dim() != 1 or target_ptr.device != pred.device or target_entity.device != pred.device):
+        raise RuntimeError("set_ranks: target_ptr must be int64 (%d,) and target_entity int64 (T,) on %s"
+                           % (n_query + 1, pred.device))
+    n_target = target_entity.numel()
+    capturing = pred.is_cuda and torch.cuda.is_current_stream_capturing()
+    if not capturing:
+        if int(target_ptr[0]) != 0 or int(target_ptr[-1]) != n_target or bool((target_ptr[1:] < target_ptr[:-1]).any()):
+            raise RuntimeError("set_ranks: target_ptr must run from 0 to T = %d without decreasing" % n_target)
+        if n_target and (int(target_entity.min()) < 0 or int(target_entity.max()) >= n_node):
+            raise RuntimeError("set_ranks: targets outside [0, %d)" % n_node)
+    if not pred.is_cuda:
+        return dense_set_ranks(pred, excluded_bits, target_ptr, target_entity)
+    rank = torch.empty(n_target, dtype=torch.int64, device=pred.device)
+    if n_target:
+        _launch(pred.device, "ultra_sets_rank", pred, n_query, n_node, pred.stride(0) if n_query > 1 else n_node,
+                None if excluded_bits is None else excluded_bits.contiguous(), target_ptr.contiguous(),
+                target_entity.contiguous(), n_target, rank)
+    return rank

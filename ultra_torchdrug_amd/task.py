@@ -699,8 +699,64 @@ class KnowledgeGraphCompletion(nn.Module):
 
         return walk(tree)
 
+    def _exact_graph(self, graph):
+        """The graph with inverse edges that :meth:`query_answers` walks: ``"fact"`` -- :meth:`message_graph` -- or ``"filter"``
+        -- the current context's filter graph through the same memoised ``_undirected``."""
+        if graph == "fact":
+            return self.message_graph()
+        if graph == "filter":
+            return self.model._undirected(self.graph)
+        raise ValueError("query_answers: graph must be \"fact\" or \"filter\", got %r" % (graph,))
+
+    def query_answer_bits(self, tree, anchors, relations, graph="fact"):
+        """:meth:`query_answers` for a parsed structure and checked inputs (:meth:`query_inputs`), as packed sets int64 ``(N,
+        ceil(Q / 64))`` (``functional.pack_sets``); the columns are consumed as :meth:`query_memberships` consumes them."""
+        from . import functional
+        csr = self._exact_graph(graph).relcsr
+        n_node = self.num_entity
+        columns = functional.column_mask(len(anchors), anchors.device)
+        at = {"e": 0, "r": 0}
+
+        def take(kind, table):
+            at[kind] += 1
+            return table[:, at[kind] - 1]
+
+        def run_ops(bits, ops):
+            for op in ops:
+                bits = functional.project_sets_exact(csr, bits, take("r", relations)) if op == "r" else ~bits & columns
+            return bits
+
+        def walk(node):
+            kind = node[0]
+            if kind == "e":
+                return run_ops(functional.seed_sets(take("e", anchors), n_node), node[1])
+            if kind == "ops":
+                return run_ops(walk(node[1]), node[2])
+            parts = [walk(child) for child in node[1]]
+            bits = parts[0]
+            for other in parts[1:]:
+                bits = bits & other if kind == "i" else bits | other
+            return bits
+
+        return walk(tree)
+
     @torch.no_grad()
-    def answer_query(self, structure, anchors, relations, k=10, threshold=0.0, max_sources=None):
+    def query_answers(self, structure, anchors, relations, graph="fact"):
+        """The EXACT answer sets of logical queries of one structure on a graph of the current context, bool ``(Q, N)`` (an
+        addition of this package): the symbolic evaluation of the query over the stated edges, no model
+        involved.  ``structure`` / ``anchors`` / ``relations`` as in :meth:`answer_query`.  ``graph="fact"``: the edges the model
+        sees (:meth:`message_graph`) -- the EASY answers; ``graph="filter"``: every known triple with its inverse -- all known
+        answers.  An anchor is a one-hot set (``functional.seed_sets``), ``'r'`` the relation-restricted expansion
+        ``functional.project_sets_exact`` (HIP on the device), ``'n'`` the complement, an intersection / union the AND / OR of
+        its branches, on 64 queries per machine word."""
+        from . import functional
+        tree, anchors, relations = self.query_inputs(structure, anchors, relations)
+        if len(anchors) == 0:
+            return torch.zeros(0, self.num_entity, dtype=torch.bool, device=anchors.device)
+        return functional.unpack_sets(self.query_answer_bits(tree, anchors, relations, graph), len(anchors))
+
+    @torch.no_grad()
+    def answer_query(self, structure, anchors, relations, k=10, threshold=0.0, max_sources=None, filtered=False):
         """The ``k`` best answers of multi-hop logical queries of ONE structure (an addition of this package: the 14 query
         types of the BetaE benchmarks, answered as ULTRAQuery's "LP" variant does -- this frozen link predictor as the relation
         projection over fuzzy sets, non-parametric fuzzy logic in between).  ``structure``: a name of ``QUERY_STRUCTURES`` or a
@@ -710,13 +766,14 @@ class KnowledgeGraphCompletion(nn.Module):
         with the cut ``threshold`` / ``max_sources``; ``'n'`` is ``1 - p``; an intersection is the product of its branches,
         left to right; a union ``1 - prod(1 - p_i)``.  The final set is never cut.  Returns ``(entities int64 (Q, k),
         membership fp32 (Q, k))`` in the order ``functional.topk_keys`` defines (membership descending, ties by ascending entity);
-        slots whose membership is not positive hold ``-1`` / ``0.0``.  Known answers are NOT filtered: a multi-hop filter needs the
-        query traversed on the filter graph, which this call does not do."""
+        slots whose membership is not positive hold ``-1`` / ``0.0``.  ``filtered``: the entities that answer the query exactly on
+        the filter graph (:meth:`query_answers` with ``graph="filter"``) get membership 0 before the top-K, so no known answer is
+        returned; the default filters nothing."""
         self._check_cut(max_sources)
         tree, anchors, relations = self.query_inputs(structure, anchors, relations)
-        return self._answer_query_checked(tree, anchors, relations, k, threshold, max_sources)
+        return self._answer_query_checked(tree, anchors, relations, k, threshold, max_sources, filtered)
 
-    def _answer_query_checked(self, tree, anchors, relations, k, threshold, max_sources):
+    def _answer_query_checked(self, tree, anchors, relations, k, threshold, max_sources, filtered=False):
         from . import functional
         k = int(k)
         if not 1 <= k <= TOPK_MAX:
@@ -724,6 +781,9 @@ class KnowledgeGraphCompletion(nn.Module):
         if len(anchors) == 0:
             return anchors.new_zeros(0, k), torch.zeros(0, k, device=anchors.device)
         p = self.query_memberships(tree, anchors, relations, threshold, max_sources).float().contiguous()
+        if filtered:
+            known = functional.unpack_sets(self.query_answer_bits(tree, anchors, relations, "filter"), len(anchors))
+            p = torch.where(known, torch.zeros_like(p), p).contiguous()
         ops = backend.get()
         zero = torch.zeros(len(p), dtype=torch.int64, device=p.device)
         value, index = (ops.topk_keys if ops.accepts(p) else functional.topk_keys)(p, k, None, zero, zero, 1)
