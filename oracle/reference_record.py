@@ -29,6 +29,14 @@ Files (every tensor ``x`` as ``x/T`` = the float64 run where one exists and ``x/
   the training branch + loss for ``adversarial_temperature`` 1 and 0 with every parameter gradient in the compact form of
   ``reference_fixture.compact``.  The relation model is float32 only (``rel_model.py:353``): runs ``R0`` .. ``R4``, ``R1`` .. ``R4``
   with the edge lists of both graphs permuted (the same multiset of edges: equally valid runs).
+* ``reference_architectures.npz``: ``TransferNBFNet`` with 3 layers in the variants of ``reference_fixture.ARCHITECTURES`` (one
+  argument of the shipped set changed each; the reference's constructor defaults; max; mean of TransE) at 64 and 16 columns,
+  ``base`` and ``max_plain`` also at 6, on the entity record's graph, batch and relation tables: eval scores of the batch and of
+  its four queries over all entities, hidden states in the compact form, and a train-mode run under grad (scores, compact
+  gradients of a seeded upstream, stacked into one matrix per case in the sorted order of their names).  The weights are NOT
+  stored (``RF.draw_state`` regenerates them; the json holds a float64 sum per tensor), and only the batch's scores keep ``R0``.
+  Two ``RelNBFNet`` (16 wide; 2 layers at 64) on the relation graph, float32, ``ref_dev`` over two runs on permuted edge lists.
+  Not recorded, because the reference's code raises: ``symmetric=True``, unequal ``hidden_dims``, ``mod=False, project=False``.
 * ``reference_fixtures.json``: shapes, seeds, torch version, and per tensor ``scale`` and ``ref_dev`` (``max|R0 - T|``, or
   ``max_k max|Rk - R0|``).  Its ``mi355x`` section (floors measured on the device) is kept as it is.
 """
@@ -46,7 +54,8 @@ import reference_fixture as RF                      # noqa: E402
 from oracle import torchdrug_standin as standin     # noqa: E402
 
 SCORE_FLOOR_CAP = 2e-5          # the largest floor a score comparison may be granted (tests/test_reference_definition_gpu.py)
-FILES = ("reference_layers.npz", "reference_layers_masked.npz", "reference_entity_model.npz", "reference_pipeline.npz")
+FILES = ("reference_layers.npz", "reference_layers_masked.npz", "reference_entity_model.npz", "reference_pipeline.npz",
+         "reference_architectures.npz")
 METRICS = ("mr", "mrr", "hits@1", "hits@3", "hits@10", "mrr-tail", "hits@1-tail", "hits@10-tail", "mrr-head")
 
 
@@ -155,8 +164,9 @@ def _spy_hiddens(model):
     model.bellmanford = spy
 
     def hiddens():
+        # (the last hidden state stands right before the query columns, with and without ``concat_hidden``; equal widths)
         width = seen["inputs"][-1].shape[-1]
-        return seen["inputs"][1:] + [seen["feature"][..., :width]]
+        return seen["inputs"][1:] + [seen["feature"][..., -2 * width:-width]]
 
     def release():
         for handle in handles:
@@ -310,6 +320,96 @@ def _assert_tie_condition(run, stat, positives):
     assert near <= 0.1 * pred.shape[0] * 2, "%d of %d (triple, side) pairs are near ties: change the seed" % (near, 2 * len(pred))
 
 
+# --------------------------------------------------------------------------------------------------------- (d)
+def _compact_gradients(got, model, tables):
+    for key, p in model.named_parameters():
+        if p.grad is not None:
+            got["train/d_" + key] = RF.compact(key, _np(p.grad))
+    for i, table in enumerate(tables):
+        if table.grad is not None:
+            got["train/d_rel_query_list.%d" % i] = RF.compact("rel_query_list.%d" % i, _np(table.grad))
+
+
+def _architecture_run(U, dtype, name, width, state, triples):
+    """Eval (batch scores, scores over all entities, hidden states) and one training forward + backward of one variant."""
+    torch.set_default_dtype(dtype)
+    try:
+        kwargs = RF.arch_arguments(name, width)
+        model = U.model.TransferNBFNet(**kwargs)
+        if state is None:
+            state = RF.draw_state({k: v.shape for k, v in model.state_dict().items()}, RF.arch_seed(name, width))
+        _load_state(model, state, dtype).eval()
+        n_layers = len(kwargs["hidden_dims"])
+        h, t, r, _, _ = RF.entity_batch(triples)
+        got = {}
+        with torch.no_grad():
+            tables = [_t(table, dtype) for table in RF.rel_query_list(n_layers + 1, 4, width)]
+            graph = standin.Graph(triples[:RF.ENTITY_TRIPLES], None, RF.ENTITY_NODES, RF.ENTITY_RELATIONS)
+            seen, hiddens, release = _spy_hiddens(model)
+            got["scores"] = _np(model(graph, tables, _t(h), _t(t), _t(r)))
+            release()
+            for i, hidden in enumerate(hiddens()):
+                got["hidden%d_rows" % i] = _np(hidden[list(RF.HIDDEN_ROWS)])
+                got["hidden%d_rowsum" % i] = _np(hidden.sum(-1))
+            ha, ta, ra = RF.arch_all_entities(triples)
+            got["scores_all"] = _np(model(graph, tables, _t(ha), _t(ta), _t(ra)))
+        model.train()
+        tables = [_t(table, dtype).requires_grad_() for table in RF.rel_query_list(n_layers + 1, 4, width)]
+        graph = standin.Graph(triples[:RF.ENTITY_TRIPLES], None, RF.ENTITY_NODES, RF.ENTITY_RELATIONS)
+        score = model(graph, tables, _t(h), _t(t), _t(r))
+        score.backward(_t(RF.arch_upstream(name, width), dtype))
+        got["train/scores"] = _np(score)
+        _compact_gradients(got, model, tables)
+        return got, state
+    finally:
+        torch.set_default_dtype(torch.float32)
+
+
+def record_architectures(U):
+    """``TransferNBFNet`` in the variants of ``reference_fixture.ARCHITECTURES`` (3 layers; 64, 16 and -- two of them -- 6 wide) on
+    the entity record's graph, batch and relation tables, and two ``RelNBFNet`` on the pipeline record's relation graph.  The
+    weights are not stored: ``RF.draw_state`` regenerates them, and the returned checksums (float64 sum per tensor) pin the draw.
+    Min / max (``max_plain``, ``defaults``): the fact graph with inverse edges holds every triple once (asserted), so the recorded
+    branch and the rspmm branch are one function on EVERY row, and no row is left out."""
+    rec, checksums = Record(), {}
+    triples = RF.entity_triples()
+    assert RF.undirected_is_distinct(triples), "a duplicate triple: min / max of the two branches differ at its row"
+    for name, width in RF.ARCH_CASES:
+        truth, state = _architecture_run(U, torch.float64, name, width, None, triples)
+        single, _ = _architecture_run(U, torch.float32, name, width, state, triples)
+        assert sorted(truth) == sorted(single)
+        tag = "%s_%d" % (name, width)
+        checksums[tag] = {key: float(np.asarray(value, dtype=np.float64).sum()) for key, value in state.items()}
+        into = rec
+        for key in truth:
+            into.tensor("%s/%s" % (tag, key), truth[key], [single[key]])
+            if key not in ("scores", "train/scores"):     # ref_dev is kept; the float32 run itself for the batch's scores only
+                del into.arrays["%s/%s/R0" % (tag, key)]
+        # the compact gradients (50 numbers each) as ONE matrix, rows in the sorted order of their names: a zip member per
+        # gradient would cost as much as its numbers (``reference_runs.arrays`` unpacks them under their own keys)
+        names = sorted(key for key in truth if key.startswith("train/d_"))
+        into.arrays["%s/train/gradients/T" % tag] = np.stack([into.arrays.pop("%s/%s/T" % (tag, key)) for key in names])
+    # the relation model: float32 only (rel_model.py:353)
+    fact = standin.Graph(triples[:RF.ENTITY_TRIPLES], None, RF.ENTITY_NODES, RF.ENTITY_RELATIONS)
+    _, _, _, positives, _ = RF.entity_batch(triples)
+    for tag, kwargs in RF.REL_ARCHITECTURES.items():
+        rel_model = U.rel_model.RelNBFNet(input_type="ones", num_relation=2 * RF.ENTITY_RELATIONS, **kwargs)
+        state = RF.draw_state({k: v.shape for k, v in rel_model.state_dict().items()}, 9100 + kwargs["hidden"] + kwargs["num_layers"])
+        _load_state(rel_model, state, torch.float32).eval()
+        checksums[tag] = {key: float(np.asarray(value, dtype=np.float64).sum()) for key, value in state.items()}
+        rel_graph = rel_model.construct_relation_graph(fact)
+        runs = []
+        rng = np.random.RandomState(6)
+        for k in range(3):                  # the edge list permuted: equally valid runs, whose spread is ref_dev
+            rel_k = rel_graph if not k else rel_graph.edge_mask(_t(rng.permutation(rel_graph.num_edge)))
+            with torch.no_grad():
+                runs.append(_np(rel_model(rel_k, None, _t(positives[:, 2]))["node_feature"]))
+        rec.tensor(tag + "/relation_output", None, runs)
+        for k in (1, 2):
+            del rec.arrays["%s/relation_output/R%d" % (tag, k)]
+    return rec, checksums
+
+
 # --------------------------------------------------------------------------------------------------------- driver
 def record(reference):
     torch.set_num_threads(1)
@@ -319,11 +419,16 @@ def record(reference):
     entity = record_entity(U)
     state = {k[len("main/"):]: v.astype(np.float64) for k, v in entity.arrays.items() if k.startswith("main/") and v.dtype == np.float16}
     pipeline = record_pipeline(U, state)
-    records = dict(zip(FILES, (layers, masked, entity, pipeline)))
+    architectures, checksums = record_architectures(U)
+    records = dict(zip(FILES, (layers, masked, entity, pipeline, architectures)))
     meta = dict(torch=torch.__version__.split("+")[0], numpy_stream="RandomState (MT19937)", threads=1, grid="2^-10",
                 seeds=dict(torch_manual_seed=0, layer_graph=370, layer_inputs="1000 + 10 * aggregate + message", layer_weights="100 + 11 * pair",
                            entity_triples=211, entity_batch=49, rel_query_list="77 + dim", entity_weights="7000 + dim + layers",
-                           relation_weights=9001, edge_permutations=5, compact="sum of the name's characters + size"),
+                           relation_weights=9001, edge_permutations=5, compact="sum of the name's characters + size",
+                           architecture_weights="8000 + 100 * variant + width", architecture_upstream="weights' seed + 50000",
+                           architecture_relation_weights="9100 + hidden + layers", architecture_edge_permutations=6),
+                architectures=dict(layers=RF.ARCH_LAYERS, cases=[list(c) for c in RF.ARCH_CASES], not_runnable=RF.ARCH_NOT_RUNNABLE,
+                                   relation_models=RF.REL_ARCHITECTURES, weight_checksums=checksums),
                 metrics=list(METRICS), hidden_rows=list(RF.HIDDEN_ROWS), layer_dim=RF.LAYER_DIM,
                 layer_duplicate_row=RF.LAYER_DUPLICATE_ROW,
                 shapes=dict(layer_graph=[RF.LAYER_NODES, int(len(RF.layer_graph()["edge_list"])), 2 * RF.LAYER_BASE_RELATIONS],

@@ -175,3 +175,88 @@ def compact(name, array):
     pick = rng.randint(0, flat.size, size=48)
     probe = grid(rng, flat.shape, -1.0, 1.0)
     return np.concatenate([flat[pick], [float(flat @ probe), float(np.sqrt(flat @ flat))]])
+
+
+# ----------------------------------------------------------------------------------------------- (d) other architectures
+ARCH_LAYERS = 3                     # a first, a middle and a last layer
+ARCH_SHIPPED = dict(message_func="distmult", aggregate_func="sum", short_cut=True, layer_norm=True, activation="relu",
+                    concat_hidden=False, num_mlp_layer=2, project=True, mod=True)
+# every variant changes ONE argument of the shipped set (the last three: the sets the names say)
+ARCHITECTURES = {
+    "base": {},
+    "no_shortcut": dict(short_cut=False),
+    "no_ln": dict(layer_norm=False),
+    "tanh": dict(activation="tanh"),
+    "concat": dict(concat_hidden=True),
+    "mlp1": dict(num_mlp_layer=1),
+    "mlp3": dict(num_mlp_layer=3),
+    "no_project": dict(project=False),
+    "not_mod": dict(mod=False),                                     # GeneralizedRelationalConvNBF, dependent=True
+    "one_layer": dict(layers=1),
+    "defaults": dict(aggregate_func="pna", short_cut=False, layer_norm=False),      # the reference's constructor defaults
+    "max_plain": dict(aggregate_func="max", layer_norm=False, short_cut=False),
+    "mean_transe": dict(aggregate_func="mean", message_func="transe"),
+}
+ARCH_WIDTHS = {name: ((64, 16, 6) if name in ("base", "max_plain") else (64, 16)) for name in ARCHITECTURES}
+ARCH_CASES = [(name, width) for name in ARCHITECTURES for width in ARCH_WIDTHS[name]]
+# configurations the reference's own code cannot run: recorded nowhere, and why
+ARCH_NOT_RUNNABLE = {
+    "symmetric": "symmetric=True: ultra/model.py:187 passes a fourth argument to bellmanford",
+    "unequal_hidden_dims": "unequal hidden_dims: ultra/layer.py:264 concatenates a boundary of another width",
+    "not_mod_no_project": "mod=False, project=False: ultra/model.py:153 assigns a tensor over an nn.Embedding",
+}
+REL_ARCHITECTURES = {"rel_hidden16": dict(input_dim=16, hidden=16, num_layers=6), "rel_two_layers": dict(input_dim=64, hidden=64, num_layers=2)}
+
+
+def arch_arguments(name, width):
+    """Constructor arguments of ``TransferNBFNet`` for one variant at one width."""
+    kwargs = dict(ARCH_SHIPPED)
+    kwargs.update(ARCHITECTURES[name])
+    layers = kwargs.pop("layers", ARCH_LAYERS)
+    kwargs.update(input_dim=width, hidden_dims=[width] * layers, num_relation=ENTITY_RELATIONS)
+    return kwargs
+
+
+def arch_seed(name, width):
+    return 8000 + 100 * list(ARCHITECTURES).index(name) + width
+
+
+def arch_all_entities(triples):
+    """The batch's four queries with EVERY entity on the corrupted side (``ultra/task.py:249-259``): rows 0 - 1 list all tails,
+    rows 2 - 3 all heads."""
+    _, _, _, positives, _ = entity_batch(triples)
+    every = np.tile(np.arange(ENTITY_NODES), (4, 1))
+    h = np.repeat(positives[:, :1], ENTITY_NODES, axis=1)
+    t = np.repeat(positives[:, 1:2], ENTITY_NODES, axis=1)
+    r = np.repeat(positives[:, 2:3], ENTITY_NODES, axis=1)
+    t[:2], h[2:] = every[:2], every[2:]
+    return h, t, r
+
+
+def arch_upstream(name, width):
+    """The seeded gradient of the 4 x 9 training scores."""
+    return grid(np.random.RandomState(arch_seed(name, width) + 50000), (4, 9), -1.0, 1.0)
+
+
+def undirected_is_distinct(triples):
+    """Whether the fact graph with its inverse edges holds no triple twice: then min / max see the same messages on the
+    materialised branch and on the rspmm branch (one coalesced edge per message) and every row can be held."""
+    fact = triples[:ENTITY_TRIPLES]
+    both = np.concatenate([fact, np.stack([fact[:, 1], fact[:, 0], fact[:, 2] + ENTITY_RELATIONS], axis=1)])
+    return len(np.unique(both, axis=0)) == len(both)
+
+
+EXTREME_ARCHITECTURES = ("defaults", "max_plain")       # the variants that aggregate with min / max
+
+
+def gradient_passes_an_extreme(name, width, key):
+    """Whether the gradient ``key`` of a training run of variant ``name`` passes through the backward of a min / max
+    aggregation.  Every node a query has not reached holds the same row, so the min / max of a stack tie structurally, and at a
+    tie the reference's two branches are different functions: the recorded branch (``scatter_max``) hands the gradient to ONE of
+    the tied messages, the rspmm branch (torchdrug's native backward, which this package's operators mirror) to EVERY tied
+    edge in full.  The score head and the last layer's ``linear`` lie behind every aggregation; everything else lies before one."""
+    if name not in EXTREME_ARCHITECTURES or "/train/d_" not in key:
+        return False
+    last = len(arch_arguments(name, width)["hidden_dims"]) - 1
+    behind = key.split("/train/d_")[1]
+    return not (behind.startswith("mlp.") or behind.startswith("layers.%d.linear." % last))

@@ -23,6 +23,13 @@ def arrays(name):
     if name not in _CACHE:
         with np.load(os.path.join(GOLDEN, "reference_%s.npz" % name)) as f:
             _CACHE[name] = {k: f[k] for k in f.files}
+        for key in [k for k in _CACHE[name] if k.endswith("/train/gradients/T")]:
+            # the compact gradients of one architecture record, stacked in the sorted order of their names
+            prefix = key[:-len("gradients/T")] + "d_"
+            names = sorted(k for k in stats(name) if k.startswith(prefix))
+            matrix = _CACHE[name].pop(key)
+            assert len(names) == len(matrix), key
+            _CACHE[name].update({n + "/T": row for n, row in zip(names, matrix)})
     return _CACHE[name]
 
 
@@ -224,6 +231,104 @@ def entity_run(name, device, dtype=torch.float32, mode="plain", materialised=Fal
             got["%s/hidden%d_rows" % (name, i)] = hidden[list(RF.HIDDEN_ROWS)]
             got["%s/hidden%d_rowsum" % (name, i)] = hidden.double().sum(-1)
     return got
+
+
+# ------------------------------------------------------------------------------------------------- (d) other architectures
+def _drawn_state(tag, module, seed):
+    """The weights ``RF.draw_state`` regenerates for ``module``, checked against the recorded per-tensor sums."""
+    state = RF.draw_state({k: v.shape for k, v in module.state_dict().items()}, seed)
+    want = stats()["architectures"]["weight_checksums"][tag]
+    assert sorted(want) == sorted(state), (tag, sorted(set(want) ^ set(state)))
+    for key, value in state.items():
+        assert float(value.sum()) == want[key], (tag, key)
+    return {k: torch.from_numpy(v) for k, v in state.items()}
+
+
+def architecture_model(name, width, device, dtype=torch.float32):
+    from ultra_torchdrug_amd.model import TransferNBFNet
+    model = TransferNBFNet(**RF.arch_arguments(name, width))
+    model.load_state_dict(_drawn_state("%s_%d" % (name, width), model, RF.arch_seed(name, width)))
+    return model.to(device=device, dtype=dtype)
+
+
+def architecture_run(name, width, device, dtype=torch.float32, mode="eval", materialised=False):
+    """This package's ``TransferNBFNet`` in the variant ``name`` (``RF.ARCHITECTURES``) with the regenerated weights on the
+    recorded inputs, under the keys of ``reference_architectures.npz``.  ``mode``: ``eval`` -- the scores of the 4 x 9 batch and
+    every layer's hidden state; ``all_entities`` -- the scores of the four queries over every entity (the caller's promise
+    ``all_entities=True``, as ``task.predict`` gives it); ``train`` -- train mode under grad: the scores and, for the seeded
+    upstream, the compact gradient of every parameter and relation table that receives one."""
+    tag = "%s_%d" % (name, width)
+    triples = RF.entity_triples()
+    with default_dtype(dtype):
+        model = architecture_model(name, width, device, dtype)
+        n_layers = len(model.layers)
+        graph = fact_graph(device)
+        und = model._undirected(graph)
+        und.requires_grad = bool(materialised)
+        und.edge_weight = und.edge_weight.to(dtype)
+        tables = [_t(table, device, dtype) for table in RF.rel_query_list(n_layers + 1, 4, width)]
+        if mode == "train":
+            model.train()
+            tables = [table.requires_grad_() for table in tables]
+            h, t, r, _, _ = RF.entity_batch(triples)
+            with torch.enable_grad():
+                score = model(graph, tables, _t(h, device), _t(t, device), _t(r, device))
+                score.backward(_t(RF.arch_upstream(name, width), device, dtype))
+            got = {tag + "/train/scores": score.detach()}
+            for key, p in list(model.named_parameters()) + [("rel_query_list.%d" % i, table) for i, table in enumerate(tables)]:
+                if p.grad is not None:
+                    got["%s/train/d_%s" % (tag, key)] = RF.compact(key, p.grad.detach().cpu().double().numpy())
+            return got
+        model.eval()
+        if mode == "all_entities":
+            h, t, r = RF.arch_all_entities(triples)
+            with torch.no_grad():
+                score = model(graph, tables, _t(h, device), _t(t, device), _t(r, device), all_entities=True)
+            return {tag + "/scores_all": score}
+        assert mode == "eval", mode
+        h, t, r, _, _ = RF.entity_batch(triples)
+        hiddens = []
+        handles = [conv.register_forward_hook(lambda mod, args, out: hiddens.append(out.detach())) for conv in model.layers]
+        try:
+            with torch.no_grad():
+                score = model(graph, tables, _t(h, device), _t(t, device), _t(r, device))
+        finally:
+            for handle in handles:
+                handle.remove()
+    got = {tag + "/scores": score}
+    assert len(hiddens) == n_layers
+    for i, hidden in enumerate(hiddens):                    # (the layers of this package add the shortcut themselves)
+        got["%s/hidden%d_rows" % (tag, i)] = hidden[list(RF.HIDDEN_ROWS)]
+        got["%s/hidden%d_rowsum" % (tag, i)] = hidden.double().sum(-1)
+    return got
+
+
+def check_gradient_keys(tag, got):
+    """The gradients of a training run against the recorded set: every recorded one is there, and one the reference leaves
+    ``None`` is, where this package produces it at all, exactly zero."""
+    prefix = tag + "/train/d_"
+    want = {k for k in stats("architectures") if k.startswith(prefix)}
+    have = {k for k in got if k.startswith(prefix)}
+    assert want <= have, sorted(want - have)
+    for key in have - want:
+        assert not np.asarray(got[key]).any(), key
+    return sorted(want)
+
+
+def relation_architecture_run(tag, device, materialised=False):
+    """The relation-model twin: this package's ``RelNBFNet`` in the configuration ``RF.REL_ARCHITECTURES[tag]`` on the relation
+    graph of the fact graph, for the batch's four relations (float32 only, as the reference's)."""
+    from ultra_torchdrug_amd.rel_model import RelNBFNet, construct_relation_graph
+    kwargs = RF.REL_ARCHITECTURES[tag]
+    rel_model = RelNBFNet(input_type="ones", num_relation=2 * RF.ENTITY_RELATIONS, **kwargs)
+    rel_model.load_state_dict(_drawn_state(tag, rel_model, 9100 + kwargs["hidden"] + kwargs["num_layers"]))
+    rel_model = rel_model.float().to(device).eval()
+    rel_graph = construct_relation_graph(fact_graph(device))
+    rel_graph.requires_grad = bool(materialised)
+    _, _, _, positives, _ = RF.entity_batch(RF.entity_triples())
+    with torch.no_grad():
+        out = rel_model(rel_graph, None, _t(positives[:, 2], device))["node_feature"]
+    return {tag + "/relation_output": out}
 
 
 # ------------------------------------------------------------------------------------------------- (c) the task

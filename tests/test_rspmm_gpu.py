@@ -190,20 +190,29 @@ def test_wide_batch_forward_and_backward_match_oracle(oracle):
     assert _same(d_x.cpu().numpy(), d_x_o) and _same(d_rel.cpu().numpy(), d_rel_o)
 
 
+# (D, B): the width of a query block and the number of queries; B * D spans at least two 64-column tiles.  D = 6: rows that are
+# no multiple of 16 bytes (B = 11, F = 66) and rows that are, with blocks that are not (B = 12, F = 72: F % 4 == 0, so the block
+# width alone keeps the four-columns-per-lane kernels out, ``boundary_ok`` in csrc/plan_path.h)
+BOUNDARY_BLOCKS = [(64, 5), (32, 5), (16, 5), (8, 9), (4, 17), (6, 11), (6, 12)]
+
+
+@pytest.mark.parametrize("D,B", BOUNDARY_BLOCKS, ids=["D%d-B%d" % c for c in BOUNDARY_BLOCKS])
 @pytest.mark.parametrize("flags", [0, 4, 1])
-def test_sparse_boundary_equals_dense_boundary(flags):
+def test_sparse_boundary_equals_dense_boundary(flags, D, B):
     """ultra_rspmm_forward_boundary_f32: the Bellman-Ford boundary as (node per query, value per query) instead of the
     dense scatter_add_ result (model.py:106-107) -- identical output in every kernel (quad / packed / general),
-    including split rows (node 2 is a hub: fix-up path), an isolated boundary node and a repeated node."""
+    including split rows (node 2 is a hub: fix-up path), an isolated boundary node and a repeated node -- for every block
+    width a model can have: a whole tile per query, several queries per tile, blocks that straddle a tile's end."""
     import ultra_torchdrug_amd as U
     from ultra_torchdrug_amd import functional as UF
-    n, r, B, D = 300, 9, 5, 64
+    n, r = 300, 9
     g = random_graph(seed=11, n_node=n, n_edge=9000, n_rel=r, skew=True, hub_row=2, hub_edges=1000, isolated=20)
     relation, x = _inputs(4, n, r, B * D)
     dev = _dev()
     csr = _relcsr(g, n, n, r)
     t = lambda a: torch.from_numpy(a).to(dev)
-    node = torch.tensor([2, 7, 299, 7, 150], dtype=torch.int64, device=dev)          # hub, twice 7, isolated 299
+    nodes = [2, 7, 299, 7, 150] + [(37 * i + 5) % n for i in range(B - 5)]              # hub, twice 7, isolated 299
+    node = torch.tensor(nodes, dtype=torch.int64, device=dev)
     value = torch.randn(B, D, generator=torch.Generator().manual_seed(3)).to(dev)
     dense = torch.zeros(n, B, D, device=dev)
     dense.scatter_add_(0, node.view(1, B, 1).expand(1, B, D), value.unsqueeze(0))
@@ -216,10 +225,11 @@ def test_sparse_boundary_equals_dense_boundary(flags):
             assert torch.equal(got, want)
     finally:
         lib.ultra_rspmm_force_general_path(0)
-    with pytest.raises(RuntimeError):
-        UF.rspmm_forward(csr, t(relation), t(x), "add", "mul", boundary=(node, value))            # int64 nodes
-    with pytest.raises(RuntimeError):
-        UF.rspmm_forward(csr, t(relation), t(x), "add", "mul", boundary=(node.to(torch.int32), value[:, :32]))
+    if D == 64:
+        with pytest.raises(RuntimeError):
+            UF.rspmm_forward(csr, t(relation), t(x), "add", "mul", boundary=(node, value))            # int64 nodes
+        with pytest.raises(RuntimeError):
+            UF.rspmm_forward(csr, t(relation), t(x), "add", "mul", boundary=(node.to(torch.int32), value[:, :32]))
 
 
 def test_sparse_tensor_entry_and_errors():
