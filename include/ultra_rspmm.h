@@ -554,6 +554,33 @@ int ultra_set_boundary_f32(const float *member, int64_t n_query, int64_t n_node,
                            const float *query, int64_t dim, float *boundary, int32_t *count, void *stream);
 
 /*
+ * Backward of ultra_set_boundary_f32 (training through projections of fuzzy sets):
+ *   d_boundary fp32 [n_node][n_query][dim], contiguous     the gradient of the boundary
+ *   member, row_stride, floor, query                       the forward's inputs, as the forward takes them
+ *   d_member   fp32 [n_query][n_node], contiguous          EVERY entry written
+ *   d_query    fp32 [n_query][dim], or NULL to skip it
+ * With keep(q, v) exactly the forward's rule (m > 0 and (floor == NULL or m >= floor[q]); a NaN is never kept):
+ *   d_member[q][v] = keep ? sum_d d_boundary[v][q][d] * query[q][d] : +0.0
+ *   d_query[q][d]  = sum over the kept v of member[q][v] * d_boundary[v][q][d]
+ * A row that is not kept is SELECTED away, not multiplied by zero: it is never loaded, gives +0.0 bits and adds nothing to
+ * d_query whatever d_boundary or query hold there (the mirror of the forward's "whatever query holds").  The floor gets no
+ * gradient: the cut is a mask.
+ * One read pass over d_boundary in the forward's decomposition (chunks of up to 16 queries x tiles of 64 nodes); fp32 sums, the
+ * dot of a row over lanes in a fixed tree, d_query over a thread's nodes in ascending order, then over the side-by-side lane
+ * groups of a block and over the blocks in order, through `workspace` (ultra_set_boundary_backward_workspace(n_query, n_node,
+ * dim) bytes; needed, and read, only when d_query is not NULL).  No atomics and no memset: the same bits on every call.
+ * The entry only enqueues -- two launches, no allocation, no host read, capturable.  All offsets are 64-bit.
+ * ULTRA_ERR_BAD_SHAPE for n_query < 1, n_node < 1, dim < 1, row_stride < n_node, or a row wider than the lanes hold (dim > 1024
+ * when dim % 4 == 0 and query / d_boundary are 16-byte aligned, dim > 256 otherwise); ULTRA_ERR_NULL_POINTER for a NULL
+ * d_boundary / member / query / d_member, or a NULL workspace with d_query; ULTRA_ERR_WORKSPACE for a workspace smaller than
+ * the query says -- all before any launch.  Bytes moved at least: 4 * (n_node * n_query * dim + 2 * n_query * n_node).
+ */
+size_t ultra_set_boundary_backward_workspace(int64_t n_query, int64_t n_node, int64_t dim);
+int ultra_set_boundary_backward_f32(const float *d_boundary, const float *member, int64_t n_query, int64_t n_node,
+                                    int64_t row_stride, const float *floor, const float *query, int64_t dim, float *d_member,
+                                    float *d_query, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Exact (crisp) answer sets of logical queries (csrc/query_exact.hip; an addition of this package).
  * A batch of n_query entity sets over n_node entities is PACKED: bits uint64 [n_node][W], W = (n_query + 63) / 64, bit q % 64 of
  * bits[v][q / 64] = "entity v is in set q".  Intersection, union and complement are &, | and ~ of such arrays.
@@ -727,6 +754,32 @@ int ultra_linear_forward_f32(const float *input, const float *weight, const floa
  */
 int ultra_score_forward_f32(const float *hidden, const float *query, const float *w1, const float *b1, const float *w2,
                             const float *b2, float *query_bias, float *out, int64_t n_node, int64_t batch, void *stream);
+
+/*
+ * Backward of the score head over ALL entities (csrc/score_backward.hip): for
+ *     score[b, n] = w2 . relu(pre[n, b]) + b2,      pre[n, b] = W1 . cat[hidden[n, b, :], query[b, :]] + b1
+ * and grad fp32 [batch] rows of n_node at grad_stride (>= n_node):
+ *     d_pre[n, b]    = pre[n, b] > 0 ? grad[b, n] * w2 : 0      the mask of ultra_score_rows_backward_f32: `>`, so neither a
+ *                                                               zero nor a NaN pre-activation passes gradient
+ *     d_hidden[n, b] = d_pre[n, b] . W1[:, :64]                 [n_node, batch, 64], EVERY row written
+ *     d_query[b]     = sum_n d_pre[n, b] . W1[:, 64:]           [batch, 64]
+ *     d_w1 = sum_{n, b} d_pre[n, b]^T cat[hidden[n, b], query[b]]   [128, 128]      d_b1 = sum_{n, b} d_pre[n, b]   [128]
+ *     d_w2 = sum_{n, b} grad[b, n] relu(pre[n, b])   [128]                          d_b2 = sum_{n, b} grad[b, n]    [1]
+ * Each of the six outputs may be NULL: it is skipped.  Nothing of the forward is kept: the pre-activations are recomputed from
+ * hidden and query (the queries' share once per query, as the forward does), and no [n_node * batch, 128] activation is ever
+ * stored.  The products run on the exact-f32 matrix cores in fp32; sums over rows go through per-workgroup records in
+ * `workspace` (ultra_score_backward_workspace(n_node, batch) bytes on the current device), which a second launch adds in a fixed
+ * order: no atomics, no memset, the same bits on every call.  A row's d_hidden depends on that row's operands alone.
+ * The entry only enqueues -- four launches, no allocation, no host read, capturable.  All offsets are 64-bit.
+ * hidden, w1 and workspace 16-byte aligned.  ULTRA_ERR_BAD_SHAPE for n_node < 1, batch < 1, batch > 65535, grad_stride < n_node
+ * or a misaligned pointer; ULTRA_ERR_NULL_POINTER for a NULL input or workspace; ULTRA_ERR_WORKSPACE for a workspace smaller
+ * than the query says -- all before any launch.
+ */
+size_t ultra_score_backward_workspace(int64_t n_node, int64_t batch);
+int ultra_score_backward_f32(const float *hidden, const float *query, const float *w1, const float *b1, const float *w2,
+                             const float *grad, int64_t grad_stride, float *d_hidden, float *d_query, float *d_w1, float *d_b1,
+                             float *d_w2, float *d_b2, void *workspace, size_t workspace_bytes, int64_t n_node, int64_t batch,
+                             void *stream);
 
 /* The relation projections of all entity layers in one launch:
  *     out[l][r, b, :] = w2[l] . relu( w1[l] . relation[b, r, :] + b1[l] ) + b2[l]

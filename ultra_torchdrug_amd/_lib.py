@@ -118,6 +118,10 @@ SIGNATURES = {
     "ultra_topk_keys_workspace": (sz, [i64, i64, i64]),
     "ultra_topk_keys": (i32, [vp, i64, i64, i64, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, sz, vp]),
     "ultra_set_boundary_f32": (i32, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]),
+    "ultra_set_boundary_backward_workspace": (sz, [i64, i64, i64]),
+    "ultra_set_boundary_backward_f32": (i32, [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
+    "ultra_score_backward_workspace": (sz, [i64, i64]),
+    "ultra_score_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, vp]),
     "ultra_sets_project_workspace": (sz, [i64, i64]),
     "ultra_sets_project": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, sz, vp]),
     "ultra_sets_rank": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp]),

@@ -18,9 +18,11 @@ optional functions: a backend is an object with this complete interface
                                         the index tensors; every other backend keeps the mask route of ``easy_edge_mask``)
     topk_keys                          (``task.answer`` / ``engine.answer``; device tensors run ``ultra_topk_keys``, CPU tensors
                                         the dense path of the same definition)
-    set_boundary                       (reached ONLY from ``project``, on tensors the backend accepts; a backend whose
-                                        ``accepts()`` is false gets ``functional.dense_set_boundary``, the same definition in
-                                        torch ops)
+    set_boundary                       (reached ONLY from ``project`` / ``project_train``, on tensors the backend accepts; a
+                                        backend whose ``accepts()`` is false gets ``functional.dense_set_boundary``, the same
+                                        definition in torch ops.  Under grad it and ``score_all_entities`` are differentiable
+                                        -- ``ultra_set_boundary_backward_f32`` / ``ultra_score_backward_f32`` -- and are passed
+                                        through as they are: ``project_train`` needs nothing else of a backend)
 
     pna_supported, pna_statistics, pna_node_table, pna_combine_forward
                                        (reached ONLY on device tensors the backend accepts, in inference, with ``layer.PNA_NATIVE``

@@ -1,6 +1,6 @@
 // query_set.hip -- the boundary condition of a relation projection whose source is a fuzzy SET of entities instead of one
-// anchor (a translation unit of libultra_rspmm.so; C ABI: ultra_set_boundary_f32 in include/ultra_rspmm.h; DESIGN.md
-// section 16).
+// anchor, and its backward (a translation unit of libultra_rspmm.so; C ABI: ultra_set_boundary_f32 and
+// ultra_set_boundary_backward_f32 in include/ultra_rspmm.h; DESIGN.md sections 16 and 19).
 //
 //     keep(q, v)        = m > 0  and  (floor == NULL or m >= floor[q]),      m = member[q * row_stride + v]   (a NaN never)
 //     boundary[v][q][:] = m * query[q][:]   where keep(q, v),   +0.0 elsewhere -- whatever query holds
@@ -114,6 +114,164 @@ __global__ __launch_bounds__(kThreads) void set_boundary_kernel(const float *__r
     }
 }
 
+
+// ---- backward (ultra_set_boundary_backward_f32) -------------------------------------------------------------------------------
+//     d_member[q][v] = keep(q, v) ? sum_d d_boundary[v][q][d] * query[q][d] : +0.0
+//     d_query[q][d]  = sum over the kept v of member[q][v] * d_boundary[v][q][d]
+// The forward's items (a chunk of queries x `sub` tiles of 64 nodes), read instead of written: a group of L lanes (a power of
+// two up to 64, at most kBwdPieces pieces of VEC floats a lane) owns one (node, query) row of d_boundary, the groups of a block lie side by side along
+// the chunk's queries and then along nodes, so that a wave's loads cover one contiguous run of a node's chunk.  A row that is
+// not kept is never loaded.  The dot of a row is summed over the group in a fixed xor tree and leaves through LDS, so that
+// d_member is stored along v.  A thread keeps its pieces of d_query in registers over ALL items of its block (blockIdx.y is the
+// chunk: they belong to one query throughout); at the end the block adds its side-by-side groups in order and writes ONE
+// partial row set, which set_boundary_dquery_kernel adds over the blocks in order.  No atomics: the same bits on every call.
+constexpr int kBwdPieces = 4;        // pieces of VEC floats a lane holds of its row
+
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void set_boundary_backward_kernel(
+    const float *__restrict__ d_boundary, const float *__restrict__ member, long long n_query, long long n_node,
+    long long row_stride, const float *__restrict__ floor, const float *__restrict__ query, long long dim,
+    float *__restrict__ d_member, float *__restrict__ partial, int chunk, int sub, int group) {
+    __shared__ float kept[kChunk][kTile + 1];
+    __shared__ float dots[kChunk][kTile + 1];
+    __shared__ float fold[kThreads * kBwdPieces * VEC];
+    const int t = (int)threadIdx.x;
+    const int wave = t / kTile, lane = t % kTile;
+    const long long q0 = (long long)blockIdx.y * chunk;
+    const int n_q = (int)(n_query - q0 < chunk ? n_query - q0 : chunk);
+    const int n_slot = n_q * sub;                                   // <= kChunk
+    const int n_group = kThreads / group;                           // >= chunk >= n_q
+    const int side = n_group / n_q;                                 // nodes side by side
+    const int g = t / group, piece = t % group;
+    const int ql = g % n_q, vg = g / n_q;
+    const bool active = vg < side;
+    const long long row_floats = n_query * dim;
+    const int n_piece = (int)(dim / VEC);                           // pieces of a row
+    float qv[kBwdPieces][VEC], acc[kBwdPieces][VEC];
+#pragma unroll
+    for (int k = 0; k < kBwdPieces; ++k) {
+        const int pc = piece + k * group;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            acc[k][e] = 0.0f;
+            qv[k][e] = (active && pc < n_piece) ? query[(q0 + ql) * dim + (long long)pc * VEC + e] : 0.0f;
+        }
+    }
+    const long long n_tiles = (n_node + (long long)kTile * sub - 1) / ((long long)kTile * sub);
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long v0 = tile * (kTile * sub);
+        const int n_v = (int)(n_node - v0 < kTile * sub ? n_node - v0 : kTile * sub);
+        for (int slot = wave; slot < n_slot; slot += kWaves) {      // stage: the forward's rule
+            const long long q = q0 + slot % n_q;
+            const int vl = slot / n_q * kTile + lane;
+            float m = 0.0f;
+            if (vl < n_v) m = member[q * row_stride + v0 + vl];
+            bool keep = m > 0.0f;
+            if (floor != nullptr) keep = keep && m >= floor[q];
+            kept[slot][lane] = keep ? m : 0.0f;
+            dots[slot][lane] = 0.0f;
+        }
+        __syncthreads();
+        if (active) {
+            const float *src = d_boundary + v0 * row_floats + (q0 + ql) * dim;
+            for (int vl = vg; vl < n_v; vl += side) {
+                const int slot = vl / kTile * n_q + ql;
+                const float m = kept[slot][vl % kTile];
+                if (!(m > 0.0f)) continue;                          // (uniform over the group: one row, one membership)
+                const float *row = src + (long long)vl * row_floats;
+                float dot = 0.0f;
+#pragma unroll
+                for (int k = 0; k < kBwdPieces; ++k) {
+                    const int pc = piece + k * group;
+                    if (pc < n_piece) {
+                        float d[VEC];
+                        if constexpr (VEC == 4) {
+                            const float4 x = *reinterpret_cast<const float4 *>(row + (long long)pc * 4);
+                            d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
+                        } else {
+                            d[0] = row[pc];
+                        }
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            dot = dot + d[e] * qv[k][e];
+                            acc[k][e] = acc[k][e] + m * d[e];
+                        }
+                    }
+                }
+                for (int s = group >> 1; s > 0; s >>= 1) dot = dot + __shfl_xor(dot, s, 64);
+                if (piece == 0) dots[slot][vl % kTile] = dot;
+            }
+        }
+        __syncthreads();
+        for (int slot = wave; slot < n_slot; slot += kWaves) {      // d_member along v; not kept: the +0.0 staged above
+            const long long q = q0 + slot % n_q;
+            const int vl = slot / n_q * kTile + lane;
+            if (vl < n_v) d_member[q * n_node + v0 + vl] = dots[slot][lane];
+        }
+        __syncthreads();                                            // the next tile restages
+    }
+    if (partial == nullptr) return;
+    // ---- the block's d_query rows: side-by-side groups added in order
+#pragma unroll
+    for (int k = 0; k < kBwdPieces; ++k)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) fold[(k * VEC + e) * kThreads + t] = acc[k][e];
+    __syncthreads();
+    if (active && vg == 0) {
+        float *out = partial + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ((long long)chunk * dim) + (long long)ql * dim;
+#pragma unroll
+        for (int k = 0; k < kBwdPieces; ++k) {
+            const int pc = piece + k * group;
+            if (pc < n_piece) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    float total = 0.0f;
+                    for (int s = 0; s < side; ++s) total = total + fold[(k * VEC + e) * kThreads + (s * n_q + ql) * group + piece];
+                    out[(long long)pc * VEC + e] = total;
+                }
+            }
+        }
+    }
+}
+
+// d_query[q][d] = the blocks' partial rows of the query's chunk, added in block order
+__global__ __launch_bounds__(kThreads) void set_boundary_dquery_kernel(const float *__restrict__ partial, long long n_query,
+                                                                       long long dim, int chunk, int blocks,
+                                                                       float *__restrict__ d_query) {
+    const long long at = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (at >= n_query * dim) return;
+    const long long q = at / dim, d = at % dim;
+    const float *src = partial + (q / chunk) * blocks * ((long long)chunk * dim) + (q % chunk) * dim + d;
+    float total = 0.0f;
+#pragma unroll 8
+    for (int b = 0; b < blocks; ++b) total = total + src[(long long)b * chunk * dim];
+    d_query[at] = total;
+}
+
+// the decomposition both the entry and its workspace query use
+struct BwdShape {
+    int vec, group, chunk, sub, blocks;
+    long long n_chunks;
+};
+bool backward_shape(long long n_query, long long n_node, long long dim, bool aligned, BwdShape *out) {
+    BwdShape s;
+    s.vec = (dim % 4 == 0 && aligned) ? 4 : 1;
+    const long long n_piece = dim / s.vec;
+    if (n_piece > (long long)kTile * kBwdPieces) return false;
+    s.group = 1;
+    while (s.group < n_piece && s.group < kTile) s.group *= 2;               // <= 64: a group never leaves its wave
+    const int n_group = kThreads / s.group;
+    s.chunk = n_group < kChunk ? n_group : kChunk;
+    s.n_chunks = (n_query + s.chunk - 1) / s.chunk;
+    s.sub = s.n_chunks == 1 ? kChunk / (int)n_query : 1;
+    const long long n_tiles = (n_node + (long long)kTile * s.sub - 1) / ((long long)kTile * s.sub);
+    long long per_chunk = kMaxBlocks / s.n_chunks;
+    if (per_chunk < 1) per_chunk = 1;
+    s.blocks = (int)(n_tiles < per_chunk ? n_tiles : per_chunk);
+    *out = s;
+    return s.n_chunks <= 65535;
+}
+
 }  // namespace
 
 extern "C" int ultra_set_boundary_f32(const float *member, int64_t n_query, int64_t n_node, int64_t row_stride,
@@ -144,5 +302,56 @@ extern "C" int ultra_set_boundary_f32(const float *member, int64_t n_query, int6
                            (long long)n_node, (long long)row_stride, floor, query, (long long)dim, boundary, count, n_chunks,
                            n_items, sub);
     HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+// the d_query partial rows of ultra_set_boundary_backward_f32: one row set per block (the larger of the two row widths)
+extern "C" size_t ultra_set_boundary_backward_workspace(int64_t n_query, int64_t n_node, int64_t dim) {
+    if (n_query < 1 || n_node < 1 || dim < 1 || n_query > (1ll << 40) / dim) return 0;
+    size_t most = 0;
+    for (int aligned = 0; aligned < 2; ++aligned) {
+        BwdShape s;
+        if (!backward_shape(n_query, n_node, dim, aligned != 0, &s)) continue;
+        const size_t bytes = (size_t)s.n_chunks * s.blocks * s.chunk * (size_t)dim * sizeof(float);
+        most = bytes > most ? bytes : most;
+    }
+    return most;
+}
+
+extern "C" int ultra_set_boundary_backward_f32(const float *d_boundary, const float *member, int64_t n_query, int64_t n_node,
+                                               int64_t row_stride, const float *floor, const float *query, int64_t dim,
+                                               float *d_member, float *d_query, void *workspace, size_t workspace_bytes,
+                                               void *stream) {
+    if (n_query < 1 || n_node < 1 || dim < 1 || row_stride < n_node) return ULTRA_ERR_BAD_SHAPE;
+    if (d_boundary == nullptr || member == nullptr || query == nullptr || d_member == nullptr) return ULTRA_ERR_NULL_POINTER;
+    if (n_query > (1ll << 40) / dim || n_node > (1ll << 60) / (n_query * dim) || row_stride > (1ll << 60) / n_query)
+        return ULTRA_ERR_BAD_SHAPE;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(d_boundary)) & 15u) == 0;
+    BwdShape s;
+    if (!backward_shape(n_query, n_node, dim, aligned, &s)) return ULTRA_ERR_BAD_SHAPE;
+    float *partial = nullptr;
+    if (d_query != nullptr) {
+        const size_t need = (size_t)s.n_chunks * s.blocks * s.chunk * (size_t)dim * sizeof(float);
+        if (workspace == nullptr) return ULTRA_ERR_NULL_POINTER;
+        if (workspace_bytes < need) return ULTRA_ERR_WORKSPACE;
+        partial = static_cast<float *>(workspace);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)s.blocks, (unsigned)s.n_chunks);
+    if (s.vec == 4)
+        hipLaunchKernelGGL(set_boundary_backward_kernel<4>, grid, dim3(kThreads), 0, st, d_boundary, member, (long long)n_query,
+                           (long long)n_node, (long long)row_stride, floor, query, (long long)dim, d_member, partial, s.chunk,
+                           s.sub, s.group);
+    else
+        hipLaunchKernelGGL(set_boundary_backward_kernel<1>, grid, dim3(kThreads), 0, st, d_boundary, member, (long long)n_query,
+                           (long long)n_node, (long long)row_stride, floor, query, (long long)dim, d_member, partial, s.chunk,
+                           s.sub, s.group);
+    HIP_TRY(hipGetLastError());
+    if (d_query != nullptr) {
+        const long long n = n_query * dim;
+        hipLaunchKernelGGL(set_boundary_dquery_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                           partial, (long long)n_query, (long long)dim, s.chunk, s.blocks, d_query);
+        HIP_TRY(hipGetLastError());
+    }
     return ULTRA_OK;
 }

@@ -225,3 +225,25 @@ def sample_queries(graph, structure, n_query, generator=None):
         relations[q] = torch.tensor(r, dtype=torch.int64)
         targets[q] = target
     return anchors, relations, targets
+
+
+def sample_query_negatives(answers, num_negative, generator=None):
+    """``num_negative`` negatives per query for ``task.query_loss``: int64 ``(Q, K)`` uniform draws WITH replacement among the
+    entities that are ``False`` in the bool ``(Q, N)`` answer matrix ``answers`` -- such as ``task.query_answers(...,
+    graph="filter")``, so that no known answer is ever a negative -- on the device of ``answers``.  Draw
+    ``k`` of row ``q`` is the ``floor(u * n_q)``-th non-answer in ascending entity order, ``u`` uniform in ``[0, 1)`` from
+    ``generator`` (a CPU generator, or ``None`` for the global one): a function of the generator's state alone.  A row in which
+    every entity answers raises ``ValueError``."""
+    if answers.dim() != 2 or answers.dtype != torch.bool:
+        raise ValueError("sample_query_negatives: answers must be bool (Q, N), got %s %s" % (answers.dtype, tuple(answers.shape)))
+    num_negative = int(num_negative)
+    if num_negative < 1:
+        raise ValueError("sample_query_negatives: num_negative must be positive, got %d" % num_negative)
+    free = ~answers
+    n_free = free.sum(dim=1)
+    if answers.shape[0] and int(n_free.min()) == 0:
+        raise ValueError("sample_query_negatives: a query whose answers are all %d entities has no negative" % answers.shape[1])
+    u = torch.rand(answers.shape[0], num_negative, dtype=torch.float64, generator=generator).to(answers.device)
+    rank = (u * n_free.unsqueeze(-1)).floor().long().clamp(max=(n_free - 1).unsqueeze(-1))        # 0-based among the non-answers
+    # the entity at which the running count of non-answers first exceeds the rank
+    return torch.searchsorted(free.long().cumsum(dim=1), rank + 1)

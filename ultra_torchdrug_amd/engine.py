@@ -1465,11 +1465,31 @@ def train_step(task, optimizer, batch, reducer=None, communicate=True, guard=Non
     reducer's hooks paused, no gradient and no metric reduce.  ``guard``: a :class:`FiniteGuard` -- the step raises
     :class:`NonFiniteError` before ``optimizer.step()`` when its loss, a parameter or a gradient is not finite (the gradient
     all-reduce of the step has been issued and retired by then, on every rank)."""
+    return _train_step(task, optimizer, lambda: task(batch), reducer, communicate, guard)
+
+
+def train_query_step(task, optimizer, structure, anchors, relations, positives, negatives, reducer=None, communicate=True,
+                     guard=None, **cut):
+    """One training step over logical queries of ONE structure (an addition of this package):
+    :func:`train_step` with ``task.query_loss(structure, anchors, relations, positives, negatives, **cut)`` as the loss --
+    the same backward, guard, gradient reduce and optimizer step, so a :class:`FiniteGuard` and the reducers work unchanged.
+    ``cut``: ``threshold`` / ``max_sources`` of ``task.answer_query``.  Eager only (no captured form).  Returns ``(loss,
+    metrics)`` with the loss as the one metric, ``"query binary cross entropy"``."""
+
+    def compute():
+        loss = task.query_loss(structure, anchors, relations, positives, negatives, **cut)
+        return loss, {"query binary cross entropy": loss.detach()}
+
+    return _train_step(task, optimizer, compute, reducer, communicate, guard)
+
+
+def _train_step(task, optimizer, compute, reducer, communicate, guard):
+    """:func:`train_step` around ``compute() -> (loss, metric)``."""
     import contextlib
     if guard is not None:
         guard.raise_if_tripped()
         guard.scan_parameters()
-    loss, metric = task(batch)
+    loss, metric = compute()
     optimizer.zero_grad(set_to_none=True)
     with (reducer.paused() if (reducer is not None and not communicate) else contextlib.nullcontext()):
         loss.backward()

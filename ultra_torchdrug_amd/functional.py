@@ -820,20 +820,77 @@ def linear_forward(input, weight, bias, relu=False):
     return out
 
 
+def _score_all_launch(hidden, query, w1, b1, w2, b2):
+    """The one launch of :func:`score_all_entities` on contiguous fp32 device tensors."""
+    n_node, batch, _ = hidden.shape
+    out = torch.empty(batch, n_node, dtype=torch.float32, device=hidden.device)
+    query_bias = torch.empty(batch, 128, dtype=torch.float32, device=hidden.device)     # the queries' share of layer 1
+    _launch(hidden.device, "ultra_score_forward_f32", hidden, query, w1, b1, w2, b2, query_bias, out, n_node, batch)
+    return out
+
+
+def score_all_backward(hidden, query, w1, b1, w2, grad, want=(True,) * 6):
+    """``ultra_score_backward_f32``: the gradients ``(d_hidden, d_query, d_w1, d_b1, d_w2, d_b2)`` of
+    :func:`score_all_entities` for ``grad`` fp32 ``(B, N)`` (its rows may be strided), recomputing the pre-activations from
+    ``hidden`` and ``query``; ``want[i]`` false: output ``i`` is skipped and returned as ``None``.  Deterministic."""
+    n_node, batch, dim = hidden.shape
+    if dim != 64 or tuple(query.shape) != (batch, 64) or tuple(w1.shape) != (128, 128) or w2.numel() != 128 or b1.numel() != 128:
+        raise RuntimeError("score_all_backward handles the 64-d model with a 128 -> 128 -> 1 head")
+    if tuple(grad.shape) != (batch, n_node) or n_node < 1 or batch < 1:
+        raise RuntimeError("score_all_backward: grad must be (%d, %d) with both >= 1, got %s" % (batch, n_node, tuple(grad.shape)))
+    if _not_fp32_on(hidden.device, (hidden, query, w1, b1, w2, grad)):
+        raise RuntimeError("score_all_backward needs fp32 tensors on one HIP device (no CPU fallback)")
+    dev = hidden.device
+    hidden, query, w1, b1, w2 = hidden.contiguous(), query.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous()
+    if (n_node > 1 and grad.stride(1) != 1) or (batch > 1 and grad.stride(0) < n_node):
+        grad = grad.contiguous()
+    stride = grad.stride(0) if batch > 1 else n_node
+    shapes = ((n_node, batch, 64), (batch, 64), (128, 128), (128,), (128,), (1,))
+    outs = [torch.empty(shape, dtype=torch.float32, device=dev) if wanted else None for shape, wanted in zip(shapes, want)]
+    with torch.cuda.device(dev):
+        ws_bytes = int(_lib.load().ultra_score_backward_workspace(n_node, batch))
+    if ws_bytes == 0:
+        raise RuntimeError("score_all_backward: unsupported shape (N, B) = (%d, %d)" % (n_node, batch))
+    workspace = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    _launch(dev, "ultra_score_backward_f32", hidden, query, w1, b1, w2, grad, stride, *outs, workspace, ws_bytes, n_node, batch)
+    return tuple(outs)
+
+
+class _ScoreAllFunction(torch.autograd.Function):
+    """:func:`score_all_entities` under autograd: the forward is inference's launch and keeps nothing but its inputs; the
+    backward is ``ultra_score_backward_f32`` (no ``(N * B, 128)`` activation is ever stored)."""
+
+    @staticmethod
+    def forward(ctx, hidden, query, w1, b1, w2, b2):
+        ctx.w2_shape, ctx.b2_shape = tuple(w2.shape), tuple(b2.shape)
+        hidden, query, w1, b1, w2, b2 = (t.contiguous() for t in (hidden, query, w1, b1, w2, b2))
+        ctx.save_for_backward(hidden, query, w1, b1, w2)
+        return _score_all_launch(hidden, query, w1, b1, w2, b2)
+
+    @staticmethod
+    def backward(ctx, grad):
+        hidden, query, w1, b1, w2 = ctx.saved_tensors
+        outs = score_all_backward(hidden, query, w1, b1, w2, grad, ctx.needs_input_grad)
+        d_w2 = None if outs[4] is None else outs[4].view(ctx.w2_shape)
+        d_b2 = None if outs[5] is None else outs[5].view(ctx.b2_shape)
+        return outs[0], outs[1], outs[2], outs[3], d_w2, d_b2
+
+
 def score_all_entities(hidden, query, w1, b1, w2, b2):
-    """Score head over ALL entities, forward only: ``hidden`` ``(N, B, 64)``, ``query`` ``(B, 64)`` ->  ``(B, N)``
-    scores ``mlp(cat[hidden, query])`` (``ultra/model.py:134-138,177-193`` with every entity as candidate tail)."""
+    """Score head over ALL entities: ``hidden`` ``(N, B, 64)``, ``query`` ``(B, 64)`` ->  ``(B, N)``
+    scores ``mlp(cat[hidden, query])`` (``ultra/model.py:134-138,177-193`` with every entity as candidate tail).  With grad
+    enabled and an input that requires it the same launch runs as one autograd node (:class:`_ScoreAllFunction`) whose
+    backward is ``ultra_score_backward_f32``; without, nothing is recorded."""
     n_node, batch, dim = hidden.shape
     if dim != 64 or tuple(query.shape) != (batch, 64) or tuple(w1.shape) != (128, 128) or w2.numel() != 128:
         raise RuntimeError("score_all_entities handles the 64-d model with a 128 -> 128 -> 1 head")
     tensors = (hidden, query, w1, b1, w2, b2)
     if _not_fp32_on(hidden.device, tensors):
         raise RuntimeError("score_all_entities needs fp32 tensors on one HIP device (no CPU fallback)")
-    out = torch.empty(batch, n_node, dtype=torch.float32, device=hidden.device)
-    query_bias = torch.empty(batch, 128, dtype=torch.float32, device=hidden.device)     # the queries' share of layer 1
-    _launch(hidden.device, "ultra_score_forward_f32", hidden.contiguous(), query.contiguous(), w1.contiguous(), b1.contiguous(),
-            w2.contiguous(), b2.contiguous(), query_bias, out, n_node, batch)
-    return out
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return _ScoreAllFunction.apply(*tensors)
+    return _score_all_launch(hidden.contiguous(), query.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(),
+                             b2.contiguous())
 
 
 def _rows_in_place(t):
@@ -1338,13 +1395,21 @@ def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
 def dense_set_boundary(member, query, floor=None, with_count=False):
     """:func:`set_boundary` in torch ops, in the dtype of ``query`` (the host twin, and the form the fp64 ATen definition of a
     projection uses): entity ``v`` is kept for query ``q`` iff ``member[q, v] > 0`` and ``member[q, v] >= floor[q]`` (a NaN is
-    never kept); kept rows hold ``member[q, v] * query[q]``, every other row ``+0.0`` whatever ``query`` holds."""
+    never kept); kept rows hold ``member[q, v] * query[q]``, every other row ``+0.0`` whatever ``query`` holds.
+    Differentiable as it stands: ``torch.where``'s own backward hands the product ``where(keep, d_boundary, 0)``, so on FINITE
+    ``d_boundary`` and ``query`` (memberships may hold NaN) its gradients equal the definition of
+    ``ultra_set_boundary_backward_f32`` entry for entry (a zero times a finite number is the selected-away zero;
+    tests/test_query_train_cpu.py holds it to that).  Only the device entry also keeps the zeros under non-finite
+    ``d_boundary`` / ``query`` values at entries that are not kept."""
     m = member.to(query.dtype)
     keep = m > 0
     if floor is not None:
         keep = keep & (m >= floor.to(query.dtype).unsqueeze(-1))
     keep_t = keep.t().unsqueeze(-1)                                      # (N, Q, 1)
-    boundary = torch.where(keep_t, m.t().unsqueeze(-1) * query.unsqueeze(0), query.new_zeros(()))
+    # (the product is taken of the KEPT memberships: the same forward values, and in backward a NaN membership that is not kept
+    # meets its zero gradient as 0 * 0, not as 0 * NaN)
+    kept = torch.where(keep, m, m.new_zeros(()))
+    boundary = torch.where(keep_t, kept.t().unsqueeze(-1) * query.unsqueeze(0), query.new_zeros(()))
     return (boundary, keep.sum(dim=1).to(torch.int32)) if with_count else boundary
 
 
@@ -1374,6 +1439,16 @@ def set_boundary(member, query, floor=None, with_count=False):
         raise RuntimeError("set_boundary: floor must be fp32 (%d,) on %s" % (n_query, member.device))
     if not member.is_cuda:
         return dense_set_boundary(member, query, floor, with_count)
+    if torch.is_grad_enabled() and (member.requires_grad or query.requires_grad):
+        boundary, count = _SetBoundaryFunction.apply(member, query, floor, bool(with_count))
+        return (boundary, count) if with_count else boundary
+    return _set_boundary_launch(member, query, floor, with_count)
+
+
+def _set_boundary_launch(member, query, floor, with_count):
+    """The one launch of :func:`set_boundary` behind its checks."""
+    n_query, n_node = member.shape
+    dim = query.shape[1]
     query = query.contiguous()
     floor = None if floor is None else floor.contiguous()
     boundary = torch.empty(n_node, n_query, dim, dtype=torch.float32, device=member.device)
@@ -1381,6 +1456,59 @@ def set_boundary(member, query, floor=None, with_count=False):
     _launch(member.device, "ultra_set_boundary_f32", member, n_query, n_node, member.stride(0) if n_query > 1 else n_node,
             floor, query, dim, boundary, count)
     return (boundary, count) if with_count else boundary
+
+
+def set_boundary_backward(d_boundary, member, query, floor=None, want_query=True):
+    """``ultra_set_boundary_backward_f32`` (the contract is in ``include/ultra_rspmm.h``): ``(d_member (Q, N), d_query (Q, D) or
+    None)`` for the gradient ``d_boundary`` fp32 ``(N, Q, D)`` of :func:`set_boundary`'s result.  An entity that is not kept is
+    selected away: ``+0.0`` in ``d_member`` and nothing in ``d_query``, whatever ``d_boundary`` and ``query`` hold there.  The
+    rows of ``member`` may be strided, as in the forward.  Deterministic; two launches, capturable."""
+    if (member.dim() != 2 or query.dim() != 2 or d_boundary.dim() != 3
+            or _not_fp32_on(member.device, (member, query, d_boundary) + (() if floor is None else (floor,)))):
+        raise RuntimeError("set_boundary_backward needs fp32 member (Q, N), query (Q, D), d_boundary (N, Q, D) on one HIP device")
+    n_query, n_node = member.shape
+    dim = query.shape[1]
+    if n_query < 1 or n_node < 1 or dim < 1 or query.shape[0] != n_query or tuple(d_boundary.shape) != (n_node, n_query, dim):
+        raise RuntimeError("set_boundary_backward: member %s, query %s and d_boundary %s do not fit"
+                           % (tuple(member.shape), tuple(query.shape), tuple(d_boundary.shape)))
+    if (n_node > 1 and member.stride(1) != 1) or (n_query > 1 and member.stride(0) < n_node):
+        raise RuntimeError("set_boundary_backward: the rows of member must be contiguous and must not overlap")
+    if floor is not None and floor.shape != (n_query,):
+        raise RuntimeError("set_boundary_backward: floor must be fp32 (%d,)" % n_query)
+    dev = member.device
+    d_boundary, query = d_boundary.contiguous(), query.contiguous()
+    floor = None if floor is None else floor.contiguous()
+    d_member = torch.empty(n_query, n_node, dtype=torch.float32, device=dev)
+    d_query = workspace = None
+    ws_bytes = 0
+    if want_query:
+        d_query = torch.empty(n_query, dim, dtype=torch.float32, device=dev)
+        ws_bytes = int(_lib.load().ultra_set_boundary_backward_workspace(n_query, n_node, dim))
+        workspace = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dev)
+    _launch(dev, "ultra_set_boundary_backward_f32", d_boundary, member, n_query, n_node,
+            member.stride(0) if n_query > 1 else n_node, floor, query, dim, d_member, d_query, workspace, ws_bytes)
+    return d_member, d_query
+
+
+class _SetBoundaryFunction(torch.autograd.Function):
+    """:func:`set_boundary` under autograd: today's launch forward, ``ultra_set_boundary_backward_f32`` backward.  ``count`` is
+    not differentiable, ``floor`` (a cut, hence a mask) gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, member, query, floor, with_count):
+        query = query.contiguous()
+        result = _set_boundary_launch(member, query, floor, with_count)
+        boundary, count = result if with_count else (result, None)
+        ctx.save_for_backward(member, query, floor)
+        if count is not None:
+            ctx.mark_non_differentiable(count)
+        return boundary, count
+
+    @staticmethod
+    def backward(ctx, d_boundary, _d_count):
+        member, query, floor = ctx.saved_tensors
+        d_member, d_query = set_boundary_backward(d_boundary, member.detach(), query.detach(), floor, ctx.needs_input_grad[1])
+        return (d_member if ctx.needs_input_grad[0] else None), d_query, None, None
 
 
 # The divergence guard's record (``include/ultra_rspmm.h``): int32 fields ``step`` (committed steps; they are numbered from 1),

@@ -659,6 +659,20 @@ class TransferNBFNet(nn.Module):
         Inference only.  The layers run as in :meth:`bellmanford` from the dense boundary: the sparse first layer, the frontier
         and the fused layers, which rest on a one-row boundary, are not taken.  A set that holds one entity with membership
         exactly 1.0 is the boundary of :meth:`score_all_entities` for that anchor, bit for bit."""
+        return self._project(graph, rel_query_list, member, r_index, floor)
+
+    def project_train(self, graph, rel_query_list, member, r_index, floor=None):
+        """:meth:`project` under the CALLER's grad mode: the same logits ``(Q, N)`` and set sizes, with
+        gradients to ``member``, the relation representations of ``rel_query_list`` and every parameter.  ``floor`` is a cut,
+        hence a mask: it gets none.  Under grad the set boundary is ``functional.set_boundary``'s autograd node
+        (``ultra_set_boundary_backward_f32``), the layers take the route they train on from a dense boundary (the shipped
+        layers: ``sum_layer`` with dense ``add_rows``; no cut phases, no candidate tiles), and the score head is the
+        differentiable ``score_all_entities`` (``ultra_score_backward_f32``) where the fused head covers the model, the
+        ``nn.Linear`` MLP otherwise.  CPU tensors take ``dense_set_boundary`` and the MLP.  Without grad this IS
+        :meth:`project`."""
+        return self._project(graph, rel_query_list, member, r_index, floor)
+
+    def _project(self, graph, rel_query_list, member, r_index, floor):
         if not graph.num_relation:
             raise ValueError("project needs a relational graph")
         self.query = rel_query_list[0]
@@ -679,7 +693,7 @@ class TransferNBFNet(nn.Module):
             from . import functional
             boundary, count = functional.dense_set_boundary(member, query, floor, with_count=True)
         parts = self.bellmanford(graph, None, r_index, want_feature=False, boundary=boundary)
-        if self._fused_head_ok(r_index, None):
+        if self._fused_head_ok(r_index, None, allow_grad=True):
             first, second = self.mlp.layers
             score = ops.score_all_entities(parts["hidden"], parts["query"], first.weight, first.bias, second.weight, second.bias)
         else:
@@ -844,9 +858,10 @@ class TransferNBFNet(nn.Module):
         inference, every entity a candidate."""
         return self._fused_head_ok(t_index, metric) and t_index.shape[1] == graph.num_node
 
-    def _fused_head_ok(self, index, metric):
+    def _fused_head_ok(self, index, metric, allow_grad=False):
+        """``allow_grad`` (:meth:`project_train`): the differentiable ``score_all_entities`` covers the same head under grad."""
         mlp = self.mlp
-        return (backend.get().accepts(index) and not torch.is_grad_enabled() and metric is None
+        return (backend.get().accepts(index) and (allow_grad or not torch.is_grad_enabled()) and metric is None
                 and not self.symmetric and not self.concat_hidden and self.dims[0] == 64 and self.dims[-1] == 64
                 and len(mlp.layers) == 2 and mlp.layers[0].in_features == 128 and mlp.layers[0].out_features == 128
                 and mlp.layers[1].out_features == 1 and mlp.activation is torch.nn.functional.relu

@@ -664,10 +664,15 @@ class KnowledgeGraphCompletion(nn.Module):
                                  "entity %d, max relation %d" % (self.split, n, r, lo, hi_node, hi_rel))
         return tree, anchors, relations
 
-    def query_memberships(self, tree, anchors, relations, threshold=0.0, max_sources=None):
+    def query_memberships(self, tree, anchors, relations, threshold=0.0, max_sources=None, differentiable=False):
         """The memberships ``(Q, N)`` of the answer set of the parsed structure ``tree`` (:func:`parse_query_structure`) for
         checked inputs (:meth:`query_inputs`); the columns of ``anchors`` / ``relations`` are consumed depth-first, left to
-        right."""
+        right.  ``differentiable``: the same definition under the caller's grad mode, every projection
+        through ``TransferNBFNet.project_train`` (:meth:`_project_sets_train`) -- the first hop too, as the one-hot set of
+        membership 1.0, which is the boundary of ``score_all_entities`` for that anchor; the sparse first layer of the
+        single-source route is given up there."""
+        if differentiable:
+            return self._query_memberships_train(tree, anchors, relations, threshold, max_sources)
         at = {"e": 0, "r": 0}
 
         def take(kind, table):
@@ -698,6 +703,93 @@ class KnowledgeGraphCompletion(nn.Module):
             return 1 - rest
 
         return walk(tree)
+
+    def _project_sets_train(self, member, relation, threshold, max_sources):
+        """:meth:`_project_sets` under the caller's grad mode: the cut (``threshold``, the K-th largest membership for
+        ``max_sources``) is computed without grad and acts as a mask; the relation representations are computed with grad (the
+        cache is for inference), and ``TransferNBFNet.project_train`` carries gradient to ``member``, to them and to every
+        parameter.  DECISION (as in :meth:`project`): a set that is empty after the cut gives a zero row -- and zero gradient."""
+        from . import functional
+        ops = backend.get()
+        n_rel = self.fact_graph.num_relation
+        member = member.float()
+        with torch.no_grad():
+            floor = torch.full((len(member),), float(threshold), dtype=torch.float32, device=member.device)
+            if max_sources is not None:
+                zero = torch.zeros(len(member), dtype=torch.int64, device=member.device)
+                topk = ops.topk_keys if ops.accepts(member) else functional.topk_keys
+                kth = topk(member.detach().contiguous(), int(max_sources), None, zero, zero, 1)[0][:, -1]
+                floor = torch.maximum(floor, torch.where(kth > 0, kth, torch.zeros_like(kth)))
+        logits, count = self.model.project_train(self.fact_graph, self.relation_representations(relation % n_rel), member,
+                                                 relation, floor)
+        p = torch.sigmoid(logits)
+        return torch.where((count > 0).unsqueeze(-1), p, torch.zeros_like(p))
+
+    def _query_memberships_train(self, tree, anchors, relations, threshold, max_sources):
+        """:meth:`query_memberships` with ``differentiable=True``."""
+        at = {"e": 0, "r": 0}
+
+        def take(kind, table):
+            at[kind] += 1
+            return table[:, at[kind] - 1]
+
+        def run_ops(p, ops):
+            for op in ops:
+                p = self._project_sets_train(p, take("r", relations), threshold, max_sources) if op == "r" else 1 - p
+            return p
+
+        def walk(node):
+            kind = node[0]
+            if kind == "e":
+                anchor = take("e", anchors)
+                seed = torch.zeros(len(anchor), self.num_entity, dtype=torch.float32, device=anchor.device)
+                seed.scatter_(1, anchor.unsqueeze(-1), 1.0)
+                # (the first hop is never cut: one member of membership 1.0)
+                return run_ops(self._project_sets_train(seed, take("r", relations), 0.0, None), node[1][1:])
+            if kind == "ops":
+                return run_ops(walk(node[1]), node[2])
+            parts = [walk(child) for child in node[1]]
+            if kind == "i":
+                p = parts[0]
+                for other in parts[1:]:
+                    p = p * other
+                return p
+            rest = 1 - parts[0]
+            for other in parts[1:]:
+                rest = rest * (1 - other)
+            return 1 - rest
+
+        return walk(tree)
+
+    def query_loss(self, structure, anchors, relations, positives, negatives, threshold=0.0, max_sources=None):
+        """The training loss of logical queries of ONE structure (an addition of this package; after
+        ULTRAQuery's fine-tuning): with ``p`` the differentiable memberships ``(Q, N)`` (:meth:`query_memberships` with
+        ``differentiable=True``), the mean over the queries of ``0.5 * (BCE(p[q, positives[q]], 1) + mean_k BCE(p[q,
+        negatives[q, k]], 0))`` with ``F.binary_cross_entropy``'s clamp of the logarithms at -100.  ``positives`` int64 ``(Q,)``,
+        ``negatives`` int64 ``(Q, K)`` (``data.sample_query_negatives``); ``structure`` / ``anchors`` / ``relations`` /
+        ``threshold`` / ``max_sources`` as in :meth:`answer_query`.  Returns a scalar under the caller's grad mode; gradients
+        reach every parameter of the entity and relation models.  An intermediate set that is empty after its cut gives a zero
+        row, hence a constant loss term and zero gradient (the DECISION of :meth:`project`)."""
+        self._check_cut(max_sources)
+        tree, anchors, relations = self.query_inputs(structure, anchors, relations)
+        positives = torch.as_tensor(positives, device=self.device)
+        negatives = torch.as_tensor(negatives, device=self.device)
+        n_query = len(anchors)
+        if (positives.dtype != torch.int64 or negatives.dtype != torch.int64 or positives.shape != (n_query,)
+                or negatives.dim() != 2 or negatives.shape[0] != n_query or negatives.shape[1] < 1 or n_query < 1):
+            raise ValueError("query_loss: positives must be int64 (Q,) and negatives int64 (Q, K >= 1) for Q = %d >= 1 queries, "
+                             "got %s %s and %s %s" % (n_query, positives.dtype, tuple(positives.shape), negatives.dtype,
+                                                      tuple(negatives.shape)))
+        lo = int(torch.min(positives.min(), negatives.min()))
+        hi = int(torch.max(positives.max(), negatives.max()))
+        if lo < 0 or hi >= self.num_entity:
+            raise ValueError("query_loss: entities must lie in [0, %d), got [%d, %d]" % (self.num_entity, lo, hi))
+        p = self._query_memberships_train(tree, anchors, relations, threshold, max_sources)
+        p_pos = p.gather(1, positives.unsqueeze(-1)).squeeze(-1)
+        p_neg = p.gather(1, negatives)
+        pos = F.binary_cross_entropy(p_pos, torch.ones_like(p_pos), reduction="none")
+        neg = F.binary_cross_entropy(p_neg, torch.zeros_like(p_neg), reduction="none").mean(dim=1)
+        return (0.5 * (pos + neg)).mean()
 
     def _exact_graph(self, graph):
         """The graph with inverse edges that :meth:`query_answers` walks: ``"fact"`` -- :meth:`message_graph` -- or ``"filter"``
