@@ -1,5 +1,5 @@
 // combine_fused_bwd.inc -- the whole backward of the fused layer epilogue in ONE pass over the rows.
-// (included at the end of rspmm_kernels.hip, after combine_train.inc)
+// (included by epilogue.hip, after combine_train.inc)
 //
 //     out = [input +] relu( LayerNorm( Linear_{128->64}( cat[input, update] ) ) )      (ultra/layer.py:386-392, model.py:126-127)
 //

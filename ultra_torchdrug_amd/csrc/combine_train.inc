@@ -1,4 +1,4 @@
-// combine_train.inc -- backward of the fused layer epilogue (included at the end of rspmm_kernels.hip).
+// combine_train.inc -- backward of the fused layer epilogue (included by epilogue.hip, after its kernels).
 //
 // Training counterpart of combine_kernel.  The reference runs the epilogue as ATen ops
 //     output = self.linear(torch.cat([input, update], dim=-1)); layer_norm; relu        (ultra/layer.py:386-392)

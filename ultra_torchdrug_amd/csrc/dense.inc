@@ -1,5 +1,5 @@
 // dense.inc -- the small dense layers around the Bellman-Ford stacks, in a documented summation order
-// (included at the end of rspmm_kernels.hip).
+// (included by dense_layers.hip).
 //
 // The reference runs them as nn.Linear through torchdrug's MLP: the per-layer relation projection 64 -> 64 -> 64
 // (/root/reference/ultra/layer.py:228,318-319) and the score head 128 -> 128 -> 1 (ultra/model.py:53,193).  BLAS

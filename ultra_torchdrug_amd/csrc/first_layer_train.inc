@@ -1,5 +1,5 @@
 // first_layer_train.inc -- the FIRST layer of an entity Bellman-Ford in TRAINING, sparse end to end (round 5; VERDICT r4 item 5 i).
-// (included at the end of rspmm_kernels.hip)
+// (included by epilogue.hip, after combine_fused_bwd.inc)
 //
 // The first layer's input is the boundary (/root/reference/ultra/model.py:106-107,116-120): zero outside one row per query.  A row
 // (v, q) that no out-edge of the query's boundary node reaches (and v is not that node) has a zero input row and a zero update row:

@@ -1,4 +1,4 @@
-// frontier.inc -- the FIRST Bellman-Ford layer's rspmm, from the boundary in its sparse form.  (included by rspmm_kernels.hip)
+// frontier.inc -- the FIRST Bellman-Ford layer's rspmm, from the boundary in its sparse form.  (included by epilogue.hip, inside its anonymous namespace)
 //
 // The first layer of every Bellman-Ford reads `input = boundary` (ultra/model.py:116-120, ultra/rel_model.py:365-369),
 // a tensor that is zero outside ONE row per query (model.py:106-107: row h_index[b] of query block b holds query[b]).

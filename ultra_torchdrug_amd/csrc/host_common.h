@@ -1,6 +1,6 @@
 // host_common.h -- what the translation units of libultra_rspmm.so share on the host side (internal: the library is built
-// with -fvisibility=hidden, nothing here is exported).  The state behind these declarations lives in rspmm_kernels.hip;
-// dense_launch in relgraph_dense.hip.
+// with -fvisibility=hidden, nothing here is exported).  The state behind these declarations lives in runtime.hip;
+// dense_launch in relgraph_dense.hip.  Beside it: device_common.h (what kernels share) and plan_kernels.h (the plan families).
 #ifndef ULTRA_HOST_COMMON_H
 #define ULTRA_HOST_COMMON_H
 
@@ -30,6 +30,11 @@ namespace ultra_detail {
 
 // ultra_rspmm_force_general_path (process-wide)
 extern Knobs g_knobs;
+
+// one-shot profiling events (ultra_rspmm_profile_next): bracket the next plan's segment kernel, or the next frontier call,
+// on its stream; whoever takes them clears them
+extern thread_local hipEvent_t g_prof_start;
+extern thread_local hipEvent_t g_prof_stop;
 
 struct DeviceInfo {
     bool valid = false;

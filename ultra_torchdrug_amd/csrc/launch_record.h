@@ -1,7 +1,7 @@
 // launch_record.h -- which kernel a plan run actually launched, as a small per-thread record (internal to libultra_rspmm.so).
 //
 // Plain C++17: nothing from HIP, no heap, no locks, no getenv, so tests/launch_record_main.cpp compiles this header with the
-// host compiler alone.  The launchers of rspmm_kernels.hip / rotate.inc write one record per plan run AT THEIR LEAVES, from the
+// host compiler alone.  The launchers of the plan_*.hip units (plan_kernels.h) write one record per plan run AT THEIR LEAVES, from the
 // template arguments they instantiate (not from plan_path()'s decision: the mapping from decision to kernel is what the record
 // lets a test see); launch_fixup adds the fix-up kernel to the record of the run it belongs to.  A record is a row of int32;
 // a field a family does not have holds -1.  Writing one is a handful of integer stores.

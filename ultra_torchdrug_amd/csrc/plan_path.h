@@ -18,7 +18,7 @@ constexpr int kTile = 64;                  // columns per tile == wave width
 constexpr int kXcd = 8;
 constexpr int kMaxLdsBytes = 156 * 1024;   // leave a little of the 160 KiB
 constexpr int kLdsHeader = 16;             // bytes in front of the tables: the workgroup's chunk ticket counter
-constexpr int kPlanBlock = 1024;           // threads per workgroup of the chunked kernels (rspmm_kernels.hip kBlock)
+constexpr int kPlanBlock = 1024;           // threads per workgroup of the chunked kernels (plan_kernels.h kBlock)
 constexpr int kPlanRgBlock = 512;          // ... of rowgroup_kernel (rowgroup.inc kRgBlock)
 
 enum Kind { KIND_FWD = 0, KIND_DX = 1, KIND_DREL = 2 };

@@ -2,7 +2,7 @@
 //
 // Two entries of include/ultra_rspmm.h:
 //  * ultra_rspmm_pna_forward_f32: the four statistics of aggregate_func = "pna" (sum, sum of squares, max, min) from ONE walk
-//    of the forward plan.  The kernel is segment_kernel / ChunkWalker (rspmm_kernels.hip) with four accumulators per column:
+//    of the forward plan.  The kernel is segment_kernel / ChunkWalker (plan_general.hip) with four accumulators per column:
 //    one wave per chunk and 64-column tile, relation tile in LDS where it fits, the same ticket scheduling, pieces of split
 //    rows into the workspace and a fix-up pass in piece order.  Every plane is updated with exactly the operations the
 //    corresponding ultra_rspmm_forward_f32 call performs (-ffp-contract=off: no fused multiply-add), in the same order per row
@@ -14,6 +14,7 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "host_common.h"
 
 namespace {
@@ -63,16 +64,10 @@ struct PnaFixParams {
     int n_tiles;
 };
 
-// the forms of rspmm_kernels.hip (identity<>, reduce<>, binary<>), NaN behaviour included
+// min / max in the forms of device_common.h's identity<> and reduce<>, NaN behaviour included (binary<> and uniform are its own)
 constexpr float kLowest = -3.402823466e+38f, kLargest = 3.402823466e+38f;   // torchdrug's NaryMax / NaryMin start values
 __device__ __forceinline__ float red_max(float acc, float y) { return (y > acc) ? y : acc; }
 __device__ __forceinline__ float red_min(float acc, float y) { return (y < acc) ? y : acc; }
-template <int MUL>
-__device__ __forceinline__ float binary(float r, float x) {
-    if constexpr (MUL == ULTRA_MUL_MUL) return r * x;
-    else return r + x;
-}
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // acc + y with the accumulator as the instruction's FIRST operand.  Where two different NaNs meet in one addition (an input NaN
 // and the -NaN that inf - inf or inf * 0 generate) the hardware keeps the first operand's, and the compiler is free to commute
 // `acc + y`: fixup_kernel's adds came out accumulator first, this file's the other way round, and a split row whose pieces hold
@@ -296,8 +291,6 @@ __global__ __launch_bounds__(256) void pna_fixup_kernel(const PnaFixParams p) {
 // mfma(A = weight, B = feature).  Nothing of the (rows, 768) update tensor exists anywhere.  The eight partial products meet in
 // LDS (two buffers: one barrier per tile) and thread (row = t >> 4, outputs 4 (t & 15) .. + 3) adds them in wave order from the
 // bias, then LayerNorm (sums over the row's 16 lanes as an xor butterfly), relu and the shortcut.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kPcWaves = 8;
 constexpr int kPcRows = 32;

@@ -1,5 +1,5 @@
 // project_bwd.inc -- backward of the grouped relation projections (project_kernel), all layers in one launch.
-// (included by rspmm_kernels.hip, after dense.inc)
+// (included by dense_layers.hip, after dense.inc)
 //
 //     out_l[r, b, :] = W2_l . relu( W1_l . x[b, r, :] + b1_l ) + b2_l          l = 0 .. L-1      (project_kernel)
 //

@@ -1,4 +1,4 @@
-// quad_kernel: the packed forward / d_input reduction with FOUR chunks per wave.  (included by rspmm_kernels.hip)
+// quad_kernel: the packed forward / d_input reduction with FOUR chunks per wave.  (included by plan_quad.hip, inside its anonymous namespace)
 //
 // packed_kernel gives a wave one chunk and a lane one column: every edge costs the wave ~9 instructions (3 scalar
 // decode, 1 buffer_load_dword, 1 address add + 1 ds_read_b32, 1 mul, 1 add, wait/branch share) for 256 B of gather, and
@@ -26,35 +26,8 @@
 #ifndef ULTRA_QUAD_DEDUP
 #define ULTRA_QUAD_DEDUP 0
 #endif
-typedef float qf4 __attribute__((ext_vector_type(4)));
-typedef uint32_t qu4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const qf4 *lds_qf4_ptr;
-typedef __attribute__((address_space(3))) char *lds_char_ptr;
-
-// 16-byte LDS read at an integer byte address (dynamic LDS starts at 0 in these kernels: no static __shared__;
-// quad_kernel traps if that ever changes) -- keeps table bases in the instruction's immediate offset.
-__device__ __forceinline__ qf4 lds_read4(uint32_t byte_addr) { return *(lds_qf4_ptr)byte_addr; }
-
-template <int RED>
-__device__ __forceinline__ qf4 reduce4(qf4 a, qf4 y) {
-    if constexpr (RED == ULTRA_SUM_ADD) {
-        return a + y;
-    } else {
-        qf4 r;
-        r.x = reduce<RED>(a.x, y.x); r.y = reduce<RED>(a.y, y.y); r.z = reduce<RED>(a.z, y.z); r.w = reduce<RED>(a.w, y.w);
-        return r;
-    }
-}
-
-template <int RED>
-__device__ __forceinline__ qf4 identity4() {
-    const float v = identity<RED>();
-    qf4 r = {v, v, v, v};
-    return r;
-}
-
-typedef __attribute__((address_space(3))) const uint32_t *lds_u32_ptr;
-__device__ __forceinline__ uint32_t lds_read1(uint32_t byte_addr) { return *(lds_u32_ptr)byte_addr; }
+// (qf4 / qu4, lds_read4 / lds_read1, reduce4 and identity4 -- the 16-lane groups' helpers, rowgroup.inc's too -- are
+// device_common.h's.)
 
 // ACT (backward of sum-aggregation only; round 4): the caller KNOWS that most gathered gradient rows are zero for this column
 // tile, and says which are not -- 1: bitmap over the word's node (d_input: the destination whose output_grad row is gathered);

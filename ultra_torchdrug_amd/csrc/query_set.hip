@@ -36,7 +36,7 @@ constexpr int kWaves = kThreads / kTile;
 constexpr int kMaxBlocks = 2048;     // grid-stride beyond
 
 // count[q] = 0 as a kernel of this library: a memset NODE of a captured graph is not reliably ordered behind earlier kernel
-// nodes (see ultra_rspmm_frontier_f32 in rspmm_kernels.hip)
+// nodes (see ultra_rspmm_frontier_f32 in epilogue.hip)
 __global__ __launch_bounds__(kThreads) void set_count_clear_kernel(int32_t *__restrict__ count, long long n_query) {
     const long long q = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (q < n_query) count[q] = 0;

@@ -25,12 +25,13 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "host_common.h"
 
 namespace {
 
 using ultra_detail::kXcd;
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+using ultra_detail::uniform;
 using ultra_detail::DenseCall;
 using ultra_detail::KIND_FWD;
 using ultra_detail::KIND_DX;

@@ -1,5 +1,5 @@
-// rotate.inc -- rspmm with RotatE messages on the plan kernels' chunk schedule (included by rspmm_kernels.hip, inside its
-// anonymous namespace, after run_plan).
+// rotate.inc -- rspmm with RotatE messages on the plan kernels' chunk schedule (included by plan_rotate.hip, inside its
+// anonymous namespace).
 //
 // The message of an edge (u -> v, r, w) for query block b of width D = block (even; column c = b * D + d):
 //     pair (b, d), d < H = D / 2:  re = input[u, c] * rel[r, c] - input[u, c + H] * rel[r, c + H]

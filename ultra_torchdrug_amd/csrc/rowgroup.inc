@@ -1,5 +1,5 @@
 // rowgroup.inc -- rspmm straight from a CSR (row_ptr, col, rel[, w]): one destination row per 16-lane group.
-// (included by rspmm_kernels.hip)
+// (included by plan_rowgroup.hip, inside its anonymous namespace)
 //
 // Two uses:
 //  * the raw-CSR entry of the C ABI, ultra_rspmm_fwd_f32(row_ptr, src, rel, w, relation, x, out, ...) -- SURVEY.md 8b's
@@ -37,27 +37,7 @@
 // Where the rest goes (same box, 5.85 ms): without the output stores 4.69 ms, with relation rows always L1-resident
 // 5.40 ms, with the input rows L2-resident 3.04 ms; the bare gather of the same rows runs 6.2-6.6 TB/s.
 
-struct RowGroupParams {
-    const int32_t *row_ptr;     // [n_rows + 1]
-    const int32_t *col;         // [E] gathered row of every edge
-    const int32_t *rel;         // [E]
-    const float *weight;        // [E] or NULL
-    const float *relation;      // [n_rel, F]
-    const float *gather;        // [n_cols, F]
-    const float *add_rows;      // [n_rows, F] or NULL (fused epilogue, as in the plan kernels)
-    const int32_t *bnode;       // sparse boundary (see KParams) or NULL
-    const float *bvec;
-    int bdim;
-    float *out;                 // [n_rows, F]
-    long long F;
-    int n_rows;
-    int n_rel;
-    int n_rel_lds;              // relation rows held in LDS (all of them, or the first ones of a table too big for it)
-    int n_tiles;                // column tiles of 4 G columns
-    int split;                  // row parts per column tile, so that n_tiles * split is a multiple of the 8 XCD labels
-    int n_slots;
-    int blocks_per_label;
-};
+// (RowGroupParams, which run_plan and the raw-CSR entry fill, is declared in plan_kernels.h.)
 
 // BACKWARD: the d_input contribution ((grad * w) * relation) of the plan kernels instead of the forward message
 // w * (relation (*|+) x) -- same factors, but fp32 products are rounded in that order.

@@ -1,5 +1,5 @@
 // sampler.inc -- the per-step index work of training and evaluation, on the device, from SORTED KEY ARRAYS instead of
-// dense (B, N) boolean masks.  (included at the end of rspmm_kernels.hip)
+// dense (B, N) boolean masks.  (included by step_index.hip)
 //
 // The reference builds, per batch,
 //   * filter masks   mask[b, n] = not (anchor_b, r_b, n) in graph             (ultra/task.py:65-100)   (B, N) bool

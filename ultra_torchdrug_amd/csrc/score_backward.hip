@@ -25,14 +25,12 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "host_common.h"
 
 namespace {
 
 using namespace ultra_detail;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kSbWaves = 4;
 constexpr int kSbRows = 32;                     // rows of a tile

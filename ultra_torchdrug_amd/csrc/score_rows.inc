@@ -1,5 +1,5 @@
 // score_rows.inc -- the score head on the CANDIDATE rows of a training step, forward and backward.
-// (included at the end of rspmm_kernels.hip)
+// (included by epilogue.hip, last)
 //
 //     score[b, j] = w2 . relu( W1 . cat[ hidden[t[b, j], b, :], query[b, :] ] + b1 ) + b2
 //
