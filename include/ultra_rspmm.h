@@ -977,6 +977,43 @@ int ultra_topk_keys(const float *pred, int64_t n_query, int64_t n_cand, int64_t 
                     int64_t index_stride, int64_t n_rel, float *value, int64_t *index,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* Relation prediction: the known relations, the filtered rank and the K best relations of every (h, ?, t) pair
+ * (csrc/relation_select.hip; an addition of this package).
+ * Replaces: nothing the reference has -- its user loops over `predict` with one triple per candidate relation, builds dense
+ * masks and reads the host per pair.  ultra_topk_keys / ultra_filtered_rank_keys cannot express the lookup: their key base
+ * (anchor, relation) is fixed per row, here the RELATION varies along the row while both entities stay fixed.
+ * For pair p:  row = score + p * row_stride holds n_cand scores; candidate j is the relation id c_j = cand[j] (cand == NULL:
+ * c_j = j), an id in [0, 2 * n_rel) where c >= n_rel is the inverse of c - n_rel; h_p / t_p are read at [p * index_stride],
+ * target_p at [p * target_stride].  Candidate j is KNOWN iff
+ *     c_j <  n_rel  and  (h_p * n_rel + c_j) * n_node + t_p            is in keys_head   (sorted distinct keys of side 0),
+ *     c_j >= n_rel  and  (h_p * n_rel + (c_j - n_rel)) * n_node + t_p  is in keys_tail   (side 1: the triple (t, c - n_rel, h)).
+ * An id c_j outside [0, 2 * n_rel), or a pair with h_p or t_p outside [0, n_node), is never known; a NULL key array holds no
+ * key; both NULL: nothing is known (unfiltered) and h / t may be NULL.  All key arithmetic is 64-bit.
+ * Outputs, each optional (NULL: not written; all five NULL: ULTRA_ERR_NULL_POINTER):
+ *   known[p, j]    (uint8, contiguous [n_pair, n_cand]) = 1 iff candidate j is known;
+ *   n_free[p]      (int64) = #{j : candidate j not known};
+ *   rank[p]        (int64): with j* = the FIRST position with c_j == target_p,
+ *                      rank = 1 + #{j : candidate j not known and row[j*] <= row[j]}
+ *                  -- the comparison of ultra_filtered_rank_keys: pessimistic on ties, false for a NaN on either side.  A
+ *                  target that is not known counts itself.  rank = 0 when target_p is -1 or no candidate lists it, and for
+ *                  every pair when target == NULL;
+ *   top_index[p, i] (int64) / top_value[p, i] (fp32), contiguous [n_pair, k]: the candidates that are not known in the order of
+ *                  ultra_topk_keys -- score descending as floats, -0.0 == +0.0, equal scores by ascending POSITION j in the
+ *                  list (not by id), NaN after every number -- as top_index = c_j (the relation id) and top_value = row[j]
+ *                  with its exact bits; slots i >= n_free[p] hold -1 / -inf.
+ * One workgroup per pair owns all of the pair's output words; the counts are integers: every schedule gives the same result.
+ * Lists of at most L = ultra_relation_select_limit() = 4096 candidates are selected in one pass over 32 KiB of LDS; longer
+ * lists (n_cand < 2^31) take a slower multi-pass form of 3968 candidates per pass in the same launch.  1 <= k <= 128,
+ * n_rel, n_node > 0, n_node * n_rel * n_node < 2^63, row_stride >= n_cand: ULTRA_ERR_BAD_SHAPE otherwise, before any device
+ * work.  n_pair == 0: ULTRA_OK, nothing is written; n_cand == 0: every pair gets -1 / -inf, rank 0, n_free 0.
+ * Only enqueues one launch: no workspace, no allocation, no host synchronisation, capturable. */
+int ultra_relation_select_limit(void);
+int ultra_relation_select_f32(const float *score, int64_t n_pair, int64_t n_cand, int64_t row_stride, const int64_t *cand,
+                              const int64_t *keys_head, int64_t n_keys_head, const int64_t *keys_tail, int64_t n_keys_tail,
+                              const int64_t *h, const int64_t *t, int64_t index_stride, const int64_t *target,
+                              int64_t target_stride, int64_t n_rel, int64_t n_node, int64_t k, int64_t *top_index,
+                              float *top_value, int64_t *rank, int64_t *n_free, uint8_t *known, void *stream);
+
 /* Divergence guard of training steps (csrc/guard.inc): does a LIST of fp32 tensors hold a non-finite element?
  * Replaces: torch.autograd.set_detect_anomaly(True) of the reference's training run (script/run_full.py:127), which raises at the
  * step that produces a NaN.  A step replayed from a hipGraph cannot raise, so the verdict is left in a device RECORD that the

@@ -117,6 +117,9 @@ SIGNATURES = {
     "ultra_sampled_rank_keys": (i32, [vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "ultra_topk_keys_workspace": (sz, [i64, i64, i64]),
     "ultra_topk_keys": (i32, [vp, i64, i64, i64, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, sz, vp]),
+    "ultra_relation_select_limit": (i32, []),
+    "ultra_relation_select_f32": (i32, [vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp,
+                                       vp, vp]),
     "ultra_set_boundary_f32": (i32, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]),
     "ultra_set_boundary_backward_workspace": (sz, [i64, i64, i64]),
     "ultra_set_boundary_backward_f32": (i32, [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, sz, vp]),

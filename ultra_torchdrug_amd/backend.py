@@ -18,6 +18,10 @@ optional functions: a backend is an object with this complete interface
                                         the index tensors; every other backend keeps the mask route of ``easy_edge_mask``)
     topk_keys                          (``task.answer`` / ``engine.answer``; device tensors run ``ultra_topk_keys``, CPU tensors
                                         the dense path of the same definition)
+    relation_select                    (``task.answer_relation`` / ``engine.answer_relation`` / ``engine.evaluate_relations``;
+                                        device tensors run ``ultra_relation_select_f32``, CPU tensors the dense twin of the
+                                        same definition; a backend whose ``accepts()`` is false is not asked: the callers go
+                                        to ``functional.relation_select``)
     set_boundary                       (reached ONLY from ``project`` / ``project_train``, on tensors the backend accepts; a
                                         backend whose ``accepts()`` is false gets ``functional.dense_set_boundary``, the same
                                         definition in torch ops.  Under grad it and ``score_all_entities`` are differentiable

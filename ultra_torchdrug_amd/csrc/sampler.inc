@@ -13,14 +13,7 @@
 
 namespace {
 
-__device__ __forceinline__ long long lower_bound_i64(const int64_t *keys, long long n, int64_t v) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (lower_bound_i64, the binary search of every kernel below, is in select_keys.h)
 
 // rank[q] = 1 + #{c : pos <= pred[q, c]} - #{c in completions(anchor_q, rel_q) : pos <= pred[q, c]}
 // SLICED = false: one workgroup per query does all of it.  SLICED = true (rows of many candidates): this launch leaves
@@ -208,7 +201,8 @@ __global__ __launch_bounds__(64 * kSampledWaves) void sampled_rank_keys_kernel(
 
 // ---------------------------------------------------------------------------------------- top-K answers of a query
 // topk_keys_kernel: the K best candidates of a score row that do NOT complete (anchor_q, rel_q, ?), best first (the contract is in
-// include/ultra_rspmm.h).  Candidate c with score v becomes one 64-bit SORT KEY
+// include/ultra_rspmm.h).  Candidate c with score v becomes one 64-bit SORT KEY (topk_key of select_keys.h, with kTopkMax and
+// kTopkEmpty)
 //       high half: order-preserving map of v (-0.0 folded into +0.0; every NaN in one class BELOW -inf)     low half: ~c
 // so that "better" is "larger key" -- equal scores go by ascending index -- and all keys of a row are distinct.  0 is no
 // candidate's key (the NaN class is 1): it marks an empty slot.
@@ -217,10 +211,8 @@ __global__ __launch_bounds__(64 * kSampledWaves) void sampled_rank_keys_kernel(
 // threshold is looked up in the query's range of the completion keys (binary search) and, when it is none of them, appended to
 // LDS [128, 2048) through an LDS counter (one atomic per wave).  When the next tile might not fit, and at the end, best + appended
 // are sorted (bitonic, descending, over the next power of two) and cut to K.  The threshold only changes there, between barriers.
-constexpr int kTopkMax = 128;                 // K <= 128
-constexpr int kTopkLds = 2048;                // keys in LDS (16 KB): [0, 128) the best so far, [128, 2048) survivors
+constexpr int kTopkLds = 2048;               // keys in LDS (16 KB): [0, 128) the best so far, [128, 2048) survivors
 constexpr int kTopkTile = 1024;               // candidates per step of a workgroup
-constexpr unsigned long long kTopkEmpty = 0ull;
 enum { kTopkRow = 0, kTopkSlice = 1, kTopkCombine = 2 };
 
 struct TopkShared {
@@ -229,16 +221,6 @@ struct TopkShared {
     long long range[2];
     int count;
 };
-
-__device__ __forceinline__ unsigned long long topk_key(float v, long long c) {
-    unsigned u = __float_as_uint(v);
-    unsigned m = 1u;                                               // NaN: below -inf (which maps to 0x007fffff)
-    if (v == v) {
-        if (u == 0x80000000u) u = 0u;                              // -0.0 == +0.0
-        m = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((unsigned long long)m << 32) | (unsigned long long)(~(unsigned)c);
-}
 
 // every thread of the workgroup calls it (the ballot and the shuffle are wave-wide)
 __device__ __forceinline__ void topk_push(TopkShared &sh, unsigned long long key, bool pass) {

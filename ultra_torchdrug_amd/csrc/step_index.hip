@@ -8,6 +8,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "select_keys.h"
 
 namespace {
 using namespace ultra_detail;

@@ -26,6 +26,9 @@
 //       one layer of the path beam search of TransferNBFNet.visualize (CUDA and CPU keys)
 //   ultra_mi::hop_distance(row_ptr, src, w?, sources, num_iters, targets?) -> Tensor
 //       hop distances from many sources, int32 (N, B) or -- with targets (B, K) -- int32 (B, K) (CUDA and CPU keys)
+//   ultra_mi::relation_select(score, cand?, keys_head?, keys_tail?, h?, t?, target?, n_rel, n_node, k, outputs)
+//       -> (top_index, top_value, rank, n_free, known)
+//       relation prediction: known relations, filtered rank and the k best relations of every (h, t) pair (CUDA key)
 //   plan-based forms used by ultra_torchdrug_amd.functional (the plan = the bytes of one `ultra_segments` struct in a
 //   CPU uint8 tensor; the device arrays it points to are owned by the Python RelCSR object):
 //   ultra_mi::rspmm_plan_fwd(plan, relation, input, add_rows?, boundary_node?, boundary_value?, n_src, sum_op, mul_op) -> Tensor
@@ -1303,9 +1306,66 @@ Tensor hop_distance_hip(const Tensor &row_ptr, const Tensor &src, const optional
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ relation_select
+// Relation prediction (include/ultra_rspmm.h, ultra_relation_select_f32): the known candidates, the
+// filtered rank of `target` and the k best candidate relations of every (h, t) pair from a (P, C) block of scores.  Device key
+// only (CPU tensors take functional.dense_relation_select, the same definition in torch ops).  Views go to the kernel as they
+// are: score needs unit stride along its rows, h and t one common element stride.  outputs: bit 0 top_index, 1 top_value, 2 rank,
+// 3 n_free, 4 known; an output that is not asked for comes back as an empty tensor and is NULL for the kernel.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> relation_select_hip(
+        const Tensor &score, const optional<Tensor> &cand, const optional<Tensor> &keys_head, const optional<Tensor> &keys_tail,
+        const optional<Tensor> &h, const optional<Tensor> &t, const optional<Tensor> &target, int64_t n_rel, int64_t n_node,
+        int64_t k, int64_t outputs) {
+    check_dense(score, "score", at::kFloat, score);
+    TORCH_CHECK(score.dim() == 2 && (score.size(1) == 0 || score.stride(1) == 1),
+                "ultra_mi::relation_select: score must be fp32 (P, C) with contiguous rows");
+    const int64_t P = score.size(0), C = score.size(1);
+    TORCH_CHECK(P <= 1 || score.stride(0) >= C, "ultra_mi::relation_select: the rows of score overlap");
+    TORCH_CHECK((outputs & 31) != 0 && (outputs & ~(int64_t)31) == 0, "ultra_mi::relation_select: outputs must name 1 to 5 results");
+    auto given = [](const optional<Tensor> &x) { return x.has_value() && x->defined(); };
+    auto vector_of = [&](const optional<Tensor> &x, const char *name, int64_t n, bool dense) -> const int64_t * {
+        if (!given(x)) return nullptr;
+        check_dense(*x, name, at::kLong, score);
+        TORCH_CHECK(x->dim() == 1 && (n < 0 || x->numel() == n), "ultra_mi::relation_select: ", name, " has shape ", x->sizes());
+        TORCH_CHECK(!dense || x->is_contiguous(), "ultra_mi::relation_select: ", name, " must be contiguous");
+        return x->data_ptr<int64_t>();
+    };
+    const int64_t *cand_p = vector_of(cand, "cand", C, true);
+    const int64_t *kh = vector_of(keys_head, "keys_head", -1, true), *kt = vector_of(keys_tail, "keys_tail", -1, true);
+    const int64_t *h_p = vector_of(h, "h", P, false), *t_p = vector_of(t, "t", P, false);
+    const int64_t *target_p = vector_of(target, "target", P, false);
+    TORCH_CHECK((h_p == nullptr) == (t_p == nullptr), "ultra_mi::relation_select: h and t come together");
+    const int64_t index_stride = (h_p != nullptr && P > 1) ? h->stride(0) : 1;
+    TORCH_CHECK(h_p == nullptr || P <= 1 || (t->stride(0) == index_stride && index_stride >= 1),
+                "ultra_mi::relation_select: h and t must share one positive stride");
+    const int64_t target_stride = (target_p != nullptr && P > 1) ? target->stride(0) : 1;
+    TORCH_CHECK(target_stride >= 0, "ultra_mi::relation_select: target has a negative stride");
+    TORCH_CHECK(k >= 1 && k <= 128, "ultra_mi::relation_select: 1 to 128 relations per pair, got ", k);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(score.device());
+    const auto i64 = score.options().dtype(at::kLong);
+    Tensor top_index = at::empty({(outputs & 1) ? P : 0, k}, i64);
+    Tensor top_value = at::empty({(outputs & 2) ? P : 0, k}, score.options());
+    Tensor rank = at::empty({(outputs & 4) ? P : 0}, i64);
+    Tensor n_free = at::empty({(outputs & 8) ? P : 0}, i64);
+    Tensor known = at::empty({(outputs & 16) ? P : 0, C}, score.options().dtype(at::kByte));
+    if (P == 0) return {top_index, top_value, rank, n_free, known};
+    check_status(ultra_relation_select_f32(C ? score.data_ptr<float>() : nullptr, P, C, P > 1 ? score.stride(0) : C, cand_p, kh,
+                                           kh ? keys_head->numel() : 0, kt, kt ? keys_tail->numel() : 0, h_p, t_p, index_stride,
+                                           target_p, target_stride, n_rel, n_node, k,
+                                           (outputs & 1) ? top_index.data_ptr<int64_t>() : nullptr,
+                                           (outputs & 2) ? top_value.data_ptr<float>() : nullptr,
+                                           (outputs & 4) ? rank.data_ptr<int64_t>() : nullptr,
+                                           (outputs & 8) ? n_free.data_ptr<int64_t>() : nullptr,
+                                           (outputs & 16) ? known.data_ptr<uint8_t>() : nullptr, current_stream(score)),
+                 "ultra_relation_select_f32");
+    return {top_index, top_value, rank, n_free, known};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
+    m.def("relation_select(Tensor score, Tensor? cand, Tensor? keys_head, Tensor? keys_tail, Tensor? h, Tensor? t, Tensor? target, "
+          "int n_rel, int n_node, int k, int outputs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("build_relcsr(Tensor edge_list, Tensor? edge_weight, int num_node, int num_relation) -> Tensor[]");
     m.def("rspmm_fwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, int sum_op, int mul_op) -> Tensor");
     m.def("rspmm_bwd(Tensor row_ptr, Tensor src, Tensor rel, Tensor? w, Tensor relation, Tensor input, Tensor output, "
@@ -1354,6 +1414,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("beam_search_step", beam_search_step_hip);
     m.impl("beam_search_step_batch", beam_search_step_batch_hip);
     m.impl("hop_distance", hop_distance_hip);
+    m.impl("relation_select", relation_select_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)

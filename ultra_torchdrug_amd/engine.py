@@ -863,6 +863,68 @@ def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None
     return torch.cat(entities), torch.cat(scores)
 
 
+def _relation_blocks(task, h, t, cand, pair_batch, batch_size):
+    """The pairs in blocks of at most ``pair_batch``, sorted by head so that the pairs of one head share its query columns:
+    yields ``(ids, scores (len(ids), C))`` -- ``ids`` the block's positions in the input; the block is all that is kept."""
+    pair_batch = int(pair_batch)
+    if pair_batch < 1:
+        raise ValueError("relation prediction: pair_batch must be positive, got %d" % pair_batch)
+    order = torch.argsort(h, stable=True)
+    with task.relation_tables_of(cand):                  # (the relation stack runs once for the call, not once per block)
+        for i in range(0, len(h), pair_batch):
+            ids = order[i:i + pair_batch]
+            yield ids, task._relation_scores(h[ids], t[ids], cand, batch_size)
+
+
+@torch.no_grad()
+def answer_relation(task, h, t, k=10, pair_batch=1024, candidates=None, inverse=False, filtered=None, batch_size=16):
+    """``task.answer_relation`` over any number of pairs with bounded memory: the ids are range-checked once, the pairs are
+    sorted by head and served ``pair_batch`` at a time -- a ``(pair_batch, C)`` block of scores is all that is kept, and
+    ``functional.relation_select`` is enqueued on it with nothing read back per block.  Each pair's result is what
+    ``task.answer_relation`` gives for it alone (a query column does not depend on its batch mates).  Returns ``(relations int64
+    (P, k), scores fp32 (P, k))`` in input order."""
+    from .functional import TOPK_MAX
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError("answer_relation: 1 to %d relations per pair, got %d" % (TOPK_MAX, k))
+    h, t, cand = task.relation_queries(h, t, candidates, inverse)
+    keys = task.relation_filter(filtered)
+    relations = torch.full((len(h), k), -1, dtype=torch.int64, device=h.device)
+    scores = torch.full((len(h), k), -float("inf"), dtype=torch.float32, device=h.device)
+    for ids, block in _relation_blocks(task, h, t, cand, pair_batch, int(batch_size)):
+        found = task._relation_select(block, cand, keys, h[ids], t[ids], None, k, ("top_index", "top_value"))
+        relations[ids], scores[ids] = found.top_index, found.top_value
+    return relations, scores
+
+
+@torch.no_grad()
+def evaluate_relations(task, triples, candidates=None, inverse=False, batch_size=16, pair_batch=1024, filtered=None):
+    """Relation prediction as an evaluation: for every row ``(h, t, r)`` of ``triples`` the rank of ``r`` among the candidate
+    relations (``task.relation_queries``) for the pair ``(h, t)``, filtered by the context's filter graph (``filtered``, default
+    ``task.filtered_ranking``): ``rank = 1 + #{candidates that are not known and score at least as high}`` -- pessimistic on ties
+    as ``filtered_rank_keys``; a target the filter graph does not hold counts itself.  A triple whose
+    relation is not among the candidates is not ranked: it is counted in ``skipped`` and its rank is 0.  Returns a dict with
+    ``mrr``, ``mr``, ``hits@1``, ``hits@3``, ``hits@10`` over the ranked triples (``nan`` when there is none), ``skipped`` and
+    ``ranks`` int64 ``(n,)`` in input order.  Memory as :func:`answer_relation`; one host read at the end."""
+    triples = torch.as_tensor(triples, device=task.device).long()
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("evaluate_relations takes (n, 3) rows of (h, t, r), got %s" % (tuple(triples.shape),))
+    validate_triples(task, triples)
+    h, t, cand = task.relation_queries(triples[:, 0], triples[:, 1], candidates, inverse)
+    keys = task.relation_filter(filtered)
+    ranks = torch.zeros(len(triples), dtype=torch.int64, device=triples.device)
+    for ids, block in _relation_blocks(task, h, t, cand, pair_batch, int(batch_size)):
+        ranks[ids] = task._relation_select(block, cand, keys, h[ids], t[ids], triples[ids, 2], 1, ("rank",)).rank
+    ranked = ranks[ranks > 0].double()
+    result = {"skipped": int(len(ranks) - len(ranked)), "ranks": ranks}
+    none = float("nan")
+    result["mrr"] = float((1 / ranked).mean()) if len(ranked) else none
+    result["mr"] = float(ranked.mean()) if len(ranked) else none
+    for top in (1, 3, 10):
+        result["hits@%d" % top] = float((ranked <= top).double().mean()) if len(ranked) else none
+    return result
+
+
 def explain(task, triples, batch_size=16, head=False):
     """``task.explain`` over any number of triples (``(n, 3)`` rows of (h, t, r) in the current context): range-checked once
     (:func:`validate_triples`), explained ``batch_size`` at a time (the last chunk is ragged), results in input order -- a list of

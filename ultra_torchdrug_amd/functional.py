@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1352,6 +1352,22 @@ def dense_topk(pred, k, keys, anchor, rel, n_rel):
     return value, index
 
 
+def _dense_topk_groups(pred, group, k):
+    """The ordering of :func:`dense_topk` on the device of ``pred`` ``(rows, n >= 1)``, from ``group`` int64 ``(rows, n)``: 0 a
+    number, 1 a NaN, 2 left out.  Returns ``(value, index)`` of the ``k`` first positions of every row."""
+    rows, n = pred.shape
+    by_score = torch.sort(torch.nan_to_num(pred, nan=0.0, posinf=float("inf"), neginf=-float("inf")), dim=1, descending=True,
+                          stable=True).indices
+    order = by_score.gather(1, torch.sort(group.gather(1, by_score), dim=1, stable=True).indices)
+    if n < k:
+        order = torch.cat([order, torch.zeros(rows, k - n, dtype=order.dtype, device=order.device)], dim=1)
+    order = order[:, :k]
+    listed = torch.arange(k, device=pred.device)[None, :] < (group != 2).sum(dim=1, keepdim=True)
+    index = torch.where(listed, order, torch.full_like(order, -1))
+    value = torch.where(listed, pred.gather(1, order), torch.full((), -float("inf"), dtype=pred.dtype, device=pred.device))
+    return value, index
+
+
 def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
     """The ``k`` best entities of every row of ``pred`` that do not complete ``(anchor[q], rel[q], ?)``, best first
     (``ultra_topk_keys``, the contract is in ``include/ultra_rspmm.h``): scores descending as floats, ``-0.0 == +0.0``, equal
@@ -1390,6 +1406,124 @@ def topk_keys(pred, k, keys, anchor, rel, n_rel, n_node=None):
         _launch(pred.device, "ultra_topk_keys", pred, rows, n_cand, pred.stride(0) if rows > 1 else n_cand, k, keys,
                 keys.numel() if keys is not None else 0, anchor, rel, stride, int(n_rel), value, index, ws, ws_bytes)
     return value, index
+
+
+# ---------------------------------------------------------------------------------------------------- relation prediction
+RELATION_OUTPUTS = ("top_index", "top_value", "rank", "n_free", "known")      # bit i of the operator's `outputs` argument
+RelationSelection = collections.namedtuple("RelationSelection", RELATION_OUTPUTS)
+
+
+def relation_select_limit():
+    """``L``: the longest candidate list ``ultra_relation_select_f32`` selects in one pass over LDS (longer lists take its
+    multi-pass form)."""
+    return int(_lib.load().ultra_relation_select_limit())
+
+
+def dense_relation_known(cand, keys_head, keys_tail, h, t, n_rel, n_node):
+    """bool ``(P, C)``: candidate relation ``cand[j]`` in ``[0, 2 * n_rel)`` is known for the pair ``(h[p], t[p])`` (the
+    definition of ``ultra_relation_select_f32`` in torch ops, as a dense mask; ids out of range are never known)."""
+    n_rel, n_node = int(n_rel), int(n_node)
+    known = torch.zeros(len(h), len(cand), dtype=torch.bool, device=cand.device)
+    pair_ok = (h >= 0) & (h < n_node) & (t >= 0) & (t < n_node)
+    for keys, first in ((keys_head, 0), (keys_tail, n_rel)):
+        if keys is None or keys.numel() == 0:
+            continue
+        rel = cand - first
+        rel_ok = (rel >= 0) & (rel < n_rel)
+        want = (h[:, None] * n_rel + rel.clamp(0, n_rel - 1)[None, :]) * n_node + t[:, None]
+        at = torch.searchsorted(keys, want).clamp(max=keys.numel() - 1)
+        known |= (keys[at] == want) & rel_ok[None, :] & pair_ok[:, None]
+    return known
+
+
+def dense_relation_select(score, cand, keys_head, keys_tail, h, t, target, n_rel, n_node, k):
+    """:func:`relation_select` in torch ops from a dense ``(P, C)`` mask -- the twin CPU tensors take, and the definition the
+    device kernel is timed against (it runs on any device)."""
+    rows, n = score.shape
+    dev = score.device
+    ids = torch.arange(n, device=dev) if cand is None else cand
+    if keys_head is None and keys_tail is None:
+        known = torch.zeros(rows, n, dtype=torch.bool, device=dev)
+    else:
+        known = dense_relation_known(ids, keys_head, keys_tail, h, t, n_rel, n_node)
+    n_free = (~known).sum(dim=1)
+    rank = torch.zeros(rows, dtype=torch.int64, device=dev)
+    if n == 0:
+        return RelationSelection(torch.full((rows, k), -1, dtype=torch.int64, device=dev),
+                                 torch.full((rows, k), -float("inf"), dtype=score.dtype, device=dev), rank, n_free,
+                                 known.to(torch.uint8))
+    if target is not None:
+        hit = (ids[None, :] == target[:, None]) & (target >= 0)[:, None]
+        at = hit.long().argmax(dim=1)                                    # the FIRST position that lists the target
+        count = ((score.gather(1, at[:, None]) <= score) & ~known).sum(dim=1)
+        rank = torch.where(hit.any(dim=1), 1 + count, rank)
+    group = torch.where(known, torch.full_like(known, 2, dtype=torch.int64), torch.isnan(score).long())
+    value, index = _dense_topk_groups(score, group, k)
+    top_index = torch.where(index < 0, index, ids[index.clamp(min=0)])
+    return RelationSelection(top_index, value, rank, n_free, known.to(torch.uint8))
+
+
+def relation_select(score, cand, keys_head, keys_tail, h, t, target, n_rel, n_node, k, outputs=RELATION_OUTPUTS):
+    """Relation prediction over a block of scores (``ultra_relation_select_f32``; the contract is in ``include/ultra_rspmm.h``,
+    DESIGN.md section 20).  ``score`` fp32 ``(P, C)``: row ``p`` holds the scores of the candidate relations ``cand`` int64 ``(C,)``
+    (ids in ``[0, 2 * n_rel)``, ``c >= n_rel`` the inverse of ``c - n_rel``; ``None``: the identity) for the pair ``(h[p], t[p])``.
+    ``keys_head`` / ``keys_tail``: the filter graph's ``completion_keys(0)`` / ``completion_keys(1)`` (both ``None``: unfiltered,
+    nothing is known); ``target`` int64 ``(P,)`` relation ids or ``None``.  Returns a :class:`RelationSelection`:
+    ``top_index`` int64 / ``top_value`` fp32 ``(P, k)`` the best relations that are not known in the order of :func:`topk_keys`
+    (equal scores by ascending position in ``cand``), ending in ``-1`` / ``-inf``; ``rank`` int64 ``(P,)`` the filtered rank of
+    ``target`` (0: not a candidate); ``n_free`` int64 ``(P,)``; ``known`` uint8 ``(P, C)``.  ``outputs`` names the results to
+    compute, the others are ``None``.  Strided views of ``score`` (unit stride along a row), ``h`` / ``t`` (one common stride) and
+    ``target`` go to the kernel as they are; one launch, no workspace, no host synchronisation.  CPU tensors take
+    :func:`dense_relation_select`."""
+    if score.dim() != 2 or score.dtype != torch.float32 or (score.shape[1] and score.stride(1) != 1):
+        raise RuntimeError("relation_select: score must be fp32 (P, C) with contiguous rows")
+    rows, n_cand = score.shape
+    dev = score.device
+    k, n_rel, n_node = int(k), int(n_rel), int(n_node)
+    if not 1 <= k <= TOPK_MAX:
+        raise RuntimeError("relation_select: 1 to %d relations per pair, got %d" % (TOPK_MAX, k))
+    if n_rel <= 0 or n_node <= 0 or float(n_node) ** 2 * n_rel >= 2.0 ** 63:
+        raise RuntimeError("relation_select: n_rel and n_node must be positive with 64-bit keys, got %d and %d" % (n_rel, n_node))
+    if rows > 1 and score.stride(0) < n_cand:
+        raise RuntimeError("relation_select: the rows of score overlap")
+    outputs = tuple(outputs)
+    if not outputs or any(name not in RELATION_OUTPUTS for name in outputs):
+        raise RuntimeError("relation_select: outputs must name some of %s, got %s" % (RELATION_OUTPUTS, outputs))
+    if cand is not None and (cand.dtype != torch.int64 or cand.shape != (n_cand,) or cand.device != dev or not cand.is_contiguous()):
+        raise RuntimeError("relation_select: cand must be a contiguous int64 (%d,) on %s" % (n_cand, dev))
+    for name, keys in (("keys_head", keys_head), ("keys_tail", keys_tail)):
+        if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous() or keys.device != dev):
+            raise RuntimeError("relation_select: %s must be a contiguous int64 vector on %s" % (name, dev))
+    filtered = keys_head is not None or keys_tail is not None
+    if filtered and (h is None or t is None):
+        raise RuntimeError("relation_select: a filtered selection needs h and t")
+    stride = 1
+    if h is not None or t is not None:
+        if h is None or t is None:
+            raise RuntimeError("relation_select: h and t come together")
+        h, t, stride = _index_pair("relation_select", h, t, rows, dev)
+    if target is not None and (target.dtype != torch.int64 or target.shape != (rows,) or target.device != dev):
+        raise RuntimeError("relation_select: target must be int64 (%d,) on %s" % (rows, dev))
+    if target is not None and rows > 1 and target.stride(0) < 0:
+        target = target.contiguous()
+    if not score.is_cuda:
+        full = dense_relation_select(score, cand, keys_head, keys_tail, h, t, target, n_rel, n_node, k)
+        return RelationSelection(*[value if name in outputs else None for name, value in zip(RELATION_OUTPUTS, full)])
+    if _torch_ext.binding() == "torch":
+        bits = sum(1 << RELATION_OUTPUTS.index(name) for name in set(outputs))
+        full = _torch_ext.load().relation_select(score, cand, keys_head, keys_tail, h, t, target, n_rel, n_node, k, bits)
+        return RelationSelection(*[value if name in outputs else None for name, value in zip(RELATION_OUTPUTS, full)])
+    shapes = {"top_index": ((rows, k), torch.int64), "top_value": ((rows, k), torch.float32), "rank": ((rows,), torch.int64),
+              "n_free": ((rows,), torch.int64), "known": ((rows, n_cand), torch.uint8)}
+    out = {name: torch.empty(shape, dtype=dtype, device=dev) if name in outputs else None
+           for name, (shape, dtype) in shapes.items()}
+    if rows:
+        _launch(dev, "ultra_relation_select_f32", score if n_cand else None, rows, n_cand, score.stride(0) if rows > 1 else n_cand,
+                cand, keys_head, keys_head.numel() if keys_head is not None else 0, keys_tail,
+                keys_tail.numel() if keys_tail is not None else 0, h, t, stride, target,
+                target.stride(0) if (target is not None and rows > 1) else 1, n_rel, n_node, k,
+                *[out[name] for name in RELATION_OUTPUTS])
+    return RelationSelection(**out)
 
 
 def dense_set_boundary(member, query, floor=None, with_count=False):

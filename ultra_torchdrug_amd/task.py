@@ -14,6 +14,7 @@ checkpoint holds after ``util.clean_save`` (``ultra/util.py:278-325``); scores a
 only the int64 ranks leave it (the reference moves ``(B, 2, N)`` scores and masks to the host per batch,
 ``task.py:263,295``).
 """
+import contextlib
 import math
 
 import torch
@@ -579,6 +580,136 @@ class KnowledgeGraphCompletion(nn.Module):
         if with_hops:
             return index, value, self.answer_hops(anchor, index)
         return index, value
+
+    # ------------------------------------------------------------------ relation prediction
+    def relation_queries(self, h, t, candidates=None, inverse=False):
+        """The range-checked inputs of :meth:`relation_scores`: ``(h, t, cand)``, int64 ``(P,)``, ``(P,)`` and ``(C,)`` on the task's
+        device (one host read per call, as :meth:`answer_queries`).  ``candidates=None``: ``[0, R)``, with ``inverse`` ``[0, 2R)``;
+        otherwise a list of ids in ``[0, 2R)`` (``c >= R``: the inverse of ``c - R``) and ``inverse`` says nothing."""
+        h = torch.as_tensor(h, device=self.device).reshape(-1)
+        t = torch.as_tensor(t, device=self.device).reshape(-1)
+        if h.dtype != torch.int64 or t.dtype != torch.int64 or h.shape != t.shape:
+            raise ValueError("relation prediction: h and t must be int64 (P,), got %s %s and %s %s"
+                             % (h.dtype, tuple(h.shape), t.dtype, tuple(t.shape)))
+        n, r = self.num_entity, self.num_relation
+        if candidates is None:
+            cand = torch.arange(2 * r if inverse else r, device=self.device)
+        else:
+            if not isinstance(candidates, torch.Tensor) and len(candidates) == 0:
+                candidates = torch.zeros(0, dtype=torch.int64)           # (an empty list has no dtype of its own)
+            cand = torch.as_tensor(candidates, device=self.device).reshape(-1)
+            if cand.dtype != torch.int64:
+                raise ValueError("relation prediction: candidates must be int64 (C,), got %s" % cand.dtype)
+        lo = [x.min() for x in (h, t, cand) if len(x)]
+        if lo:
+            lo = int(torch.stack(lo).min())
+            hi_node = int(torch.max(h.max(), t.max())) if len(h) else -1
+            hi_rel = int(cand.max()) if len(cand) else -1
+            if lo < 0 or hi_node >= n or hi_rel >= 2 * r:
+                raise ValueError("pairs or candidates out of range for context `%s` (%d entities, relations in [0, %d)): min id "
+                                 "%d, max entity %d, max relation %d" % (self.split, n, 2 * r, lo, hi_node, hi_rel))
+        return h, t, cand
+
+    def relation_filter(self, filtered=None):
+        """``(keys_head, keys_tail, n_rel, n_node)`` of the filter of :meth:`answer_relation`: both sorted completion key arrays
+        of the current context's filter graph, or ``None`` twice when the ranking is not filtered."""
+        graph = self.graph
+        if filtered is None:
+            filtered = self.filtered_ranking
+        if filtered and graph.num_relation != self.num_relation:
+            # (candidate c >= R is looked up as relation c - R: both graphs must count relations alike)
+            raise ValueError("context `%s`: the filter graph has %d relations, the fact graph %d"
+                             % (self.split, graph.num_relation, self.num_relation))
+        keys = (graph.completion_keys(0), graph.completion_keys(1)) if filtered else (None, None)
+        return keys + (max(self.num_relation, 1), graph.num_node)
+
+    @contextlib.contextmanager
+    def relation_tables_of(self, cand):
+        """Around the query columns of one relation-prediction call, in evaluation mode without gradient: when the context has
+        no relation cache, the relation representations of the candidates' base relations are computed here ONCE, each relation
+        ALONE -- the call ``predict`` makes for a single triple, so a score keeps the bits of its definition on every model
+        (a relation stack that runs through the BLAS library gives a relation other bits next to batch mates) -- and serve as
+        the cache for the duration.  A context that has a cache keeps it: the scores are then those of ``predict`` with that
+        cache.  One pass of the relation stack per distinct base relation; ``cache_relation_representations()`` ahead of many
+        calls saves them."""
+        own = (not self.training and not torch.is_grad_enabled() and self.split not in self._relation_cache and len(cand) > 0)
+        if own:
+            n_rel = self.fact_graph.num_relation
+            tables = None
+            for base in torch.unique(cand % n_rel).tolist():
+                rows = self.relation_representations(torch.tensor([base], device=cand.device))
+                if tables is None:
+                    tables = [torch.zeros((n_rel,) + tuple(row.shape[1:]), dtype=row.dtype, device=row.device) for row in rows]
+                for table, row in zip(tables, rows):
+                    table[base] = row[0]
+            self._relation_cache[self.split] = tables
+        try:
+            yield
+        finally:
+            if own:
+                self._relation_cache.pop(self.split, None)
+
+    def _relation_scores(self, h, t, cand, batch_size):
+        """:meth:`relation_scores` behind its argument checks, inside :meth:`relation_tables_of`."""
+        n_pair, n_cand = len(h), len(cand)
+        out = torch.empty(n_pair, n_cand, dtype=torch.float32, device=h.device)
+        if n_pair == 0 or n_cand == 0:
+            return out
+        heads, of_pair = torch.unique(h, return_inverse=True)
+        order = torch.argsort(of_pair, stable=True)                      # the pairs grouped by their head
+        bounds = [0] + torch.bincount(of_pair, minlength=len(heads)).cumsum(0).tolist()
+        # column head_i * C + j asks (heads[head_i], cand[j], ?); the columns of different heads fill the same batches
+        col_anchor, col_rel = heads.repeat_interleave(n_cand), cand.repeat(len(heads))
+        for c0 in range(0, len(col_anchor), batch_size):
+            c1 = min(c0 + batch_size, len(col_anchor))
+            pred = self._first_hop(col_anchor[c0:c1], col_rel[c0:c1])                    # (c1 - c0, N)
+            for i in range(c0 // n_cand, (c1 - 1) // n_cand + 1):                        # the heads this batch has columns of
+                a, b = max(c0, i * n_cand), min(c1, (i + 1) * n_cand)
+                pairs = order[bounds[i]:bounds[i + 1]]
+                out[pairs, a - i * n_cand:b - i * n_cand] = pred[a - c0:b - c0][:, t[pairs]].t()
+        return out
+
+    @torch.no_grad()
+    def relation_scores(self, h, t, candidates=None, inverse=False, batch_size=16):
+        """Scores of candidate relations between the entities of ``P`` pairs (an addition of this package: the third question of
+        link prediction, ``(h, ?, t)``): ``(scores fp32 (P, C), cand int64 (C,))`` with ``scores[p, j]`` = the logit of entity
+        ``t[p]`` in the query column ``(h[p], cand[j], ?)`` -- ``predict([[h, t, c]])[0, 0, t]`` for ``c < R`` and
+        ``predict([[t, h, c - R]])[0, 1, t]`` for the inverse ids ``c >= R``, the same bits.  Candidates: :meth:`relation_queries`.
+        The pairs are grouped by their head: every distinct ``(head, candidate)`` is ONE Bellman-Ford column (:meth:`_first_hop`),
+        read at all the tails of that head, and the columns of different heads fill the same batches of ``batch_size`` -- ``#heads
+        * C`` columns, not ``P * C``.  (A model without the fused all-entity score head scores a column through ``predict``, which
+        computes the triple's other side too.)  The relation cache (:meth:`cache_relation_representations`) is honoured; without
+        one the relation stack runs once per distinct base relation of the call (:meth:`relation_tables_of`)."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("relation_scores: batch_size must be positive, got %d" % batch_size)
+        h, t, cand = self.relation_queries(h, t, candidates, inverse)
+        with self.relation_tables_of(cand):
+            return self._relation_scores(h, t, cand, batch_size), cand
+
+    @staticmethod
+    def _relation_select(score, cand, keys, h, t, target, k, outputs):
+        from . import functional
+        ops = backend.get()
+        select = ops.relation_select if ops.accepts(score) else functional.relation_select
+        return select(score, cand, keys[0], keys[1], h, t, target, keys[2], keys[3], k, outputs=outputs)
+
+    @torch.no_grad()
+    def answer_relation(self, h, t, k=10, candidates=None, inverse=False, filtered=None, batch_size=16):
+        """Which relations hold between ``h`` and ``t``, best first: ``(relations int64 (P, k), scores fp32 (P, k))`` of the
+        candidates (:meth:`relation_queries`) that are not known -- ``c`` is known for ``(h, t)`` when the filter graph holds
+        ``(h, c, t)``, or ``(t, c - R, h)`` for an inverse id ``c >= R`` (``filtered``, default ``self.filtered_ranking``) -- in the
+        order ``functional.relation_select`` defines: score descending, equal scores by ascending position in the candidate list,
+        NaN last; a pair with fewer than ``k`` such candidates ends in ``-1`` / ``-inf``.  Scores: :meth:`relation_scores`."""
+        k = int(k)
+        if not 1 <= k <= TOPK_MAX:
+            raise ValueError("answer_relation: 1 to %d relations per pair, got %d" % (TOPK_MAX, k))
+        h, t, cand = self.relation_queries(h, t, candidates, inverse)
+        keys = self.relation_filter(filtered)
+        with self.relation_tables_of(cand):
+            score = self._relation_scores(h, t, cand, int(batch_size))
+        found =self._relation_select(score, cand, keys, h, t, None, k, ("top_index", "top_value"))
+        return found.top_index, found.top_value
 
     # ------------------------------------------------------------------ logical queries (DESIGN.md section 16)
     def _first_hop(self, anchor, relation):
