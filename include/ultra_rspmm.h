@@ -169,7 +169,14 @@ int ultra_rspmm_force_general_path(int on);
 /* Process-wide: size every persistent grid for `n` compute units fewer than the device has (default 0).  The plan kernels run
  * one workgroup per compute unit for the life of a launch; a collective overlapped with them on a side stream (RCCL's kernels
  * during the phased training step) then finds no free compute unit until workgroups retire.  Affects launches (and hipGraph
- * captures) made AFTER the call; results never depend on it. */
+ * captures) made AFTER the call.  Floor: grids are never sized for fewer than 8 compute units (one workgroup per XCD label),
+ * however large `n` is; n < 0 is ULTRA_ERR_BAD_SHAPE.  Everything computed per row never depends on it, bit for bit; sums
+ * over rows that go through per-workgroup partials (the parameter gradients of the backward entries) are associated by the
+ * number of partials and agree within rounding.  The size queries (ultra_combine_backward_waves,
+ * ultra_combine_backward_fused_waves, ultra_relation_project_backward_blocks, ultra_score_backward_workspace,
+ * ultra_first_layer_epilogue_backward_workspace) read the same setting as the launches: a caller
+ * changes it between calls, never between a size query and the launch the buffer is for (ultra_combine_backward_f32 takes
+ * no buffer size and would write the partials of the new count into a buffer sized for the old one). */
 int ultra_rspmm_reserve_cus(int n);
 
 /* Scratch bytes a call over `seg` with row width F needs (piece partial sums). */

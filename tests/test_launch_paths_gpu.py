@@ -218,7 +218,23 @@ def _hub_graph():
     return EG._memo[key]
 
 
+def _removed_csr():
+    """The unit-weight graph of EG._removed_case with the step's triples removed (``with_removed_edges``: marked words)."""
+    from ultra_torchdrug_amd import RelCSR
+    key = ("lp_removed_csr",)
+    if key not in EG._memo:
+        dst, src, rel, w, (h, t, q), *_ = EG._removed_case()
+        base = RelCSR(EG._t(dst), EG._t(src), EG._t(rel), None, 300, 300, 6)
+        assert base.unit_weight
+        cut = base.with_removed_edges(EG._t(h), EG._t(t), EG._t(q), 3)
+        assert np.array_equal(cut.weight.cpu().numpy(), w)
+        EG._memo[key] = cut
+    return EG._memo[key]
+
+
 def _csr(row):
+    if row["graph"] == "removed":
+        return _removed_csr()
     if row["graph"] == "lp_hub":
         _hub_graph()
     return EG._csr(row["graph"], **row.get("opts", {}))
@@ -695,6 +711,7 @@ def _run_call(row, call, csr, n_cu):
     assert len(got) == len(outputs)
     for tensor, (what, value) in zip(got, outputs):
         assert EG._same(tensor, value), (label, what)
+    return got, records         # (tests/test_cu_count_gpu.py compares both across compute-unit counts)
 
 
 @pytest.mark.parametrize("row", ROWS, ids=[row["id"] for row in ROWS])
@@ -702,19 +719,7 @@ def test_launch_path(row):
     """Every call of the row launches the kernel the table names and computes the definition (module docstring)."""
     from ultra_torchdrug_amd import _lib
     lib = _lib.load()
-    if row["graph"] == "removed":
-        from ultra_torchdrug_amd import RelCSR
-        key = ("lp_removed_csr",)
-        if key not in EG._memo:
-            dst, src, rel, w, (h, t, q), *_ = EG._removed_case()
-            base = RelCSR(EG._t(dst), EG._t(src), EG._t(rel), None, 300, 300, 6)
-            assert base.unit_weight
-            cut = base.with_removed_edges(EG._t(h), EG._t(t), EG._t(q), 3)
-            assert np.array_equal(cut.weight.cpu().numpy(), w)
-            EG._memo[key] = cut
-        csr = EG._memo[key]
-    else:
-        csr = _csr(row)
+    csr = _csr(row)
     _check_shape(row, csr)
     with EG._knob(row["knob"]):
         try:

@@ -7,7 +7,9 @@ launch_quad_w and the packed / general launchers of that commit, rule by rule --
 
 Numbers used below: a 64-column relation tile is 256 B per relation, kMaxLdsBytes = 159 744 B = 624 such rows, every
 launch has a 16-byte LDS header; n_cu = 256 gives 32 workgroups per XCD label (grid 256), n_cu = 248 (after
-ultra_rspmm_reserve_cus(8)) gives 31, which no power of two divides: concurrent tiles stay at 1 there.
+ultra_rspmm_reserve_cus(8)) gives 31, which no power of two divides: concurrent tiles stay at 1 there.  The `*_cus` rows at the
+end hold the geometry at 8, 24 and 240 compute units (the floor, an odd count per label, bench.py's reserved legs), which
+tests/test_cu_count_gpu.py runs on the device.
 """
 import os
 import shutil
@@ -179,6 +181,31 @@ CASES = [
     case("fixup_grid", SPLIT, dict(F=1024, n_long_rows=3, n_pieces=30), fixup=1, fixup_grid=12),
     case("fixup_general", SPLIT, dict(knobs=1), family=GENERAL, fixup=2),
 ]
+
+
+# ---- the compute-unit count: the minimum (8), an odd number of workgroups per label (24) and what bench.py leaves its
+# multi-GPU legs (240 = 256 - 16).  blocks_per_label = ceil(n_cu / 8) = 1, 3, 30; grid = 8 * that.  `concurrent`, by hand from
+# the loop "c -> 2c while 2c <= slots_per_label and bpl % 2c == 0 and bpl / 2c >= 4" (slots_per_label = ceil(n_slots / 8)):
+#   bpl = 1:  1 % 2 != 0                                                   -> 1 at every F
+#   bpl = 3:  3 % 2 != 0                                                   -> 1 at every F
+#   bpl = 30: F = 64:   1 tile x split 8 = 8 slots, 1 per label: 2 > 1     -> 1
+#             F = 1024: 16 tiles x split 1, 2 per label: 2 <= 2, 30 % 2 == 0, 15 >= 4 -> 2; then 4 > 2 -> 2
+#             F = 4096: 64 tiles, 8 per label: 2 as above; then 30 % 4 = 2 -> 2
+CU_GEO = {8: (1, 8), 24: (3, 24), 240: (30, 240)}
+QUAD_TILES = {64: (1, 8, 8), 1024: (16, 1, 16), 4096: (64, 1, 64)}          # F -> n_tiles, split, n_slots
+QUAD_CONC = {(8, 64): 1, (8, 1024): 1, (8, 4096): 1, (24, 64): 1, (24, 1024): 1, (24, 4096): 1,
+             (240, 64): 1, (240, 1024): 2, (240, 4096): 2}
+for _n_cu, (_bpl, _grid) in CU_GEO.items():
+    _geo = dict(blocks_per_label=_bpl, grid=_grid)
+    for _F, (_tiles, _split, _slots) in QUAD_TILES.items():
+        CASES.append(case("quad_F%d_%d_cus" % (_F, _n_cu), dict(F=_F, n_cu=_n_cu), status=0, family=QUAD, n_tiles=_tiles,
+                          split=_split, n_slots=_slots, concurrent=QUAD_CONC[_n_cu, _F], **_geo))
+    CASES.append(case("rowgroup_%d_cus" % _n_cu, WIDE, dict(n_cu=_n_cu), status=0, family=ROWGROUP, group=16, n_tiles=1, split=8,
+                      n_slots=8, **_geo))
+    CASES.append(case("packed_F66_%d_cus" % _n_cu, dict(F=66, n_cu=_n_cu), status=0, family=PACKED, n_tiles=2, split=4, n_slots=8,
+                      **_geo))
+    CASES.append(case("general_%d_cus" % _n_cu, dict(knobs=1, n_cu=_n_cu), status=0, family=GENERAL, n_tiles=1, split=8, n_slots=8,
+                      **_geo))
 
 
 @pytest.fixture(scope="module")
