@@ -230,29 +230,42 @@ int ultra_score_rows_backward_f32(const float *hidden, const float *query, const
                                   float *d_hidden, float *d_query, float *d_w1, float *d_b1, float *d_w2, float *d_b2,
                                   int64_t n_node, int64_t n_batch, int64_t per_row, void *stream) {
     if (n_node < 0 || n_batch < 0 || per_row < 0 || n_batch * per_row > 0x7fffffffLL || per_row > 160) return ULTRA_ERR_BAD_SHAPE;
-    // (`hidden` is not read by the backward -- its candidate rows are in in_rows -- and may be NULL)
-    if (query == nullptr || t_index == nullptr || w1 == nullptr || w2 == nullptr || h == nullptr ||
-        in_rows == nullptr || partial == nullptr || grad == nullptr || d_pre == nullptr || d_hidden == nullptr || d_query == nullptr || d_w1 == nullptr || d_b1 == nullptr ||
-        d_w2 == nullptr || d_b2 == nullptr)
-        return ULTRA_ERR_NULL_POINTER;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long n4 = n_node * n_batch * 16;
-    if (n4 > 0) {
+    const auto fill_d_hidden = [&]() -> int {
         const unsigned fb = (unsigned)((n4 + 256 * 8 - 1) / (256 * 8) < 4096 ? (n4 + 256 * 8 - 1) / (256 * 8) : 4096);
         hipLaunchKernelGGL(zero_fill_kernel, dim3(fb ? fb : 1), dim3(256), 0, s, reinterpret_cast<qf4 *>(d_hidden), n4);
         HIP_TRY(hipGetLastError());
-    }
-    ScoreRowsParams p{};
-    p.hidden = hidden; p.query = query; p.t_index = reinterpret_cast<const long long *>(t_index); p.w1 = w1; p.w2 = w2;
-    p.h = const_cast<float *>(h); p.in_rows = const_cast<float *>(in_rows); p.partial = partial; p.grad = grad; p.d_pre = d_pre; p.d_hidden = d_hidden; p.d_query = d_query; p.d_w1 = d_w1;
-    p.d_b1 = d_b1; p.d_w2 = d_w2; p.d_b2 = d_b2; p.n_batch = (int)n_batch; p.per_row = (int)per_row;
-    if (n_batch * per_row == 0) {       // no rows: zero parameter gradients
+        return ULTRA_OK;
+    };
+    if (n_batch * per_row == 0) {       // no rows: EVERY gradient is zero, d_query's too (the row operands are empty and may be NULL)
+        if (d_w1 == nullptr || d_b1 == nullptr || d_w2 == nullptr || d_b2 == nullptr || (n4 > 0 && d_hidden == nullptr) ||
+            (n_batch > 0 && d_query == nullptr))
+            return ULTRA_ERR_NULL_POINTER;
+        if (n4 > 0) {
+            const int rc = fill_d_hidden();
+            if (rc) return rc;
+        }
+        if (n_batch > 0) HIP_TRY(hipMemsetAsync(d_query, 0, (size_t)n_batch * 64 * sizeof(float), s));
         HIP_TRY(hipMemsetAsync(d_w1, 0, 128 * 128 * sizeof(float), s));
         HIP_TRY(hipMemsetAsync(d_b1, 0, 128 * sizeof(float), s));
         HIP_TRY(hipMemsetAsync(d_w2, 0, 128 * sizeof(float), s));
         HIP_TRY(hipMemsetAsync(d_b2, 0, sizeof(float), s));
         return ULTRA_OK;
     }
+    // (`hidden` is not read by the backward -- its candidate rows are in in_rows -- and may be NULL)
+    if (query == nullptr || t_index == nullptr || w1 == nullptr || w2 == nullptr || h == nullptr ||
+        in_rows == nullptr || partial == nullptr || grad == nullptr || d_pre == nullptr || d_hidden == nullptr || d_query == nullptr || d_w1 == nullptr || d_b1 == nullptr ||
+        d_w2 == nullptr || d_b2 == nullptr)
+        return ULTRA_ERR_NULL_POINTER;
+    if (n4 > 0) {
+        const int rc = fill_d_hidden();
+        if (rc) return rc;
+    }
+    ScoreRowsParams p{};
+    p.hidden = hidden; p.query = query; p.t_index = reinterpret_cast<const long long *>(t_index); p.w1 = w1; p.w2 = w2;
+    p.h = const_cast<float *>(h); p.in_rows = const_cast<float *>(in_rows); p.partial = partial; p.grad = grad; p.d_pre = d_pre; p.d_hidden = d_hidden; p.d_query = d_query; p.d_w1 = d_w1;
+    p.d_b1 = d_b1; p.d_w2 = d_w2; p.d_b2 = d_b2; p.n_batch = (int)n_batch; p.per_row = (int)per_row;
     const size_t lds = (size_t)(128 * 128 + 16 * 128 + 2 * per_row * 64 + 2 * per_row) * sizeof(float);
     if (lds > (size_t)kMaxLdsBytes) return ULTRA_ERR_BAD_SHAPE;
     int rc = ensure_lds_attribute(reinterpret_cast<const void *>(score_rows_backward_kernel), lds);
