@@ -1022,6 +1022,49 @@ int ultra_relation_select_f32(const float *score, int64_t n_pair, int64_t n_cand
                               int64_t target_stride, int64_t n_rel, int64_t n_node, int64_t k, int64_t *top_index,
                               float *top_value, int64_t *rank, int64_t *n_free, uint8_t *known, void *stream);
 
+/* Candidate sets: the rank, the counts and the K best entities of every query among a LIST of admissible entities
+ * (csrc/candidate_select.hip; an addition of this package).
+ * Replaces: nothing the reference has -- its user builds a (Q, N) boolean mask of the admissible entities, copies the masked
+ * scores and calls torch.topk.  ultra_topk_keys / ultra_filtered_rank_keys walk every entity [0, n_node); ultra_sets_rank takes a
+ * dense exclusion matrix and has no top-K.  Here the admissible entities of a query are one of n_sets sets in CSR form:
+ * ptr int64 [n_sets + 1], items int32 [n_items = ptr[n_sets]], the items of a set ASCENDING and DISTINCT, each in [0, n_node).
+ * For query q:  row = pred + q * row_stride holds n_node scores;  s = set_of[q * index_stride];  the list L_q is
+ * items[ptr[s] .. ptr[s + 1]) for s in [0, n_sets) and EVERY entity [0, n_node) for s == -1 (set_of == NULL: -1 for every
+ * query);  the completions are C_q = {e : base_q + e in keys} with base_q = (anchor_q * n_rel + rel_q) * n_node, anchor / rel
+ * read at [q * index_stride] -- the keys of ultra_topk_keys; keys == NULL: nothing is filtered;  the candidates are L_q \ C_q.
+ * target_q is read at [q * target_stride].
+ * Outputs, each optional (NULL: not written; all five NULL: ULTRA_ERR_NULL_POINTER):
+ *   n_free[q]  (int64) = |L_q \ C_q|;
+ *   member[q]  (uint8) = 1 iff target_q is in L_q (0 when target == NULL or target_q == -1);
+ *   rank[q]    (int64) = 1 + #{e in L_q \ C_q : row[target_q] <= row[e]} -- the comparison of ultra_filtered_rank_keys:
+ *              pessimistic on ties, false for a NaN on either side.  A target that is a candidate counts itself;
+ *              row[target_q] is read whether or not the target is in the list.  rank = 0 when target == NULL or target_q == -1;
+ *   top_index[q, j] (int64) / top_value[q, j] (fp32), contiguous [n_query, k]: the candidates in the order of ultra_topk_keys --
+ *              score descending as floats, -0.0 == +0.0, equal scores by ascending ENTITY (not by position in the list), NaN
+ *              after every number -- with top_value = row[top_index] in its exact bits (re-read from pred); slots
+ *              j >= n_free[q] hold -1 / -inf.
+ * max_len bounds every list's length (n_node when -1 may occur): a longer list has only its first max_len positions
+ * considered.  max_len <= 32768: ONE launch, one workgroup of 256 threads per query, no workspace.  Longer: two launches -- grid
+ * (slices of 32768 positions, queries) leaves each slice's k sort keys and two integer counts in the workspace
+ * (ultra_candidate_select_workspace(n_query, max_len, k) bytes = n_query * slices * (8 * k + 16), 0 for short lists; a k outside
+ * [1, 128] stands for "no top outputs"; ULTRA_ERR_WORKSPACE when it is smaller), then one workgroup per query combines them.
+ * The grid is sized by queries and slices alone.  Counts are integers and the order is total: every schedule, eager or replayed
+ * from a hipGraph, gives the same words.
+ * No id read from device memory addresses anything unchecked: a set id outside [-1, n_sets) is the empty list, ptr values are
+ * clamped to [0, n_items], an item outside [0, n_node) is skipped, a target outside [0, n_node) counts as -1.  (Items that are
+ * not ascending and distinct give an unspecified selection, never an out-of-bounds access.)
+ * Before any device work: 1 <= k <= 128 when a top output is asked for, n_node in [1, 2^31), row_stride >= n_node,
+ * 0 <= max_len < 2^31, n_query <= 65535 in the two-launch form, n_rel > 0 and n_node * n_rel * n_node < 2^63 when keys is given,
+ * no negative count or stride: ULTRA_ERR_BAD_SHAPE otherwise.  n_query == 0: ULTRA_OK, nothing is written.
+ * Only enqueues work: no allocation, no host synchronisation, capturable. */
+size_t ultra_candidate_select_workspace(int64_t n_query, int64_t max_len, int64_t k);
+int ultra_candidate_select_f32(const float *pred, int64_t n_query, int64_t n_node, int64_t row_stride, const int64_t *ptr,
+                               const int32_t *items, int64_t n_sets, int64_t n_items, const int64_t *set_of, int64_t max_len,
+                               const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel,
+                               int64_t index_stride, int64_t n_rel, const int64_t *target, int64_t target_stride, int64_t k,
+                               int64_t *top_index, float *top_value, int64_t *rank, int64_t *n_free, uint8_t *member,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* Divergence guard of training steps (csrc/guard.inc): does a LIST of fp32 tensors hold a non-finite element?
  * Replaces: torch.autograd.set_detect_anomaly(True) of the reference's training run (script/run_full.py:127), which raises at the
  * step that produces a NaN.  A step replayed from a hipGraph cannot raise, so the verdict is left in a device RECORD that the

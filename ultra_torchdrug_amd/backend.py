@@ -22,6 +22,10 @@ optional functions: a backend is an object with this complete interface
                                         device tensors run ``ultra_relation_select_f32``, CPU tensors the dense twin of the
                                         same definition; a backend whose ``accepts()`` is false is not asked: the callers go
                                         to ``functional.relation_select``)
+    candidate_select                   (``task.answer(candidates=...)`` / ``task.rank_among`` / ``engine.answer`` /
+                                        ``engine.evaluate_constrained``; device tensors run ``ultra_candidate_select_f32``, CPU
+                                        tensors the dense twin; as ``relation_select``, a backend whose ``accepts()`` is false
+                                        is not asked: the callers go to ``functional.candidate_select``)
     set_boundary                       (reached ONLY from ``project`` / ``project_train``, on tensors the backend accepts; a
                                         backend whose ``accepts()`` is false gets ``functional.dense_set_boundary``, the same
                                         definition in torch ops.  Under grad it and ``score_all_entities`` are differentiable

@@ -211,61 +211,8 @@ __global__ __launch_bounds__(64 * kSampledWaves) void sampled_rank_keys_kernel(
 // threshold is looked up in the query's range of the completion keys (binary search) and, when it is none of them, appended to
 // LDS [128, 2048) through an LDS counter (one atomic per wave).  When the next tile might not fit, and at the end, best + appended
 // are sorted (bitonic, descending, over the next power of two) and cut to K.  The threshold only changes there, between barriers.
-constexpr int kTopkLds = 2048;               // keys in LDS (16 KB): [0, 128) the best so far, [128, 2048) survivors
-constexpr int kTopkTile = 1024;               // candidates per step of a workgroup
+// (kTopkLds, kTopkTile, TopkShared, topk_push and topk_flush are in select_keys.h, shared with candidate_select.hip)
 enum { kTopkRow = 0, kTopkSlice = 1, kTopkCombine = 2 };
-
-struct TopkShared {
-    unsigned long long arr[kTopkLds];
-    unsigned long long thr;
-    long long range[2];
-    int count;
-};
-
-// every thread of the workgroup calls it (the ballot and the shuffle are wave-wide)
-__device__ __forceinline__ void topk_push(TopkShared &sh, unsigned long long key, bool pass) {
-    const unsigned long long mask = __ballot(pass ? 1 : 0);
-    if (mask == 0ull) return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mask) - 1;
-    int start = 0;
-    if (lane == leader) start = atomicAdd(&sh.count, __popcll(mask));
-    start = __shfl(start, leader, 64);
-    if (pass) sh.arr[kTopkMax + start + __popcll(mask & ((1ull << lane) - 1ull))] = key;
-}
-
-// best K of (best so far + appended) -> arr[0, K) descending, threshold = arr[K - 1], count = 0.  Called by every thread, after a
-// barrier behind the last append.
-__device__ void topk_flush(TopkShared &sh, int K) {
-    const int tid = threadIdx.x;
-    const int cnt = sh.count;
-    if (cnt == 0) return;
-    const int n = kTopkMax + cnt;
-    int P = 256;
-    while (P < n) P <<= 1;
-    for (int j = K + tid; j < kTopkMax; j += 256) sh.arr[j] = kTopkEmpty;        // leftovers of the last sort
-    for (int j = n + tid; j < P; j += 256) sh.arr[j] = kTopkEmpty;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += 256) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i | j;
-                const unsigned long long a = sh.arr[i], b = sh.arr[l];
-                if ((a < b) == ((i & k) == 0)) {
-                    sh.arr[i] = b;
-                    sh.arr[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) {
-        sh.thr = sh.arr[K - 1];
-        sh.count = 0;
-    }
-    __syncthreads();
-}
 
 // MODE kTopkRow:     grid (queries): the whole row, value / index written.
 // MODE kTopkSlice:   grid (slices, queries): candidates [slice * kRankSlice, ...), the slice's K keys -> ws[q, slice, 0 .. K).

@@ -29,6 +29,9 @@
 //   ultra_mi::relation_select(score, cand?, keys_head?, keys_tail?, h?, t?, target?, n_rel, n_node, k, outputs)
 //       -> (top_index, top_value, rank, n_free, known)
 //       relation prediction: known relations, filtered rank and the k best relations of every (h, t) pair (CUDA key)
+//   ultra_mi::candidate_select(pred, ptr?, items?, set_of?, max_len, keys?, anchor?, rel?, n_rel, target?, k, outputs)
+//       -> (top_index, top_value, rank, n_free, member)
+//       candidate sets: rank, membership, count and the k best entities of every query among its set of entities (CUDA key)
 //   plan-based forms used by ultra_torchdrug_amd.functional (the plan = the bytes of one `ultra_segments` struct in a
 //   CPU uint8 tensor; the device arrays it points to are owned by the Python RelCSR object):
 //   ultra_mi::rspmm_plan_fwd(plan, relation, input, add_rows?, boundary_node?, boundary_value?, n_src, sum_op, mul_op) -> Tensor
@@ -1361,9 +1364,89 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> relation_select_hip(
     return {top_index, top_value, rank, n_free, known};
 }
 
+// ------------------------------------------------------------------------------------------------ candidate_select
+// Candidate sets (include/ultra_rspmm.h, ultra_candidate_select_f32): rank, membership, count and the k
+// best entities of every query among its set of admissible entities, from a (Q, N) block of scores.  Device key only (CPU
+// tensors take functional.dense_candidate_select, the same definition in torch ops).  Views go to the kernel as they are: pred
+// needs unit stride along its rows, set_of / anchor / rel one common element stride.  outputs: bit 0 top_index, 1 top_value,
+// 2 rank, 3 n_free, 4 member; an output that is not asked for comes back as an empty tensor and is NULL for the kernel.  The
+// workspace of lists longer than 32768 comes from the caching allocator before the launches.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> candidate_select_hip(
+        const Tensor &pred, const optional<Tensor> &ptr, const optional<Tensor> &items, const optional<Tensor> &set_of,
+        int64_t max_len, const optional<Tensor> &keys, const optional<Tensor> &anchor, const optional<Tensor> &rel, int64_t n_rel,
+        const optional<Tensor> &target, int64_t k, int64_t outputs) {
+    check_dense(pred, "pred", at::kFloat, pred);
+    TORCH_CHECK(pred.dim() == 2 && pred.size(1) >= 1 && pred.stride(1) == 1,
+                "ultra_mi::candidate_select: pred must be fp32 (Q, N >= 1) with contiguous rows");
+    const int64_t Q = pred.size(0), N = pred.size(1);
+    TORCH_CHECK(Q <= 1 || pred.stride(0) >= N, "ultra_mi::candidate_select: the rows of pred overlap");
+    TORCH_CHECK((outputs & 31) != 0 && (outputs & ~(int64_t)31) == 0, "ultra_mi::candidate_select: outputs must name 1 to 5 results");
+    auto given = [](const optional<Tensor> &x) { return x.has_value() && x->defined(); };
+    auto vector_of = [&](const optional<Tensor> &x, const char *name, at::ScalarType dtype, int64_t n, bool dense) -> const void * {
+        if (!given(x)) return nullptr;
+        check_dense(*x, name, dtype, pred);
+        TORCH_CHECK(x->dim() == 1 && (n < 0 || x->numel() == n), "ultra_mi::candidate_select: ", name, " has shape ", x->sizes());
+        TORCH_CHECK(!dense || x->is_contiguous(), "ultra_mi::candidate_select: ", name, " must be contiguous");
+        return x->data_ptr();
+    };
+    const auto *ptr_p = static_cast<const int64_t *>(vector_of(ptr, "ptr", at::kLong, -1, true));
+    const auto *items_p = static_cast<const int32_t *>(vector_of(items, "items", at::kInt, -1, true));
+    const auto *keys_p = static_cast<const int64_t *>(vector_of(keys, "keys", at::kLong, -1, true));
+    const auto *set_p = static_cast<const int64_t *>(vector_of(set_of, "set_of", at::kLong, Q, false));
+    const auto *anchor_p = static_cast<const int64_t *>(vector_of(anchor, "anchor", at::kLong, Q, false));
+    const auto *rel_p = static_cast<const int64_t *>(vector_of(rel, "rel", at::kLong, Q, false));
+    const auto *target_p = static_cast<const int64_t *>(vector_of(target, "target", at::kLong, Q, false));
+    // (an empty tensor has no data pointer: whether an argument was given is asked of the tensor)
+    TORCH_CHECK(given(ptr) == given(items) && (!given(ptr) || ptr->numel() >= 1),
+                "ultra_mi::candidate_select: ptr (S + 1,) and items come together");
+    TORCH_CHECK(!given(set_of) || given(ptr), "ultra_mi::candidate_select: set_of needs the sets");
+    TORCH_CHECK((anchor_p == nullptr) == (rel_p == nullptr), "ultra_mi::candidate_select: anchor and rel come together");
+    TORCH_CHECK(keys_p == nullptr || anchor_p != nullptr, "ultra_mi::candidate_select: a filtered selection needs anchor and rel");
+    int64_t index_stride = 1;
+    if (Q > 1) {
+        bool first = true;
+        for (const optional<Tensor> *x : {&set_of, &anchor, &rel}) {
+            if (!given(*x)) continue;
+            TORCH_CHECK((*x)->stride(0) >= 1 && (first || (*x)->stride(0) == index_stride),
+                        "ultra_mi::candidate_select: set_of, anchor and rel must share one positive stride");
+            index_stride = (*x)->stride(0);
+            first = false;
+        }
+    }
+    const int64_t target_stride = (target_p != nullptr && Q > 1) ? target->stride(0) : 1;
+    TORCH_CHECK(target_stride >= 0, "ultra_mi::candidate_select: target has a negative stride");
+    const bool want_top = (outputs & 3) != 0;
+    TORCH_CHECK(!want_top || (k >= 1 && k <= 128), "ultra_mi::candidate_select: 1 to 128 entities per query, got ", k);
+    const int64_t k_out = want_top ? k : 1;
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pred.device());
+    const auto i64 = pred.options().dtype(at::kLong);
+    Tensor top_index = at::empty({(outputs & 1) ? Q : 0, k_out}, i64);
+    Tensor top_value = at::empty({(outputs & 2) ? Q : 0, k_out}, pred.options());
+    Tensor rank = at::empty({(outputs & 4) ? Q : 0}, i64);
+    Tensor n_free = at::empty({(outputs & 8) ? Q : 0}, i64);
+    Tensor member = at::empty({(outputs & 16) ? Q : 0}, pred.options().dtype(at::kByte));
+    if (Q == 0) return {top_index, top_value, rank, n_free, member};
+    const size_t ws_bytes = ultra_candidate_select_workspace(Q, max_len, want_top ? k : 0);
+    Tensor ws = at::empty({(int64_t)(ws_bytes / 8)}, i64);
+    check_status(ultra_candidate_select_f32(pred.data_ptr<float>(), Q, N, Q > 1 ? pred.stride(0) : N, ptr_p, items_p,
+                                            ptr_p ? ptr->numel() - 1 : 0, items_p ? items->numel() : 0, set_p, max_len, keys_p,
+                                            keys_p ? keys->numel() : 0, anchor_p, rel_p, index_stride, n_rel, target_p,
+                                            target_stride, k,
+                                            (outputs & 1) ? top_index.data_ptr<int64_t>() : nullptr,
+                                            (outputs & 2) ? top_value.data_ptr<float>() : nullptr,
+                                            (outputs & 4) ? rank.data_ptr<int64_t>() : nullptr,
+                                            (outputs & 8) ? n_free.data_ptr<int64_t>() : nullptr,
+                                            (outputs & 16) ? member.data_ptr<uint8_t>() : nullptr,
+                                            ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, current_stream(pred)),
+                 "ultra_candidate_select_f32");
+    return {top_index, top_value, rank, n_free, member};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
+    m.def("candidate_select(Tensor pred, Tensor? ptr, Tensor? items, Tensor? set_of, int max_len, Tensor? keys, Tensor? anchor, "
+          "Tensor? rel, int n_rel, Tensor? target, int k, int outputs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("relation_select(Tensor score, Tensor? cand, Tensor? keys_head, Tensor? keys_tail, Tensor? h, Tensor? t, Tensor? target, "
           "int n_rel, int n_node, int k, int outputs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("build_relcsr(Tensor edge_list, Tensor? edge_weight, int num_node, int num_relation) -> Tensor[]");
@@ -1415,6 +1498,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("beam_search_step_batch", beam_search_step_batch_hip);
     m.impl("hop_distance", hop_distance_hip);
     m.impl("relation_select", relation_select_hip);
+    m.impl("candidate_select", candidate_select_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)

@@ -87,6 +87,114 @@ def stress_task(device, n_node=None, n_triple=None, n_rel=None, seed=DEFAULT_SEE
     return task, gen
 
 
+class CandidateSets:
+    """``S`` sets of entities in CSR form, the admissible answers of ``task.answer(candidates=...)``, ``task.rank_among`` and
+    ``functional.candidate_select``: ``ptr`` int64 ``(S + 1,)``, ``items`` int32 ``(ptr[S],)`` with the
+    items of every set ASCENDING and DISTINCT, each in ``[0, num_node)``; ``max_len`` the longest set's length (a host int).
+    The constructor checks all of that with ONE host read (``validate=False``: the caller vouches for it and passes
+    ``max_len``).  :meth:`to` moves it."""
+
+    def __init__(self, ptr, items, num_node, max_len=None, validate=True):
+        ptr, items = torch.as_tensor(ptr), torch.as_tensor(items)
+        num_node = int(num_node)
+        if ptr.dtype != torch.int64 or ptr.dim() != 1 or ptr.numel() < 1:
+            raise ValueError("CandidateSets: ptr must be int64 (S + 1,), got %s %s" % (ptr.dtype, tuple(ptr.shape)))
+        if items.dtype != torch.int32 or items.dim() != 1 or items.device != ptr.device:
+            raise ValueError("CandidateSets: items must be int32 (ptr[S],) on %s, got %s %s on %s"
+                             % (ptr.device, items.dtype, tuple(items.shape), items.device))
+        if not 1 <= num_node < 2 ** 31:
+            raise ValueError("CandidateSets: num_node must be in [1, 2^31), got %d" % num_node)
+        self.ptr, self.items, self.num_node = ptr.contiguous(), items.contiguous(), num_node
+        if validate:
+            n = items.numel()
+            length = ptr[1:] - ptr[:-1]
+            bad_ptr = (ptr[0] != 0) | (ptr[-1] != n) | (length < 0).any()
+            bad_item = ((items < 0) | (items >= num_node)).any()
+            starts = torch.zeros(n + 1, dtype=torch.bool, device=ptr.device)
+            starts[ptr.clamp(0, n)] = True                                       # position i begins a set
+            bad_order = (~((items[1:] > items[:-1]) | starts[1:n])).any() if n > 1 else torch.zeros((), dtype=torch.bool, device=ptr.device)
+            longest = length.max() if length.numel() else torch.zeros((), dtype=torch.int64, device=ptr.device)
+            bad_ptr, bad_item, bad_order, longest = torch.stack([bad_ptr.long(), bad_item.long(), bad_order.long(), longest]).tolist()
+            if bad_ptr:
+                raise ValueError("CandidateSets: ptr must start at 0, never decrease and end at len(items) = %d" % n)
+            if bad_item:
+                raise ValueError("CandidateSets: items outside [0, %d)" % num_node)
+            if bad_order:
+                raise ValueError("CandidateSets: the items of a set must be ascending and distinct")
+            max_len = longest
+        elif max_len is None:
+            raise ValueError("CandidateSets: validate=False needs max_len")
+        self.max_len = int(max_len)
+
+    @property
+    def num_sets(self):
+        return self.ptr.numel() - 1
+
+    def __len__(self):
+        return self.num_sets
+
+    @property
+    def device(self):
+        return self.ptr.device
+
+    def to(self, device):
+        """The same sets on ``device`` (not validated again)."""
+        return CandidateSets(self.ptr.to(device), self.items.to(device), self.num_node, self.max_len, validate=False)
+
+    def set(self, s):
+        """The items of set ``s``, int32 (a view)."""
+        first, last = self.ptr[s:s + 2].tolist()
+        return self.items[first:last]
+
+
+def _sets_from_keys(keys, n_sets, num_node):
+    """:class:`CandidateSets` from int64 keys ``set * num_node + entity`` (any order, duplicates merged)."""
+    keys = torch.unique(keys)                                                    # sorted and distinct
+    ptr = torch.searchsorted(keys, torch.arange(n_sets + 1, dtype=torch.int64, device=keys.device) * num_node)
+    return CandidateSets(ptr, (keys % num_node).to(torch.int32), num_node)
+
+
+def relation_candidates(triples, num_node, num_relation):
+    """The type constraints a graph implies, ``2R`` :class:`CandidateSets` from ``(n, 3)`` rows of ``(h, t, r)``: set ``r`` is
+    ``{t : (h, r, t)}``, the RANGE of ``r`` -- the admissible tails of ``(h, r, ?)`` -- and set ``r + R`` is ``{h : (h, r, t)}``,
+    the range of the inverse relation, i.e. the DOMAIN of ``r`` -- the admissible heads of ``(?, r, t)``, which the package asks
+    as ``(t, r + R, ?)``.  A relation without a triple gets the empty set.  Ids out of range raise ``ValueError``."""
+    triples = torch.as_tensor(triples)
+    num_node, num_relation = int(num_node), int(num_relation)
+    if triples.dim() != 2 or triples.shape[1] != 3 or triples.dtype != torch.int64:
+        raise ValueError("relation_candidates takes int64 (n, 3) rows of (h, t, r), got %s %s" % (triples.dtype, tuple(triples.shape)))
+    if num_relation < 0 or not 1 <= num_node < 2 ** 31:
+        raise ValueError("relation_candidates: %d entities and %d relations" % (num_node, num_relation))
+    h, t, r = triples.t()
+    if len(triples):
+        lo, hi_node, hi_rel = torch.stack([triples.min(), torch.max(h.max(), t.max()), r.max()]).tolist()
+        if lo < 0 or hi_node >= num_node or hi_rel >= num_relation:
+            raise ValueError("relation_candidates: triples out of range for %d entities and %d relations: min id %d, max entity "
+                             "%d, max relation %d" % (num_node, num_relation, lo, hi_node, hi_rel))
+    return _sets_from_keys(torch.cat([r * num_node + t, (r + num_relation) * num_node + h]), 2 * num_relation, num_node)
+
+
+def candidate_sets(lists, num_node, device=None):
+    """:class:`CandidateSets` from user-supplied types: ``lists`` is a sequence of Python lists or integer tensors of entity ids,
+    one per set, in any order and with repeats -- they are sorted and deduplicated.  An id outside ``[0, num_node)`` raises
+    ``ValueError``."""
+    num_node = int(num_node)
+    if not 1 <= num_node < 2 ** 31:
+        raise ValueError("candidate_sets: num_node must be in [1, 2^31), got %d" % num_node)
+    keys = []
+    for i, ids in enumerate(lists):
+        ids = torch.as_tensor(ids, device=device).reshape(-1) if not (isinstance(ids, (list, tuple)) and len(ids) == 0) \
+            else torch.zeros(0, dtype=torch.int64, device=device)
+        if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError("candidate_sets: set %d holds %s, expected entity ids" % (i, ids.dtype))
+        ids = ids.long()
+        if len(ids) and (int(ids.min()) < 0 or int(ids.max()) >= num_node):
+            raise ValueError("candidate_sets: set %d has ids outside [0, %d)" % (i, num_node))
+        keys.append(i * num_node + ids)
+    keys = torch.cat(keys) if keys else torch.zeros(0, dtype=torch.int64, device=device)
+    return _sets_from_keys(keys, len(lists), num_node)
+
+
 def load_triples(path, entity_vocab=None, relation_vocab=None):
     """Read ``h<TAB>r<TAB>t`` lines (the layout of ``ultra/dataset.py:69-96``) into ``(h, t, r)`` ids."""
     entity_vocab = {} if entity_vocab is None else entity_vocab

@@ -826,23 +826,40 @@ def _ranks_of_unique_queries(task, local, batch_size, graphed, statistics=False,
 
 
 @torch.no_grad()
-def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None, filtered=None, with_hops=False):
+def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None, filtered=None, with_hops=False,
+           candidates=None, candidate_set=None):
     """``task.answer`` over any number of queries: the ``k`` best unfiltered entities of ``(anchor[q], relation[q], ?)`` (``head``:
     of ``(?, relation[q], anchor[q])``).  The queries are scored ``2 * batch_size`` at a time through one :class:`GraphedScores`
     (the last chunk repeats its end) and ``functional.topk_keys`` is enqueued on each chunk's static scores: nothing of size
     ``(Q, N)`` beside those scores is built and nothing is read back per chunk.  ``graphed`` (default: on a GPU, in eval mode,
     when there are at least two full chunks): the score pass is captured once and replayed.  A model without a fused all-entity
     score head goes through ``task.answer`` chunk by chunk.  Returns ``(entities int64 (Q, k), scores fp32 (Q, k))`` and, with
-    ``with_hops``, ``task.answer_hops`` of all of them as a third result (one hop-distance call behind the chunks)."""
+    ``with_hops``, ``task.answer_hops`` of all of them as a third result (one hop-distance call behind the chunks).
+    ``candidates`` / ``candidate_set``: as ``task.answer`` -- each query's answers come from its set of a ``data.CandidateSets``,
+    checked once for the call, and ``functional.candidate_select`` takes the place of ``topk_keys`` on every chunk."""
     from . import backend
     if with_hops:
-        entities, scores = answer(task, anchor, relation, k, head, batch_size, graphed, filtered)
+        entities, scores = answer(task, anchor, relation, k, head, batch_size, graphed, filtered, False, candidates, candidate_set)
         return entities, scores, task.answer_hops(task.answer_queries(anchor, relation, head)[0], entities)
-    anchor, q_rel, base = task.answer_queries(anchor, relation, head)
+    sets = set_of = max_len = None
+    if candidates is None:
+        if candidate_set is not None:
+            raise ValueError("answer: candidate_set needs candidates")
+        anchor, q_rel, base = task.answer_queries(anchor, relation, head)
+    elif candidate_set is None:
+        anchor, q_rel, base = task.answer_queries(anchor, relation, head)
+        sets, set_of, max_len = task.answer_sets(candidates, q_rel)
+    else:
+        if not hasattr(candidates, "num_sets"):
+            raise ValueError("answer: candidates must be a data.CandidateSets, got %s" % type(candidates).__name__)
+        anchor, q_rel, base, set_of, any_all = task.answer_queries(anchor, relation, head, candidate_set, candidates.num_sets)
+        sets, set_of, max_len = task.answer_sets(candidates, q_rel, set_of, any_all)
     keys, n_rel, n_node = task.answer_filter(head, filtered)
     n, chunk = len(anchor), 2 * batch_size
     if graphed is None:
         graphed = task.device.type == "cuda" and n >= 2 * chunk and not task.training
+    if sets is not None and not 1 <= int(k) <= 128:
+        raise ValueError("answer: 1 to 128 answers per query, got %d" % int(k))
     entities, scores = [], []
     scorer = None
     for c in range(0, n, chunk):
@@ -851,16 +868,55 @@ def answer(task, anchor, relation, k=10, head=False, batch_size=16, graphed=None
         if scorer is None:
             probe = GraphedScores(task, *args, graphed=False)
             if probe(*args) is None:                     # no fused all-entity score path for this model
-                parts = [task.answer(anchor[i:i + chunk], base[i:i + chunk], k, head, filtered) for i in range(0, n, chunk)]
+                parts = [task.answer(anchor[i:i + chunk], base[i:i + chunk], k, head, filtered, False, sets,
+                                     None if candidate_set is None else set_of[i:i + chunk]) for i in range(0, n, chunk)]
                 return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             scorer = GraphedScores(task, *args, graphed=bool(graphed) and n >= 2 * chunk)
-        value, index = backend.get().topk_keys(scorer(*args), k, keys, args[0], args[2], n_rel, n_node)
+        if sets is None:
+            value, index = backend.get().topk_keys(scorer(*args), k, keys, args[0], args[2], n_rel, n_node)
+        else:
+            found = task._candidate_select(scorer(*args), sets, set_of[ids], int(k), keys, args[0], args[2], n_rel, None,
+                                           ("top_index", "top_value"), max_len)
+            index, value = found.top_index, found.top_value
         keep = min(chunk, n - c)
         entities.append(index[:keep])
         scores.append(value[:keep])
     if not entities:
-        return task.answer(anchor, base, k, head, filtered)
+        return task.answer(anchor, base, k, head, filtered, False, sets, None if candidate_set is None else set_of)
     return torch.cat(entities), torch.cat(scores)
+
+
+@torch.no_grad()
+def evaluate_constrained(task, triples, candidates, batch_size=16):
+    """Type-constrained evaluation, the usual protocol beside the filtered one: every tail of ``triples`` (``(n, 3)`` rows of
+    (h, t, r)) is ranked among the set ``r`` of ``candidates`` and every head among the set ``r + R`` (``data.relation_candidates``;
+    ``task.rank_among``, both sides filtered by the context's filter graph as ``evaluate``).  A side whose target is NOT in its set
+    is left out of every mean and counted in ``outside`` -- never silently ranked.  Returns a dict with ``mrr``, ``mr``, ``hits@1``,
+    ``hits@3``, ``hits@10`` over the sides inside (``nan`` when there is none), ``outside``, ``ranks`` int64 ``(n, 2)`` (column 0
+    the tail side; 0 for a side outside), and ``mean_candidates``, the mean number of candidates a side inside was ranked among.
+    ``batch_size`` triples are scored at a time; one host read at the end."""
+    triples = torch.as_tensor(triples, device=task.device).long()
+    if triples.dim() != 2 or triples.shape[1] != 3:
+        raise ValueError("evaluate_constrained takes (n, 3) rows of (h, t, r), got %s" % (tuple(triples.shape),))
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("evaluate_constrained: batch_size must be positive, got %d" % batch_size)
+    validate_triples(task, triples)
+    parts = [task.rank_among(triples[i:i + batch_size], candidates) for i in range(0, len(triples), batch_size)]
+    if parts:
+        ranks, member, count = (torch.cat([p[j] for p in parts]) for j in range(3))
+    else:
+        ranks = count = torch.zeros(0, 2, dtype=torch.int64, device=triples.device)
+        member = torch.zeros(0, 2, dtype=torch.bool, device=triples.device)
+    ranks = torch.where(member, ranks, torch.zeros_like(ranks))
+    inside = member.double()                              # 1 for a side inside its set; its rank is at least 1 there
+    safe = ranks.clamp(min=1).double()
+    sums = [inside.sum(), (inside / safe).sum(), (inside * ranks).sum(), (inside * count).sum()]
+    sums += [(inside * (safe <= top)).sum() for top in (1, 3, 10)]
+    n_inside, mrr, mr, candidates, hits1, hits3, hits10 = torch.stack(sums).tolist()          # the one host read
+    mean = lambda total: total / n_inside if n_inside else float("nan")
+    return {"outside": int(member.numel() - n_inside), "ranks": ranks, "mrr": mean(mrr), "mr": mean(mr), "hits@1": mean(hits1),
+            "hits@3": mean(hits3), "hits@10": mean(hits10), "mean_candidates": mean(candidates)}
 
 
 def _relation_blocks(task, h, t, cand, pair_batch, batch_size):

@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "candidate_select", "dense_candidate_select", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1524,6 +1524,160 @@ def relation_select(score, cand, keys_head, keys_tail, h, t, target, n_rel, n_no
                 target.stride(0) if (target is not None and rows > 1) else 1, n_rel, n_node, k,
                 *[out[name] for name in RELATION_OUTPUTS])
     return RelationSelection(**out)
+
+
+# ---------------------------------------------------------------------------------------------------------- candidate sets
+CANDIDATE_OUTPUTS = ("top_index", "top_value", "rank", "n_free", "member")    # bit i of the operator's `outputs` argument
+CandidateSelection = collections.namedtuple("CandidateSelection", CANDIDATE_OUTPUTS)
+CANDIDATE_SLICE = 32768         # list positions per workgroup of ultra_candidate_select_f32; longer lists take two launches
+
+
+def _candidate_arguments(name, pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len):
+    """The checked arguments of :func:`candidate_select` / :func:`dense_candidate_select`:
+    ``(set_of, anchor, rel, index stride, target, outputs, max_len)``."""
+    if pred.dim() != 2 or pred.dtype != torch.float32 or pred.shape[1] < 1 or pred.stride(1) != 1:
+        raise RuntimeError("%s: pred must be fp32 (Q, N >= 1) with contiguous rows" % name)
+    rows, n_node = pred.shape
+    dev = pred.device
+    if rows > 1 and pred.stride(0) < n_node:
+        raise RuntimeError("%s: the rows of pred overlap" % name)
+    if n_node >= 2 ** 31:
+        raise RuntimeError("%s: entity ids are 31-bit, got %d entities" % (name, n_node))
+    outputs = tuple(outputs)
+    if not outputs or any(o not in CANDIDATE_OUTPUTS for o in outputs):
+        raise RuntimeError("%s: outputs must name some of %s, got %s" % (name, CANDIDATE_OUTPUTS, outputs))
+    if ("top_index" in outputs or "top_value" in outputs) and not 1 <= int(k) <= TOPK_MAX:
+        raise RuntimeError("%s: 1 to %d entities per query, got %d" % (name, TOPK_MAX, int(k)))
+    if sets is None and set_of is not None:
+        raise RuntimeError("%s: set_of needs the sets" % name)
+    if sets is not None:
+        if int(sets.num_node) != n_node:
+            raise RuntimeError("%s: the scores list %d entities but the sets were built over %d" % (name, n_node, int(sets.num_node)))
+        if (sets.ptr.dtype != torch.int64 or sets.items.dtype != torch.int32 or sets.ptr.dim() != 1 or sets.items.dim() != 1
+                or sets.ptr.numel() < 1 or sets.ptr.device != dev or sets.items.device != dev
+                or not sets.ptr.is_contiguous() or not sets.items.is_contiguous()):
+            raise RuntimeError("%s: the sets must hold contiguous ptr int64 (S + 1,) and items int32 on %s" % (name, dev))
+    if set_of is not None and (set_of.dtype != torch.int64 or set_of.shape != (rows,) or set_of.device != dev):
+        raise RuntimeError("%s: set_of must be int64 (%d,) on %s" % (name, rows, dev))
+    if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous() or keys.device != dev):
+        raise RuntimeError("%s: keys must be a contiguous int64 vector on %s" % (name, dev))
+    if keys is not None and (anchor is None or rel is None):
+        raise RuntimeError("%s: a filtered selection needs anchor and rel" % name)
+    if keys is not None and (int(n_rel) <= 0 or float(n_node) ** 2 * int(n_rel) >= 2.0 ** 63):
+        raise RuntimeError("%s: n_rel must be positive with 64-bit keys, got %d over %d entities" % (name, int(n_rel), n_node))
+    stride = 1
+    if anchor is not None or rel is not None:
+        if anchor is None or rel is None:
+            raise RuntimeError("%s: anchor and rel come together" % name)
+        anchor, rel, stride = _index_pair(name, anchor, rel, rows, dev)
+    if set_of is not None and rows > 1 and (set_of.stride(0) < 1 or (anchor is not None and set_of.stride(0) != stride)):
+        if anchor is not None and stride != 1:
+            anchor, rel, stride = anchor.contiguous(), rel.contiguous(), 1
+        set_of = set_of.contiguous()
+    if set_of is not None and anchor is None and rows > 1:
+        stride = set_of.stride(0)
+    if target is not None and (target.dtype != torch.int64 or target.shape != (rows,) or target.device != dev):
+        raise RuntimeError("%s: target must be int64 (%d,) on %s" % (name, rows, dev))
+    if target is not None and rows > 1 and target.stride(0) < 0:
+        target = target.contiguous()
+    if max_len is None:
+        max_len = n_node                                  # (right for every set_of: a -1 takes all entities)
+    max_len = int(max_len)
+    if not 0 <= max_len < 2 ** 31:
+        raise RuntimeError("%s: max_len must be in [0, 2^31), got %d" % (name, max_len))
+    return set_of, anchor, rel, stride, target, outputs, max_len
+
+
+def dense_candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target=None, outputs=CANDIDATE_OUTPUTS, max_len=None):
+    """:func:`candidate_select` in torch ops from dense ``(Q, N)`` masks -- the twin CPU tensors take, and the route the device
+    kernel is timed against (it runs on any device; building the masks reads the host once)."""
+    set_of, anchor, rel, _, target, outputs, max_len = _candidate_arguments(
+        "dense_candidate_select", pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len)
+    rows, n = pred.shape
+    dev = pred.device
+    every = torch.arange(n, device=dev)[None, :] < max_len                       # the list of s == -1
+    if set_of is None:
+        listed = every.expand(rows, n)
+    else:
+        n_sets = sets.ptr.numel() - 1
+        real = (set_of >= 0) & (set_of < n_sets)
+        s = set_of.clamp(0, max(n_sets - 1, 0))
+        n_items = sets.items.numel()
+        first = sets.ptr[s].clamp(0, n_items) if n_sets else torch.zeros_like(s)
+        last = torch.maximum(sets.ptr[s + 1].clamp(0, n_items), first) if n_sets else first
+        count = torch.where(real, (last - first).clamp(max=max_len), torch.zeros_like(first))
+        row = torch.repeat_interleave(torch.arange(rows, device=dev), count)
+        at = torch.arange(int(count.sum()), device=dev) - torch.repeat_interleave(count.cumsum(0) - count, count) + first[row]
+        item = sets.items[at].long()
+        inside = (item >= 0) & (item < n)
+        listed = torch.zeros(rows, n, dtype=torch.bool, device=dev)
+        listed[row[inside], item[inside]] = True
+        listed = torch.where((set_of == -1)[:, None], every, listed)
+    known = torch.zeros(rows, n, dtype=torch.bool, device=dev)
+    if keys is not None and rows and keys.numel():
+        base = (anchor * int(n_rel) + rel) * n
+        first, last = torch.searchsorted(keys, base), torch.searchsorted(keys, base + n)
+        count = last - first
+        row = torch.repeat_interleave(torch.arange(rows, device=dev), count)
+        at = torch.arange(int(count.sum()), device=dev) - torch.repeat_interleave(count.cumsum(0) - count, count) + first[row]
+        known[row, keys[at] - base[row]] = True
+    cand = listed & ~known
+    n_free = cand.sum(dim=1)
+    rank = torch.zeros(rows, dtype=torch.int64, device=dev)
+    member = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    if target is not None:
+        valid = (target >= 0) & (target < n)
+        at = target.clamp(0, n - 1)[:, None]
+        rank = torch.where(valid, 1 + ((pred.gather(1, at) <= pred) & cand).sum(dim=1), rank)
+        member = (valid & listed.gather(1, at)[:, 0]).to(torch.uint8)
+    top_value = top_index = None
+    if "top_index" in outputs or "top_value" in outputs:
+        group = torch.where(cand, torch.isnan(pred).long(), torch.full((), 2, dtype=torch.int64, device=dev))
+        top_value, top_index = _dense_topk_groups(pred, group, int(k))
+    full = dict(top_index=top_index, top_value=top_value, rank=rank, n_free=n_free, member=member)
+    return CandidateSelection(*[full[name] if name in outputs else None for name in CANDIDATE_OUTPUTS])
+
+
+def candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target=None, outputs=CANDIDATE_OUTPUTS, max_len=None):
+    """Rank, counts and the ``k`` best entities of every query AMONG A SET of admissible entities (``ultra_candidate_select_f32``;
+    the contract is in ``include/ultra_rspmm.h``).  ``pred`` fp32 ``(Q, N)`` (a strided view with unit
+    stride along a row is fine); ``sets``: a ``data.CandidateSets`` over ``N`` entities (``ptr`` int64 ``(S + 1,)``, ``items``
+    int32, ascending and distinct inside a set) or ``None``; ``set_of`` int64 ``(Q,)``: the set of every query, ``-1`` = every
+    entity (``None``: ``-1`` for all).  ``keys`` / ``anchor`` / ``rel`` / ``n_rel``: the filter of :func:`topk_keys` (``keys=None``:
+    nothing is filtered); ``target`` int64 ``(Q,)`` entities (``-1``: none) or ``None``.  Returns a :class:`CandidateSelection`:
+    ``top_index`` int64 / ``top_value`` fp32 ``(Q, k)`` the candidates -- listed and not known -- in the order of
+    :func:`topk_keys` (equal scores by ascending ENTITY), ending in ``-1`` / ``-inf``; ``rank`` int64 ``(Q,)`` = ``1 + #{candidates
+    e : pred[q, target] <= pred[q, e]}`` whether or not the target is listed (0 without a target); ``n_free`` int64 ``(Q,)`` the
+    number of candidates; ``member`` uint8 ``(Q,)``: the target is listed.  ``outputs`` names the results to compute, the others
+    are ``None``.  ``max_len``: an upper bound of every list's length, ``N`` when a ``-1`` may occur (the default; a caller that
+    knows its ``set_of`` holds none passes ``sets.max_len``) -- lists of at most 32768 take one launch, longer ones two and a
+    workspace from the caching allocator.  No host synchronisation.  CPU tensors take :func:`dense_candidate_select`."""
+    if not pred.is_cuda:
+        return dense_candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len)
+    set_of, anchor, rel, stride, target, outputs, max_len = _candidate_arguments(
+        "candidate_select", pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len)
+    rows, n_node = pred.shape
+    dev = pred.device
+    want_top = "top_index" in outputs or "top_value" in outputs
+    k = int(k) if want_top else 1
+    ptr, items = (sets.ptr, sets.items) if sets is not None else (None, None)
+    if _torch_ext.binding() == "torch":
+        bits = sum(1 << CANDIDATE_OUTPUTS.index(name) for name in set(outputs))
+        full = _torch_ext.load().candidate_select(pred, ptr, items, set_of, max_len, keys, anchor, rel, int(n_rel), target, k, bits)
+        return CandidateSelection(*[value if name in outputs else None for name, value in zip(CANDIDATE_OUTPUTS, full)])
+    shapes = {"top_index": ((rows, k), torch.int64), "top_value": ((rows, k), torch.float32), "rank": ((rows,), torch.int64),
+              "n_free": ((rows,), torch.int64), "member": ((rows,), torch.uint8)}
+    out = {name: torch.empty(shape, dtype=dtype, device=dev) if name in outputs else None
+           for name, (shape, dtype) in shapes.items()}
+    if rows:
+        ws_bytes = int(_lib.load().ultra_candidate_select_workspace(rows, max_len, k if want_top else 0))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev) if ws_bytes else None
+        _launch(dev, "ultra_candidate_select_f32", pred, rows, n_node, pred.stride(0) if rows > 1 else n_node, ptr, items,
+                ptr.numel() - 1 if ptr is not None else 0, items.numel() if items is not None else 0, set_of, max_len, keys,
+                keys.numel() if keys is not None else 0, anchor, rel, stride, int(n_rel), target,
+                target.stride(0) if (target is not None and rows > 1) else 1, k, *[out[name] for name in CANDIDATE_OUTPUTS],
+                ws, ws_bytes)
+    return CandidateSelection(**out)
 
 
 def dense_set_boundary(member, query, floor=None, with_count=False):

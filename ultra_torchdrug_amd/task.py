@@ -486,23 +486,39 @@ class KnowledgeGraphCompletion(nn.Module):
             h, t, r = t, h, r + self.fact_graph.num_relation
         return self.model.visualize_batch(self.fact_graph, rel_inputs, h, t, r)
 
-    def answer_queries(self, anchor, relation, head=False):
+    def answer_queries(self, anchor, relation, head=False, candidate_set=None, num_sets=None):
         """The range-checked queries of :meth:`answer` in tail form: ``(anchor, query relation in [0, 2R), base relation)``,
         each int64 ``(Q,)`` on the task's device -- ``head=True`` asks ``(anchor, relation + R, ?)``
-        (``negative_sample_to_tail``)."""
+        (``negative_sample_to_tail``).  With ``candidate_set`` (int64 ``(Q,)`` ids in ``[-1, num_sets)``, checked in the same
+        host read) two more results: the set ids on the device and whether a ``-1`` -- every entity -- occurs."""
         anchor = torch.as_tensor(anchor, device=self.device).reshape(-1)
         relation = torch.as_tensor(relation, device=self.device).reshape(-1)
         if anchor.dtype != torch.int64 or relation.dtype != torch.int64 or anchor.shape != relation.shape:
             raise ValueError("answer: anchor and relation must be int64 (Q,), got %s %s and %s %s"
                              % (anchor.dtype, tuple(anchor.shape), relation.dtype, tuple(relation.shape)))
+        if candidate_set is not None:
+            candidate_set = torch.as_tensor(candidate_set, device=self.device).reshape(-1)
+            if candidate_set.dtype != torch.int64 or candidate_set.shape != anchor.shape:
+                raise ValueError("answer: candidate_set must be int64 (%d,), got %s %s"
+                                 % (len(anchor), candidate_set.dtype, tuple(candidate_set.shape)))
+        any_all = False
         if len(anchor):
             # once per call, as engine.validate_triples: the kernels index with these ids without a bounds check of their own
             n, r = self.num_entity, self.num_relation
-            lo, hi_node, hi_rel = int(torch.min(anchor.min(), relation.min())), int(anchor.max()), int(relation.max())
+            seen = [torch.min(anchor.min(), relation.min()), anchor.max(), relation.max()]
+            if candidate_set is not None:
+                seen += [candidate_set.min(), candidate_set.max()]
+            seen = torch.stack(seen).tolist()
+            lo, hi_node, hi_rel = seen[:3]
             if lo < 0 or hi_node >= n or hi_rel >= r:
                 raise ValueError("queries out of range for context `%s` (%d entities, %d relations): min id %d, max entity %d, "
                                  "max relation %d" % (self.split, n, r, lo, hi_node, hi_rel))
-        return anchor, (relation + self.fact_graph.num_relation if head else relation), relation
+            if candidate_set is not None:
+                if seen[3] < -1 or seen[4] >= int(num_sets):
+                    raise ValueError("answer: candidate_set must hold ids in [-1, %d), got %d to %d" % (int(num_sets), seen[3], seen[4]))
+                any_all = seen[3] == -1
+        queries = anchor, (relation + self.fact_graph.num_relation if head else relation), relation
+        return queries if candidate_set is None else queries + (candidate_set, any_all)
 
     def answer_filter(self, head=False, filtered=None):
         """``(keys, n_rel, n_node)`` of the filter of :meth:`answer`: the current context's sorted completion keys of the asked
@@ -554,16 +570,58 @@ class KnowledgeGraphCompletion(nn.Module):
         found = functional.hop_distance(self.message_graph().relcsr, anchor, len(self.model.layers), entities.clamp(min=0))
         return torch.where(entities < 0, torch.full_like(found, -1), found)
 
+    def answer_sets(self, candidates, q_rel, candidate_set=None, any_all=False):
+        """``(sets, set_of, max_len)`` of a constrained :meth:`answer`: the :class:`data.CandidateSets` on the task's device, every
+        query's set id -- ``candidate_set`` as :meth:`answer_queries` checked it, or by default the query relation in ``[0, 2R)``,
+        which needs the ``2R`` sets of ``data.relation_candidates`` -- and the bound of the list lengths (``num_entity`` when a
+        ``-1`` occurs)."""
+        if not all(hasattr(candidates, name) for name in ("ptr", "items", "num_node", "max_len")):
+            raise ValueError("answer: candidates must be a data.CandidateSets, got %s" % type(candidates).__name__)
+        if candidates.num_node != self.num_entity:
+            raise ValueError("answer: the candidate sets were built over %d entities, context `%s` has %d"
+                             % (candidates.num_node, self.split, self.num_entity))
+        if candidates.ptr.device != self.device:
+            candidates = candidates.to(self.device)
+        if candidate_set is None:
+            n_rel = self.fact_graph.num_relation
+            if candidates.num_sets != 2 * n_rel:
+                raise ValueError("answer: without candidate_set a query takes the set of its relation in [0, 2R): that needs %d "
+                                 "sets (data.relation_candidates), got %d" % (2 * n_rel, candidates.num_sets))
+            return candidates, q_rel, candidates.max_len
+        return candidates, candidate_set, (self.num_entity if any_all else candidates.max_len)
+
+    @staticmethod
+    def _candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len):
+        from . import functional
+        ops = backend.get()
+        select = ops.candidate_select if ops.accepts(pred) else functional.candidate_select
+        return select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target=target, outputs=outputs, max_len=max_len)
+
     @torch.no_grad()
-    def answer(self, anchor, relation, k=10, head=False, filtered=None, with_hops=False):
+    def answer(self, anchor, relation, k=10, head=False, filtered=None, with_hops=False, candidates=None, candidate_set=None):
         """Which entities complete ``(anchor, relation, ?)`` -- or, with ``head=True``, ``(?, relation, anchor)`` -- best first (an
         addition of this package; the reference's user masks the ``predict`` scores and calls ``torch.topk``).  ``anchor`` /
         ``relation``: int64 ``(Q,)``, ``relation`` in ``[0, R)``.  Entities that complete the query in the current context's
         filter graph are left out (``filtered``, default ``self.filtered_ranking``).  Returns ``(entities int64 (Q, k), scores
         fp32 (Q, k))`` in the order ``functional.topk_keys`` defines (score descending, ties by ascending entity, NaN last); a
         query with fewer than ``k`` candidates ends in ``-1`` / ``-inf``.  ``with_hops``: a third result, :meth:`answer_hops`
-        of the returned entities -- an answer farther from its anchor than the model has layers was scored without the anchor."""
-        anchor, q_rel, base = self.answer_queries(anchor, relation, head)
+        of the returned entities -- an answer farther from its anchor than the model has layers was scored without the anchor.
+        ``candidates`` (a ``data.CandidateSets``): only the entities of each query's set are admissible answers
+        (``functional.candidate_select``) -- the set ``candidate_set[q]`` int64 ``(Q,)`` in ``[-1, S)``, ``-1``
+        = every entity; by default the set of the query relation in ``[0, 2R)`` (``relation``, with ``head`` ``relation + R``),
+        which needs the ``2R`` sets of ``data.relation_candidates``.  ``candidates=None``: every entity, the path above."""
+        if candidates is None:
+            if candidate_set is not None:
+                raise ValueError("answer: candidate_set needs candidates")
+            anchor, q_rel, base = self.answer_queries(anchor, relation, head)
+        elif candidate_set is None:
+            anchor, q_rel, base = self.answer_queries(anchor, relation, head)
+            sets, set_of, max_len = self.answer_sets(candidates, q_rel)
+        else:
+            if not hasattr(candidates, "num_sets"):
+                raise ValueError("answer: candidates must be a data.CandidateSets, got %s" % type(candidates).__name__)
+            anchor, q_rel, base, set_of, any_all = self.answer_queries(anchor, relation, head, candidate_set, candidates.num_sets)
+            sets, set_of, max_len = self.answer_sets(candidates, q_rel, set_of, any_all)
         keys, n_rel, n_node = self.answer_filter(head, filtered)
         k = int(k)
         if not 1 <= k <= TOPK_MAX:
@@ -576,10 +634,46 @@ class KnowledgeGraphCompletion(nn.Module):
             zero = torch.zeros_like(anchor)
             batch = torch.stack([zero, anchor, base] if head else [anchor, zero, base], dim=1)
             pred = self.predict(batch)[:, 1 if head else 0]
-        value, index = backend.get().topk_keys(pred, k, keys, anchor, base, n_rel, n_node)
+        if candidates is None:
+            value, index = backend.get().topk_keys(pred, k, keys, anchor, base, n_rel, n_node)
+        else:
+            if n_node != pred.shape[1]:
+                raise RuntimeError("answer: the scores list %d entities but the completion keys were built over %d nodes (filter "
+                                   "graph and fact graph must share the entity set)" % (pred.shape[1], n_node))
+            found = self._candidate_select(pred, sets, set_of, k, keys, anchor, base, n_rel, None, ("top_index", "top_value"),
+                                           max_len)
+            index, value = found.top_index, found.top_value
         if with_hops:
             return index, value, self.answer_hops(anchor, index)
         return index, value
+
+    @torch.no_grad()
+    def rank_among(self, batch, candidates, pred=None):
+        """Type-constrained filtered ranks of a batch of triples ``(B, 3)`` rows of (h, t, r): every tail is ranked among the set
+        ``r`` of ``candidates`` and every head among the set ``r + R`` (the ``2R`` sets of ``data.relation_candidates``: the
+        range of the relation and of its inverse), both sides filtered like :meth:`rank_batch`.  Returns ``(ranks int64 (B, 2),
+        member bool (B, 2), n_free int64 (B, 2))``, column 0 the tail side: ``rank = 1 + #{e in the set, not a known completion :
+        score[target] <= score[e]}`` -- computed whether or not the target is in its set, ``member`` says which it is, a caller
+        leaves the others out (``engine.evaluate_constrained``) --, ``n_free`` the number of candidates ranked among.  One launch
+        per side on the device (``functional.candidate_select``), the dense twin on CPU tensors; no host synchronisation."""
+        if pred is None:
+            pred = self.predict(batch)
+        batch = self._select(batch)
+        pos_h_index, pos_t_index, pos_r_index = batch.t()
+        sets, _, max_len = self.answer_sets(candidates, None)
+        graph = self.graph
+        n_rel = max(graph.num_relation, 1)
+        if graph.num_node != pred.shape[-1]:
+            raise RuntimeError("rank_among: the scores list %d entities but the completion keys were built over %d nodes"
+                               % (pred.shape[-1], graph.num_node))
+        keys = (graph.completion_keys(0), graph.completion_keys(1)) if self.filtered_ranking else (None, None)
+        outputs = ("rank", "n_free", "member")
+        tail = self._candidate_select(pred[:, 0], sets, pos_r_index, 1, keys[0], pos_h_index, pos_r_index, n_rel, pos_t_index,
+                                      outputs, max_len)
+        head = self._candidate_select(pred[:, 1], sets, pos_r_index + self.fact_graph.num_relation, 1, keys[1], pos_t_index,
+                                      pos_r_index, n_rel, pos_h_index, outputs, max_len)
+        return (torch.stack([tail.rank, head.rank], dim=1), torch.stack([tail.member, head.member], dim=1).bool(),
+                torch.stack([tail.n_free, head.n_free], dim=1))
 
     # ------------------------------------------------------------------ relation prediction (DESIGN.md section 20)
     def relation_queries(self, h, t, candidates=None, inverse=False):
