@@ -1065,6 +1065,37 @@ int ultra_candidate_select_f32(const float *pred, int64_t n_query, int64_t n_nod
                                int64_t *top_index, float *top_value, int64_t *rank, int64_t *n_free, uint8_t *member,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* Type-constrained strict negatives: every row draws its corrupted entities from a LIST of admissible entities minus the known
+ * completions (csrc/candidate_negative.hip; an addition of this package).
+ * Replaces: nothing the reference has -- its strict negatives (ultra/task.py:102-118) are drawn among ALL entities that are not
+ * known completions, which is ultra_strict_negative here.  The sets are those of ultra_candidate_select_f32: ptr int64
+ * [n_sets + 1], items int32 [n_items], the items of a set ASCENDING and DISTINCT, each in [0, n_node).
+ * For row q:  s = set_of[q * index_stride];  the list L_q is items[ptr[s] .. ptr[s + 1]) for s in [0, n_sets) and EVERY entity
+ * [0, n_node) for s == -1 (set_of == NULL: -1 for every row);  the completions are C_q = {e : base_q + e in keys} with
+ * base_q = (anchor_q * n_rel + rel_q) * n_node, anchor / rel read at [q * index_stride] -- the sorted distinct keys of
+ * ultra_strict_negative (n_keys == 0: nothing is known);  F_q = L_q \ C_q in ascending entity order, n_free_q = |F_q|.
+ *   n_free_q >= min_free:  out[q, j] = F_q[min((long long)(rand[q, j] * (float)n_free_q), n_free_q - 1)] -- the fp32 product,
+ *                          truncated and clamped, the draw of ultra_strict_negative;
+ *   otherwise the row FALLS BACK to the unconstrained strict draw: out[q, j] is the word ultra_strict_negative returns for the
+ *                          same rand[q, j] (0 when every entity is a completion).
+ * rand fp32 [n_query, n_sample] in [0, 1), out int64 [n_query, n_sample], both contiguous;  n_free (optional, NULL: not
+ * written) int64 [n_query]: the SET-SIDE count |L_q \ C_q| -- a caller sees which rows fell back as n_free < min_free.
+ * One launch, one workgroup of 256 threads per row, the grid sized by the rows alone; no workspace.  Lists of at most 32768
+ * positions are looked up once, longer ones twice in the same launch (count, then chunk by chunk).  Counts are integers and
+ * every sample is independent: every schedule, eager or replayed from a hipGraph, gives the same words.
+ * No id read from device memory addresses anything unchecked: a set id outside [-1, n_sets) is the empty list, ptr values are
+ * clamped to [0, n_items], an item outside [0, n_node) is skipped; a rand of exactly 1.0, a negative one or a NaN gives an
+ * in-range entity.  (Items that are not ascending and distinct give an unspecified draw, never an out-of-bounds access.)
+ * Before any device work, with nothing written: n_node in [1, 2^31), n_rel > 0 and n_node * n_rel * n_node < 2^63, n_sample >= 1,
+ * min_free >= 1, n_query < 2^31, no negative count or stride: ULTRA_ERR_BAD_SHAPE otherwise;  ptr and items come together
+ * (items may be NULL when n_items == 0), anchor / rel / rand / out given, keys given when n_keys > 0: ULTRA_ERR_NULL_POINTER
+ * otherwise.  n_query == 0: ULTRA_OK, nothing is written.
+ * Only enqueues work: no allocation, no host synchronisation, capturable. */
+int ultra_constrained_negative(const int64_t *keys, int64_t n_keys, const int64_t *anchor, const int64_t *rel,
+                               const int64_t *set_of, int64_t index_stride, int64_t n_query, int64_t n_rel, int64_t n_node,
+                               const int64_t *ptr, const int32_t *items, int64_t n_sets, int64_t n_items, const float *rand,
+                               int64_t n_sample, int64_t min_free, int64_t *out, int64_t *n_free, void *stream);
+
 /* Divergence guard of training steps (csrc/guard.inc): does a LIST of fp32 tensors hold a non-finite element?
  * Replaces: torch.autograd.set_detect_anomaly(True) of the reference's training run (script/run_full.py:127), which raises at the
  * step that produces a NaN.  A step replayed from a hipGraph cannot raise, so the verdict is left in a device RECORD that the

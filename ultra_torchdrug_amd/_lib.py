@@ -123,6 +123,7 @@ SIGNATURES = {
     "ultra_candidate_select_workspace": (sz, [i64, i64, i64]),
     "ultra_candidate_select_f32": (i32, [vp, i64, i64, i64, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, vp,
                                         vp, vp, vp, vp, sz, vp]),
+    "ultra_constrained_negative": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, i64, vp, i64, i64, vp, vp, vp]),
     "ultra_set_boundary_f32": (i32, [vp, i64, i64, i64, vp, vp, i64, vp, vp, vp]),
     "ultra_set_boundary_backward_workspace": (sz, [i64, i64, i64]),
     "ultra_set_boundary_backward_f32": (i32, [vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, sz, vp]),

@@ -26,6 +26,10 @@ optional functions: a backend is an object with this complete interface
                                         ``engine.evaluate_constrained``; device tensors run ``ultra_candidate_select_f32``, CPU
                                         tensors the dense twin; as ``relation_select``, a backend whose ``accepts()`` is false
                                         is not asked: the callers go to ``functional.candidate_select``)
+    constrained_negatives              (type-constrained strict negatives, DESIGN.md section 22: device tensors run
+                                        ``ultra_constrained_negative``, CPU tensors ``functional.dense_constrained_negatives``,
+                                        the same definition in torch ops.  Nothing in the task reaches it yet:
+                                        ``_strict_negative`` keeps its two ``strict_negatives`` calls)
     set_boundary                       (reached ONLY from ``project`` / ``project_train``, on tensors the backend accepts; a
                                         backend whose ``accepts()`` is false gets ``functional.dense_set_boundary``, the same
                                         definition in torch ops.  Under grad it and ``score_all_entities`` are differentiable

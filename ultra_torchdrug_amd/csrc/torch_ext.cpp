@@ -32,6 +32,8 @@
 //   ultra_mi::candidate_select(pred, ptr?, items?, set_of?, max_len, keys?, anchor?, rel?, n_rel, target?, k, outputs)
 //       -> (top_index, top_value, rank, n_free, member)
 //       candidate sets: rank, membership, count and the k best entities of every query among its set of entities (CUDA key)
+//   ultra_mi::constrained_negatives(keys, anchor, rel, set_of?, ptr?, items?, n_rel, n_node, rand, min_free) -> (out, n_free)
+//       type-constrained strict negatives: draws from every row's set of entities minus the known completions (CUDA key)
 //   plan-based forms used by ultra_torchdrug_amd.functional (the plan = the bytes of one `ultra_segments` struct in a
 //   CPU uint8 tensor; the device arrays it points to are owned by the Python RelCSR object):
 //   ultra_mi::rspmm_plan_fwd(plan, relation, input, add_rows?, boundary_node?, boundary_value?, n_src, sum_op, mul_op) -> Tensor
@@ -1442,9 +1444,59 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> candidate_select_hip(
     return {top_index, top_value, rank, n_free, member};
 }
 
+// ------------------------------------------------------------------------------------------------ constrained_negatives
+// Type-constrained strict negatives (include/ultra_rspmm.h, ultra_constrained_negative): every row draws
+// from its set of admissible entities minus the known completions, or falls back to the unconstrained strict draw.  Device key
+// only (CPU tensors take functional.dense_constrained_negatives).  anchor / rel / set_of go to the kernel as they are and share
+// one positive element stride; rand is contiguous.  Returns (out (B, S), n_free (B,)).
+std::tuple<Tensor, Tensor> constrained_negatives_hip(const Tensor &keys, const Tensor &anchor, const Tensor &rel,
+                                                     const optional<Tensor> &set_of, const optional<Tensor> &ptr,
+                                                     const optional<Tensor> &items, int64_t n_rel, int64_t n_node,
+                                                     const Tensor &rand, int64_t min_free) {
+    check_dense(rand, "rand", at::kFloat, rand);
+    TORCH_CHECK(rand.dim() == 2 && rand.size(1) >= 1 && rand.is_contiguous(),
+                "ultra_mi::constrained_negatives: rand must be contiguous fp32 (B, S >= 1)");
+    const int64_t B = rand.size(0), S = rand.size(1);
+    auto given = [](const optional<Tensor> &x) { return x.has_value() && x->defined(); };
+    auto vector_of = [&](const Tensor &x, const char *name, at::ScalarType dtype, int64_t n, bool dense) -> const void * {
+        check_dense(x, name, dtype, rand);
+        TORCH_CHECK(x.dim() == 1 && (n < 0 || x.numel() == n), "ultra_mi::constrained_negatives: ", name, " has shape ", x.sizes());
+        TORCH_CHECK(!dense || x.is_contiguous(), "ultra_mi::constrained_negatives: ", name, " must be contiguous");
+        return x.data_ptr();
+    };
+    const auto *keys_p = static_cast<const int64_t *>(vector_of(keys, "keys", at::kLong, -1, true));
+    const auto *anchor_p = static_cast<const int64_t *>(vector_of(anchor, "anchor", at::kLong, B, false));
+    const auto *rel_p = static_cast<const int64_t *>(vector_of(rel, "rel", at::kLong, B, false));
+    const auto *set_p = given(set_of) ? static_cast<const int64_t *>(vector_of(*set_of, "set_of", at::kLong, B, false)) : nullptr;
+    const auto *ptr_p = given(ptr) ? static_cast<const int64_t *>(vector_of(*ptr, "ptr", at::kLong, -1, true)) : nullptr;
+    const auto *items_p = given(items) ? static_cast<const int32_t *>(vector_of(*items, "items", at::kInt, -1, true)) : nullptr;
+    TORCH_CHECK(given(ptr) == given(items) && (!given(ptr) || ptr->numel() >= 1),
+                "ultra_mi::constrained_negatives: ptr (S + 1,) and items come together");
+    TORCH_CHECK(!given(set_of) || given(ptr), "ultra_mi::constrained_negatives: set_of needs the sets");
+    int64_t index_stride = 1;
+    if (B > 1) {
+        index_stride = anchor.stride(0);
+        TORCH_CHECK(index_stride >= 1 && rel.stride(0) == index_stride && (!given(set_of) || set_of->stride(0) == index_stride),
+                    "ultra_mi::constrained_negatives: anchor, rel and set_of must share one positive stride");
+    }
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(rand.device());
+    const auto i64 = rand.options().dtype(at::kLong);
+    Tensor out = at::empty({B, S}, i64);
+    Tensor n_free = at::empty({B}, i64);
+    if (B == 0) return {out, n_free};
+    check_status(ultra_constrained_negative(keys_p, keys.numel(), anchor_p, rel_p, set_p, index_stride, B, n_rel, n_node, ptr_p,
+                                            items_p, ptr_p ? ptr->numel() - 1 : 0, given(items) ? items->numel() : 0,
+                                            rand.data_ptr<float>(), S, min_free, out.data_ptr<int64_t>(),
+                                            n_free.data_ptr<int64_t>(), current_stream(rand)),
+                 "ultra_constrained_negative");
+    return {out, n_free};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
+    m.def("constrained_negatives(Tensor keys, Tensor anchor, Tensor rel, Tensor? set_of, Tensor? ptr, Tensor? items, int n_rel, "
+          "int n_node, Tensor rand, int min_free) -> (Tensor, Tensor)");
     m.def("candidate_select(Tensor pred, Tensor? ptr, Tensor? items, Tensor? set_of, int max_len, Tensor? keys, Tensor? anchor, "
           "Tensor? rel, int n_rel, Tensor? target, int k, int outputs) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("relation_select(Tensor score, Tensor? cand, Tensor? keys_head, Tensor? keys_tail, Tensor? h, Tensor? t, Tensor? target, "
@@ -1499,6 +1551,7 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("hop_distance", hop_distance_hip);
     m.impl("relation_select", relation_select_hip);
     m.impl("candidate_select", candidate_select_hip);
+    m.impl("constrained_negatives", constrained_negatives_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)

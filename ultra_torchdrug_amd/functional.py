@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "candidate_select", "dense_candidate_select", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "candidate_select", "dense_candidate_select", "constrained_negatives", "dense_constrained_negatives", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1595,6 +1595,27 @@ def dense_candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, targ
         "dense_candidate_select", pred, sets, set_of, k, keys, anchor, rel, n_rel, target, outputs, max_len)
     rows, n = pred.shape
     dev = pred.device
+    listed, known = _dense_listed_known(rows, n, dev, sets, set_of, max_len, keys, anchor, rel, n_rel)
+    cand = listed & ~known
+    n_free = cand.sum(dim=1)
+    rank = torch.zeros(rows, dtype=torch.int64, device=dev)
+    member = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    if target is not None:
+        valid = (target >= 0) & (target < n)
+        at = target.clamp(0, n - 1)[:, None]
+        rank = torch.where(valid, 1 + ((pred.gather(1, at) <= pred) & cand).sum(dim=1), rank)
+        member = (valid & listed.gather(1, at)[:, 0]).to(torch.uint8)
+    top_value = top_index = None
+    if "top_index" in outputs or "top_value" in outputs:
+        group = torch.where(cand, torch.isnan(pred).long(), torch.full((), 2, dtype=torch.int64, device=dev))
+        top_value, top_index = _dense_topk_groups(pred, group, int(k))
+    full = dict(top_index=top_index, top_value=top_value, rank=rank, n_free=n_free, member=member)
+    return CandidateSelection(*[full[name] if name in outputs else None for name in CANDIDATE_OUTPUTS])
+
+
+def _dense_listed_known(rows, n, dev, sets, set_of, max_len, keys, anchor, rel, n_rel):
+    """The dense ``(rows, n)`` bool masks of the candidate-set operators' torch twins: ``listed[q, e]`` -- entity ``e`` is in the
+    list of row ``q`` (its first ``max_len`` positions) -- and ``known[q, e]`` -- ``e`` completes ``(anchor[q], rel[q], ?)``."""
     every = torch.arange(n, device=dev)[None, :] < max_len                       # the list of s == -1
     if set_of is None:
         listed = every.expand(rows, n)
@@ -1621,21 +1642,7 @@ def dense_candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, targ
         row = torch.repeat_interleave(torch.arange(rows, device=dev), count)
         at = torch.arange(int(count.sum()), device=dev) - torch.repeat_interleave(count.cumsum(0) - count, count) + first[row]
         known[row, keys[at] - base[row]] = True
-    cand = listed & ~known
-    n_free = cand.sum(dim=1)
-    rank = torch.zeros(rows, dtype=torch.int64, device=dev)
-    member = torch.zeros(rows, dtype=torch.uint8, device=dev)
-    if target is not None:
-        valid = (target >= 0) & (target < n)
-        at = target.clamp(0, n - 1)[:, None]
-        rank = torch.where(valid, 1 + ((pred.gather(1, at) <= pred) & cand).sum(dim=1), rank)
-        member = (valid & listed.gather(1, at)[:, 0]).to(torch.uint8)
-    top_value = top_index = None
-    if "top_index" in outputs or "top_value" in outputs:
-        group = torch.where(cand, torch.isnan(pred).long(), torch.full((), 2, dtype=torch.int64, device=dev))
-        top_value, top_index = _dense_topk_groups(pred, group, int(k))
-    full = dict(top_index=top_index, top_value=top_value, rank=rank, n_free=n_free, member=member)
-    return CandidateSelection(*[full[name] if name in outputs else None for name in CANDIDATE_OUTPUTS])
+    return listed, known
 
 
 def candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target=None, outputs=CANDIDATE_OUTPUTS, max_len=None):
@@ -1678,6 +1685,90 @@ def candidate_select(pred, sets, set_of, k, keys, anchor, rel, n_rel, target=Non
                 target.stride(0) if (target is not None and rows > 1) else 1, k, *[out[name] for name in CANDIDATE_OUTPUTS],
                 ws, ws_bytes)
     return CandidateSelection(**out)
+
+
+# ------------------------------------------------------------------------------------------ type-constrained strict negatives
+def _negative_arguments(name, keys, anchor, rel, n_rel, n_node, rand, sets, set_of, min_free, device_only):
+    """The checked arguments of :func:`constrained_negatives` / :func:`dense_constrained_negatives`:
+    ``(anchor, rel, set_of, index stride)``."""
+    if rand.dim() != 2 or rand.dtype != torch.float32 or rand.shape[1] < 1 or not rand.is_contiguous() \
+            or (device_only and not rand.is_cuda):
+        raise RuntimeError("%s: rand must be contiguous fp32 (B, S >= 1)%s" % (name, " on the HIP device" if device_only else ""))
+    rows, dev = rand.shape[0], rand.device
+    n_rel, n_node, min_free = int(n_rel), int(n_node), int(min_free)
+    if not 1 <= n_node < 2 ** 31 or n_rel <= 0 or float(n_node) ** 2 * n_rel >= 2.0 ** 63:
+        raise RuntimeError("%s: %d entities (1 to 2^31 - 1) and %d relations (positive, 64-bit keys)" % (name, n_node, n_rel))
+    if min_free < 1:
+        raise RuntimeError("%s: min_free must be at least 1, got %d" % (name, min_free))
+    if keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous() or keys.device != dev:
+        raise RuntimeError("%s: keys must be a contiguous int64 vector on %s" % (name, dev))
+    if sets is None and set_of is not None:
+        raise RuntimeError("%s: set_of needs the sets" % name)
+    if sets is not None:
+        if int(sets.num_node) != n_node:
+            raise RuntimeError("%s: %d entities but the sets were built over %d" % (name, n_node, int(sets.num_node)))
+        if (sets.ptr.dtype != torch.int64 or sets.items.dtype != torch.int32 or sets.ptr.dim() != 1 or sets.items.dim() != 1
+                or sets.ptr.numel() < 1 or sets.ptr.device != dev or sets.items.device != dev
+                or not sets.ptr.is_contiguous() or not sets.items.is_contiguous()):
+            raise RuntimeError("%s: the sets must hold contiguous ptr int64 (S + 1,) and items int32 on %s" % (name, dev))
+    if set_of is not None and (set_of.dtype != torch.int64 or set_of.shape != (rows,) or set_of.device != dev):
+        raise RuntimeError("%s: set_of must be int64 (%d,) on %s" % (name, rows, dev))
+    anchor, rel, stride = _index_pair(name, anchor, rel, rows, dev)
+    if set_of is not None and rows > 1 and set_of.stride(0) != stride:
+        anchor, rel, set_of, stride = anchor.contiguous(), rel.contiguous(), set_of.contiguous(), 1
+    return anchor, rel, set_of, stride
+
+
+def dense_constrained_negatives(keys, anchor, rel, n_rel, n_node, rand, sets=None, set_of=None, min_free=1, return_free=False):
+    """:func:`constrained_negatives` in torch ops over dense ``(B, N)`` masks -- the twin CPU tensors take, and the side the
+    kernel is compared with (it runs on any device; building the masks reads the host once).  With ``free = listed & ~known``
+    and ``n_free = free.sum(-1)``, a row with ``n_free >= min_free`` returns ``free.nonzero()``'s entities at
+    ``(rand * n_free).long()`` -- the indexing of ``task.variadic_sample`` with ``rand`` given -- and any other row the same over
+    ``~known``; an index is clamped into its row, and a row without any entity to draw gives 0."""
+    anchor, rel, set_of, _ = _negative_arguments("dense_constrained_negatives", keys, anchor, rel, n_rel, n_node, rand, sets,
+                                                 set_of, min_free, False)
+    rows, n = rand.shape[0], int(n_node)
+    listed, known = _dense_listed_known(rows, n, rand.device, sets, set_of, n, keys, anchor, rel, n_rel)
+    free = listed & ~known
+    n_free = free.sum(dim=1)
+    constrained = n_free >= int(min_free)
+    mask = torch.where(constrained[:, None], free, ~known)
+    size = mask.sum(dim=1)
+    index = (rand * size.unsqueeze(-1)).long()                                   # fp32 product, truncated
+    index = torch.minimum(index, size.unsqueeze(-1) - 1).clamp(min=0)            # (1.0 rounds up; negative / NaN -> 0)
+    out = torch.searchsorted(mask.long().cumsum(dim=1), index + 1)               # the (index)-th True of the row
+    out = torch.where(size.unsqueeze(-1) > 0, out, torch.zeros_like(out))
+    return (out, n_free) if return_free else out
+
+
+def constrained_negatives(keys, anchor, rel, n_rel, n_node, rand, sets=None, set_of=None, min_free=1, return_free=False):
+    """Type-constrained strict negatives (``ultra_constrained_negative``; the contract is in ``include/ultra_rspmm.h``, DESIGN.md
+    section 22): row ``q`` draws ``rand.shape[1]`` entities from the list of set ``set_of[q]`` of ``sets`` (a
+    ``data.CandidateSets`` over ``n_node`` entities; ``-1`` = every entity; ``set_of=None``: ``-1`` for all rows) minus the
+    entities that complete ``(anchor[q], rel[q], ?)`` in ``keys`` -- ``F[min((rand * n_free).long(), n_free - 1)]`` with ``F``
+    ascending, the draw of :func:`strict_negatives`.  A row with fewer than ``min_free`` free entities in its set, an empty
+    set or a set id outside ``[-1, S)`` falls back to the row :func:`strict_negatives` returns for the same ``rand``.
+    ``anchor`` / ``rel`` / ``set_of`` int64 ``(B,)`` may be views that share one positive stride (the columns of ``batch.t()``);
+    ``rand`` contiguous fp32 ``(B, S)`` on the device.  Returns int64 ``(B, S)`` and, with ``return_free``, ``n_free`` int64
+    ``(B,)``: the SET-SIDE count of every row (a row fell back iff ``n_free < min_free``).  One launch, no ``(B, N)`` mask, no
+    host synchronisation.  CPU tensors take :func:`dense_constrained_negatives`."""
+    if not rand.is_cuda:
+        return dense_constrained_negatives(keys, anchor, rel, n_rel, n_node, rand, sets, set_of, min_free, return_free)
+    anchor, rel, set_of, stride = _negative_arguments("constrained_negatives", keys, anchor, rel, n_rel, n_node, rand, sets,
+                                                      set_of, min_free, True)
+    rows, n_sample = rand.shape
+    ptr, items = (sets.ptr, sets.items) if sets is not None else (None, None)
+    if _torch_ext.binding() == "torch":
+        out, n_free = _torch_ext.load().constrained_negatives(keys, anchor, rel, set_of, ptr, items, int(n_rel), int(n_node), rand,
+                                                              int(min_free))
+        return (out, n_free) if return_free else out
+    out = torch.empty(rows, n_sample, dtype=torch.int64, device=rand.device)
+    n_free = torch.empty(rows, dtype=torch.int64, device=rand.device) if return_free else None
+    if rows:
+        _launch(rand.device, "ultra_constrained_negative", keys, keys.numel(), anchor, rel, set_of, stride, rows, int(n_rel),
+                int(n_node), ptr, items, ptr.numel() - 1 if ptr is not None else 0, items.numel() if items is not None else 0,
+                rand, n_sample, int(min_free), out, n_free)
+    return (out, n_free) if return_free else out
 
 
 def dense_set_boundary(member, query, floor=None, with_count=False):
