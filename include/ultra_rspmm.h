@@ -1301,6 +1301,48 @@ int ultra_relation_graph_marks(const int32_t *head_ptr, const int32_t *head_rel,
                                int64_t n_node, int64_t n_rel, uint8_t *marks, void *stream);
 
 /*
+ * Per-query relation tables of ALL layers of a NeuralBellmanFordNetwork in one launch:
+ *
+ *     out[l][r, b, d] = bias[l][r*D_l + d] + sum_k w[l][r*D_l + d, k] * query[b, k]
+ *             l < n_layers, r < n_rel, b < batch, d < D_l = dims[l], k < K
+ *
+ * = relation_linear(graph.query).view(B, R, D).transpose(0, 1) of GeneralizedRelationalConvNBF(dependent=True)
+ * (/root/reference/ultra/layer.py:48,58-61) for every layer, written straight into the (n_rel, batch * D_l) layout the rspmm
+ * reads.  query [batch] rows of K floats, row b at query + b * stride_q (stride_q >= K); w[l] [n_rel * D_l, K], bias[l]
+ * [n_rel * D_l] and out[l] [n_rel, batch, D_l] are contiguous.  w, bias and out are HOST arrays of n_layers device pointers
+ * (as in ultra_relation_project_f32) and dims a host array: layers may differ in width.  1 <= n_layers <= 8.
+ * Summation order: every entry is ONE fmaf chain that starts from the bias and takes k ASCENDING:
+ *     acc = bias[l][j];  for k = 0 .. K-1:  acc = fmaf(w[l][j, k], query[b, k], acc)
+ * whatever D_l, K and batch are.  When K % 4 == 0 and every w[l] is 16-byte aligned (in the backward every d_w[l] too) the weight
+ * rows are loaded (and the d_w rows stored) 16 bytes at a time; any other K >= 1 takes 4-byte accesses and the same chain: the
+ * same bits.  The query block is always read 4 bytes at a time: its alignment and stride never choose the route.
+ * All addressing is 64-bit; the grid follows from the shapes alone; no allocation, no host read: the call is capturable.
+ * Before any launch: ULTRA_ERR_BAD_SHAPE for n_layers outside [1, 8], K < 1, a D_l < 1, a negative batch or n_rel, or
+ * stride_q < K; ULTRA_ERR_NULL_POINTER for a NULL query, dims, array or array entry.  batch == 0 or n_rel == 0: ULTRA_OK,
+ * nothing is launched.
+ *
+ * Backward (ultra_query_tables_backward_f32): grad[l] [n_rel, batch, D_l] is the gradient of out[l]; a NULL entry means zeros.
+ *     d_w[l][(r,d), k] = sum_b grad[l][r, b, d] * query[b, k]           an fmaf chain from +0.0, b ascending
+ *     d_bias[l][(r,d)] = sum_b grad[l][r, b, d]                         b ascending
+ *     d_query[b, k]    = sum_l sum_(r,d) grad[l][r, b, d] * w[l][(r,d), k]
+ * d_w[l], d_bias[l] (host arrays of device pointers, every entry given) and d_query [batch, K] contiguous are written
+ * completely.  d_query is summed without atomics: a workgroup adds 512 consecutive rows (r,d) of one layer in ascending order
+ * (fmaf chain from +0.0) into a partial [batch, K] block of `workspace`, and the same call then adds the partial blocks in
+ * ASCENDING block order, layer by layer; the layers whose grad is NULL have no blocks in that sum.  The same bits on every call.
+ * workspace: ultra_query_tables_backward_workspace(n_layers, batch, n_rel, dims, K) bytes (0 for a shape the entry refuses).
+ * Statuses as the forward, and ULTRA_ERR_NULL_POINTER for a NULL grad array, d_w / d_bias (array or entry), d_query or a NULL
+ * workspace of a non-empty shape; ULTRA_ERR_WORKSPACE for a workspace that is too small.
+ */
+int ultra_query_tables_f32(const float *query, int64_t stride_q, const float *const *w, const float *const *bias,
+                           float *const *out, const int64_t *dims, int64_t n_layers, int64_t batch, int64_t n_rel, int64_t K,
+                           void *stream);
+size_t ultra_query_tables_backward_workspace(int64_t n_layers, int64_t batch, int64_t n_rel, const int64_t *dims, int64_t K);
+int ultra_query_tables_backward_f32(const float *query, int64_t stride_q, const float *const *w, const float *const *grad,
+                                    float *const *d_w, float *const *d_bias, float *d_query, void *workspace,
+                                    size_t workspace_bytes, const int64_t *dims, int64_t n_layers, int64_t batch, int64_t n_rel,
+                                    int64_t K, void *stream);
+
+/*
  * On-box calibration for the HBM roofline line of bench.py ("confirm on the box with a copy / gather
  * calibration, report both"): the bare gather of `n_index` random 256-byte rows of `table` (n_rows x 64 fp32) -- four rows
  * per wave-instruction (buffer_load_dwordx4), eight instructions in flight per wave, every lane's values summed into

@@ -7,8 +7,10 @@ host-side mirror of the reference's operator / layer / model interface for that 
 from . import _lib
 from .relcsr import RelCSR, Segments
 from .functional import generalized_rspmm, rotate_rspmm, rotate_rspmm_forward, rspmm_forward
+from .nbfnet import NBFNet, NeuralBellmanFordNetwork
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "RelCSR", "Segments", "library_path", "require_library"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "RelCSR", "Segments", "library_path", "require_library",
+           "NeuralBellmanFordNetwork", "NBFNet"]
 __version__ = "0.1.0"
 
 

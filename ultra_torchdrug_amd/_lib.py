@@ -110,6 +110,9 @@ SIGNATURES = {
     "ultra_relation_project_f32": (i32, [vp, i64, i64, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "ultra_relation_project_backward_blocks": (i32, [i32, i64, i64, i64, vp]),
     "ultra_relation_project_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i64, i64, vp]),
+    "ultra_query_tables_f32": (i32, [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+    "ultra_query_tables_backward_workspace": (sz, [i64, i64, i64, vp, i64]),
+    "ultra_query_tables_backward_f32": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, sz, vp, i64, i64, i64, i64, vp]),
     "ultra_filtered_rank": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "ultra_filtered_rank_keys": (i32, [vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
     "ultra_strict_negative": (i32, [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp]),

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 EXT_PATH = os.environ.get("ULTRA_TORCH_EXT") or os.path.join(_HERE, "libultra_torch_ext.so")
 OPS = ("build_relcsr", "rspmm_fwd", "rspmm_bwd", "rspmm_plan_fwd", "rspmm_plan_bwd", "beam_search_step", "beam_search_step_batch", "abi_version",
        "rspmm_rotate_fwd", "rspmm_rotate_bwd", "rspmm_rotate_plan_fwd", "rspmm_rotate_plan_bwd", "hop_distance",
-       "relation_select", "candidate_select", "constrained_negatives")
+       "relation_select", "candidate_select", "constrained_negatives", "query_tables", "query_tables_backward")
 _loaded = None
 
 

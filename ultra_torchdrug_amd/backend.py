@@ -36,6 +36,12 @@ optional functions: a backend is an object with this complete interface
                                         -- ``ultra_set_boundary_backward_f32`` / ``ultra_score_backward_f32`` -- and are passed
                                         through as they are: ``project_train`` needs nothing else of a backend)
 
+    query_tables                       (reached ONLY from ``nbfnet.NeuralBellmanFordNetwork``: the relation tables of all its
+                                        ``dependent`` layers from one launch, ``ultra_query_tables_f32``, one autograd node under
+                                        grad; CPU and non-fp32 tensors take ``functional.dense_query_tables`` inside it.  The model
+                                        asks a backend for it by name: one that does not have the entry -- the object backends of
+                                        the tests -- lets every layer build its own table, the reference's route)
+
     pna_supported, pna_statistics, pna_node_table, pna_combine_forward
                                        (reached ONLY on device tensors the backend accepts, in inference, with ``layer.PNA_NATIVE``
                                         set: the one-walk statistics and the fused 13-wide epilogue of ``aggregate_func="pna"``;

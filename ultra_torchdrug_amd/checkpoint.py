@@ -98,6 +98,13 @@ def load_checkpoint(task, checkpoint, fix_reasoner=False, optimizer=None, map_lo
     for key in GRAPH_KEYS:
         if key in model_state and not torch.is_tensor(model_state[key]):
             model_state.pop(key)
+    if len(getattr(task, "rel_models", ())) == 0 and hasattr(task, "rel_models"):
+        # a task over a model with a relation vocabulary of its own (task.build_nbfnet): a non-strict load would drop the
+        # relation models of an ULTRA checkpoint without a word and leave the entity model half loaded
+        foreign = sorted(k for k in model_state if k.startswith("rel_models."))
+        if foreign:
+            raise ValueError("checkpoint holds %d `rel_models.*` tensors (%s, ...): it belongs to a task with relation models, this "
+                             "task (%s) has none" % (len(foreign), foreign[0], type(task.model).__name__))
     if fix_reasoner:
         current = task.state_dict()
         for key in [k for k in model_state if any(mark in k for mark in _REASONER_MARKS)]:

@@ -1492,9 +1492,103 @@ std::tuple<Tensor, Tensor> constrained_negatives_hip(const Tensor &keys, const T
     return {out, n_free};
 }
 
+// ------------------------------------------------------------------------------------------------ query_tables
+// Per-query relation tables of all layers of a NeuralBellmanFordNetwork in one launch, and their backward
+// (include/ultra_rspmm.h, ultra_query_tables_f32 / ultra_query_tables_backward_f32).  Device key only
+// (CPU tensors take functional.dense_query_tables).  query fp32 (B, K) with unit column stride (rows may be strided); weights[l]
+// (n_rel * D_l, K) and biases[l] (n_rel * D_l) contiguous.
+struct QueryTableShape {
+    int64_t batch, K, stride_q;
+    std::vector<int64_t> dims;
+};
+
+QueryTableShape query_table_shape(const char *what, const Tensor &query, const at::TensorList &weights, int64_t n_rel) {
+    check_dense(query, "query", at::kFloat, query);
+    TORCH_CHECK(query.dim() == 2 && query.size(1) >= 1 && query.stride(1) == 1 && n_rel >= 0, what,
+                ": query must be fp32 (B, K >= 1) with a unit column stride");
+    QueryTableShape s;
+    s.batch = query.size(0);
+    s.K = query.size(1);
+    s.stride_q = s.batch > 1 ? query.stride(0) : s.K;
+    TORCH_CHECK(weights.size() >= 1 && weights.size() <= 8, what, ": 1 to 8 layers, got ", weights.size());
+    for (const Tensor &w : weights) {
+        check_dense(w, "weight", at::kFloat, query);
+        TORCH_CHECK(w.dim() == 2 && w.size(1) == s.K && w.is_contiguous() && w.size(0) >= 1 && (n_rel == 0 || w.size(0) % n_rel == 0),
+                    what, ": a weight must be contiguous (n_rel * D, K), got ", w.sizes());
+        s.dims.push_back(n_rel ? w.size(0) / n_rel : w.size(0));
+    }
+    return s;
+}
+
+std::vector<Tensor> query_tables_hip(const Tensor &query, at::TensorList weights, at::TensorList biases, int64_t n_rel) {
+    const QueryTableShape s = query_table_shape("ultra_mi::query_tables", query, weights, n_rel);
+    TORCH_CHECK(biases.size() == weights.size(), "ultra_mi::query_tables: one bias per weight");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(query.device());
+    std::vector<Tensor> outs;
+    std::vector<const float *> w_p, b_p;
+    std::vector<float *> o_p;
+    for (size_t l = 0; l < weights.size(); ++l) {
+        check_dense(biases[l], "bias", at::kFloat, query);
+        TORCH_CHECK(biases[l].dim() == 1 && biases[l].size(0) == weights[l].size(0) && biases[l].is_contiguous(),
+                    "ultra_mi::query_tables: a bias must be contiguous (n_rel * D,)");
+        outs.push_back(at::empty({n_rel, s.batch * s.dims[l]}, query.options()));
+        w_p.push_back(weights[l].data_ptr<float>());
+        b_p.push_back(biases[l].data_ptr<float>());
+        o_p.push_back(outs.back().data_ptr<float>());
+    }
+    if (s.batch == 0 || n_rel == 0) return outs;
+    check_status(ultra_query_tables_f32(query.data_ptr<float>(), s.stride_q, w_p.data(), b_p.data(), o_p.data(), s.dims.data(),
+                                        (int64_t)weights.size(), s.batch, n_rel, s.K, current_stream(query)),
+                 "ultra_query_tables_f32");
+    return outs;
+}
+
+// returns d_weights..., d_biases..., d_query
+std::vector<Tensor> query_tables_backward_hip(const Tensor &query, at::TensorList weights,
+                                              const c10::List<c10::optional<Tensor>> &grads, int64_t n_rel) {
+    const QueryTableShape s = query_table_shape("ultra_mi::query_tables_backward", query, weights, n_rel);
+    TORCH_CHECK(grads.size() == weights.size(), "ultra_mi::query_tables_backward: one gradient (or None) per weight");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(query.device());
+    const size_t n = weights.size();
+    std::vector<Tensor> out, keep;
+    std::vector<const float *> w_p, g_p;
+    std::vector<float *> dw_p, db_p;
+    for (size_t l = 0; l < n; ++l) out.push_back(at::empty_like(weights[l]));
+    for (size_t l = 0; l < n; ++l) out.push_back(at::empty({weights[l].size(0)}, query.options()));
+    out.push_back(at::empty({s.batch, s.K}, query.options()));
+    for (size_t l = 0; l < n; ++l) {
+        const c10::optional<Tensor> g = grads.get(l);
+        const float *g_ptr = nullptr;
+        if (g.has_value() && g->defined()) {
+            check_dense(*g, "grad", at::kFloat, query);
+            TORCH_CHECK(g->numel() == n_rel * s.batch * s.dims[l] && g->is_contiguous(),
+                        "ultra_mi::query_tables_backward: a gradient must be contiguous with n_rel * B * D entries");
+            keep.push_back(*g);
+            g_ptr = g->data_ptr<float>();
+        }
+        w_p.push_back(weights[l].data_ptr<float>());
+        g_p.push_back(g_ptr);
+        dw_p.push_back(out[l].data_ptr<float>());
+        db_p.push_back(out[n + l].data_ptr<float>());
+    }
+    if (s.batch == 0 || n_rel == 0) {
+        for (size_t l = 0; l < 2 * n; ++l) out[l].zero_();
+        return out;
+    }
+    const size_t ws_bytes = ultra_query_tables_backward_workspace((int64_t)n, s.batch, n_rel, s.dims.data(), s.K);
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(ws_bytes, 4) / 4}, query.options());
+    check_status(ultra_query_tables_backward_f32(query.data_ptr<float>(), s.stride_q, w_p.data(), g_p.data(), dw_p.data(),
+                                                 db_p.data(), out[2 * n].data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                                                 s.dims.data(), (int64_t)n, s.batch, n_rel, s.K, current_stream(query)),
+                 "ultra_query_tables_backward_f32");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ultra_mi, m) {
+    m.def("query_tables(Tensor query, Tensor[] weights, Tensor[] biases, int n_rel) -> Tensor[]");
+    m.def("query_tables_backward(Tensor query, Tensor[] weights, Tensor?[] grads, int n_rel) -> Tensor[]");
     m.def("constrained_negatives(Tensor keys, Tensor anchor, Tensor rel, Tensor? set_of, Tensor? ptr, Tensor? items, int n_rel, "
           "int n_node, Tensor rand, int min_free) -> (Tensor, Tensor)");
     m.def("candidate_select(Tensor pred, Tensor? ptr, Tensor? items, Tensor? set_of, int max_len, Tensor? keys, Tensor? anchor, "
@@ -1552,6 +1646,8 @@ TORCH_LIBRARY_IMPL(ultra_mi, CUDA, m) {
     m.impl("relation_select", relation_select_hip);
     m.impl("candidate_select", candidate_select_hip);
     m.impl("constrained_negatives", constrained_negatives_hip);
+    m.impl("query_tables", query_tables_hip);
+    m.impl("query_tables_backward", query_tables_backward_hip);
 }
 
 // host kernels of the same three operators (config 1: `--gpus null`)

@@ -23,7 +23,7 @@ import torch
 from . import _lib, _torch_ext
 from .relcsr import RelCSR
 
-__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "candidate_select", "dense_candidate_select", "constrained_negatives", "dense_constrained_negatives", "RelCSR"]
+__all__ = ["generalized_rspmm", "rspmm_forward", "rotate_rspmm", "rotate_rspmm_forward", "rotate_rspmm_backward_weight", "rspmm_backward_weight_blocks", "rotate_rspmm_backward_weight_blocks", "beam_search_step_batch", "first_layer_forward", "dense_layer_forward", "combine_forward", "combine", "linear_forward", "linear_supported", "score_all_entities", "relation_stack_inputs", "statistics", "bce_adversarial_loss", "candidate_tiles", "candidate_rows", "score_candidates", "hop_distance", "pack_sets", "unpack_sets", "seed_sets", "column_mask", "project_sets_exact", "set_ranks", "relation_select", "dense_relation_select", "candidate_select", "dense_candidate_select", "constrained_negatives", "dense_constrained_negatives", "query_tables", "dense_query_tables", "RelCSR"]
 
 # Plans built from raw sparse tensors, most recent last.  Every entry holds strong references to the index and
 # value tensors it was built from, so a (data_ptr, version) key cannot be reused by another live tensor.
@@ -1120,6 +1120,138 @@ def relation_project_train(relation, weights):
         raise RuntimeError("relation_project_train: at most 8 layers per call")
     flat = [t for layer_weights in weights for t in layer_weights]
     return list(_ProjectFunction.apply(relation, *flat))
+
+
+# Per-query relation tables of a NeuralBellmanFordNetwork (csrc/query_tables.hip): ULTRA_QUERY_TABLES=0
+# sends every layer through its own nn.Linear + transposing copy again (A/B timing; the same definition, ATen's rounding).
+QUERY_TABLES = _env_bool("ULTRA_QUERY_TABLES", True)
+QUERY_TABLES_MAX_LAYERS = 8
+
+
+def dense_query_tables(query, weights, biases, n_rel):
+    """:func:`query_tables` in torch ops, in the dtype of ``query`` (the host twin and the fp64 definition): per layer
+    ``F.linear(query, w, b).view(B, n_rel, D).transpose(0, 1)`` (``ultra/layer.py:58-61``) as an ``(n_rel, B * D)`` table."""
+    batch = query.shape[0]
+    return [torch.nn.functional.linear(query, w, b).view(batch, n_rel, -1).transpose(0, 1).reshape(n_rel, -1)
+            for w, b in zip(weights, biases)]
+
+
+def _query_table_arguments(what, query, weights, biases, n_rel):
+    """Checks of :func:`query_tables_forward` / :func:`query_tables_backward`; returns ``(query, weights, biases, dims)`` with
+    the query's rows dense (a column view keeps its row stride) and the parameters contiguous."""
+    n_rel = int(n_rel)
+    if query.dim() != 2 or query.shape[1] < 1 or query.dtype != torch.float32 or not query.is_cuda or n_rel < 0:
+        raise RuntimeError("%s: query must be fp32 (B, K >= 1) on a HIP device, got %s" % (what, tuple(query.shape)))
+    if not 1 <= len(weights) <= QUERY_TABLES_MAX_LAYERS or (biases is not None and len(biases) != len(weights)):
+        raise RuntimeError("%s: 1 to %d layers with one bias each, got %d" % (what, QUERY_TABLES_MAX_LAYERS, len(weights)))
+    if query.stride(1) != 1 or (query.shape[0] > 1 and query.stride(0) < query.shape[1]):
+        query = query.contiguous()
+    K = query.shape[1]
+    dims, keep_w, keep_b = [], [], []
+    for l, w in enumerate(weights):
+        if w.dim() != 2 or w.shape[1] != K or w.dtype != torch.float32 or w.device != query.device \
+                or (n_rel and (w.shape[0] % n_rel or not w.shape[0])) or (not n_rel and w.shape[0] < 1):
+            raise RuntimeError("%s: weight %d must be fp32 (n_rel * D, %d) on %s, got %s" % (what, l, K, query.device, tuple(w.shape)))
+        dims.append(w.shape[0] // n_rel if n_rel else w.shape[0])
+        keep_w.append(w.detach().contiguous())
+        if biases is not None:
+            b = biases[l]
+            if b.dtype != torch.float32 or b.device != query.device or tuple(b.shape) != (w.shape[0],):
+                raise RuntimeError("%s: bias %d must be fp32 (%d,) on %s" % (what, l, w.shape[0], query.device))
+            keep_b.append(b.detach().contiguous())
+    return query, keep_w, keep_b, dims
+
+
+def _row_stride(query):
+    return query.stride(0) if query.shape[0] > 1 else query.shape[1]
+
+
+def query_tables_forward(query, weights, biases, n_rel):
+    """The tables of :func:`query_tables` without autograd: one launch of ``ultra_query_tables_f32`` for all layers."""
+    query, w, b, dims = _query_table_arguments("query_tables", query.detach(), weights, biases, n_rel)
+    n_rel, batch, K = int(n_rel), query.shape[0], query.shape[1]
+    if _torch_ext.binding() == "torch":
+        return list(_torch_ext.load().query_tables(query, w, b, n_rel))
+    outs = [torch.empty(n_rel, batch * d, dtype=torch.float32, device=query.device) for d in dims]
+    if batch and n_rel:
+        _launch(query.device, "ultra_query_tables_f32", query, _row_stride(query), _pointer_array(w), _pointer_array(b),
+                _pointer_array(outs), (ctypes.c_int64 * len(dims))(*dims), len(dims), batch, n_rel, K)
+    return outs
+
+
+def query_tables_backward(query, weights, grads, n_rel):
+    """``(d_weights, d_biases, d_query)`` of :func:`query_tables` for the table gradients ``grads`` (``(n_rel, B * D_l)`` each,
+    ``None`` = zeros): ONE call of ``ultra_query_tables_backward_f32``, deterministic (no atomics; the partial sums of
+    ``d_query`` are added in ascending block order)."""
+    query, w, _, dims = _query_table_arguments("query_tables_backward", query.detach(), weights, None, n_rel)
+    n_rel, batch, K = int(n_rel), query.shape[0], query.shape[1]
+    if len(grads) != len(w):
+        raise RuntimeError("query_tables_backward: %d gradients for %d layers" % (len(grads), len(w)))
+    keep = []
+    for l, g in enumerate(grads):
+        if g is not None:
+            if g.dtype != torch.float32 or g.device != query.device or g.numel() != n_rel * batch * dims[l]:
+                raise RuntimeError("query_tables_backward: gradient %d must be fp32 with %d x %d x %d entries on %s"
+                                   % (l, n_rel, batch, dims[l], query.device))
+            g = g.detach().contiguous()
+        keep.append(g)
+    if _torch_ext.binding() == "torch":
+        out = list(_torch_ext.load().query_tables_backward(query, w, keep, n_rel))
+        return out[:len(w)], out[len(w):2 * len(w)], out[-1]
+    dev = query.device
+    d_w = [torch.empty_like(t) for t in w]
+    d_b = [torch.empty(t.shape[0], dtype=torch.float32, device=dev) for t in w]
+    d_query = torch.empty(batch, K, dtype=torch.float32, device=dev)
+    if not (batch and n_rel):
+        for t in d_w + d_b:
+            t.zero_()
+        return d_w, d_b, d_query
+    c_dims = (ctypes.c_int64 * len(dims))(*dims)
+    need = int(_lib.load().ultra_query_tables_backward_workspace(len(dims), batch, n_rel, c_dims, K))
+    ws = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
+    _launch(dev, "ultra_query_tables_backward_f32", query, _row_stride(query), _pointer_array(w), _pointer_array(keep),
+            _pointer_array(d_w), _pointer_array(d_b), d_query, ws, need, c_dims, len(dims), batch, n_rel, K)
+    return d_w, d_b, d_query
+
+
+class _QueryTablesFunction(torch.autograd.Function):
+    """All layers' per-query relation tables as ONE autograd node: forward = ``ultra_query_tables_f32``, backward =
+    ``ultra_query_tables_backward_f32`` (one call for the gradients of every weight, every bias and the query)."""
+
+    @staticmethod
+    def forward(ctx, n_rel, query, *flat):
+        n = len(flat) // 2
+        ctx.n_rel = n_rel
+        # a table nothing reads arrives in backward as None, not as a tensor of zeros: the C entry takes NULL for it and skips
+        # that layer's d_query blocks
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(query, *flat[:n])
+        return tuple(query_tables_forward(query, flat[:n], flat[n:], n_rel))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        query, *weights = ctx.saved_tensors
+        d_w, d_b, d_query = query_tables_backward(query, weights, list(grads), ctx.n_rel)
+        n = len(weights)
+        need = ctx.needs_input_grad
+        return (None, d_query if need[1] else None,
+                *[g if need[2 + i] else None for i, g in enumerate(d_w)],
+                *[g if need[2 + n + i] else None for i, g in enumerate(d_b)])
+
+
+def query_tables(query, weights, biases, n_rel):
+    """The relation tables of every ``dependent`` layer of a :class:`NeuralBellmanFordNetwork` from ONE launch: ``query`` fp32
+    ``(B, K)`` (the query relations' embeddings), ``weights[l]`` ``(n_rel * D_l, K)`` and ``biases[l]`` ``(n_rel * D_l,)`` (the
+    layers' ``relation_linear``).  Returns one ``(n_rel, B * D_l)`` table per layer -- ``relation_linear(query).view(B, n_rel,
+    D_l).transpose(0, 1).flatten(1)`` (``ultra/layer.py:58-61``) in the summation order ``include/ultra_rspmm.h`` documents -- as
+    one autograd node whose backward is one call too.  At most 8 layers.  CPU tensors and tensors that are not fp32 take
+    :func:`dense_query_tables`, the same definition in torch ops."""
+    tensors = [query] + list(weights) + list(biases)
+    if not query.is_cuda or any(t.dtype != torch.float32 or t.device != query.device for t in tensors):
+        return dense_query_tables(query, weights, biases, n_rel)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return list(_QueryTablesFunction.apply(int(n_rel), query, *weights, *biases))
+    return query_tables_forward(query, weights, biases, n_rel)
 
 
 def prepare_queries(batch, rel_rep, n_base_rel):

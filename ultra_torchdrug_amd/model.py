@@ -127,11 +127,7 @@ class TransferNBFNet(nn.Module):
         query -- in place of the one-hot rows at ``h_index``, which is then not read (pass ``None``); the layers get it in its
         dense form only, so no shortcut that rests on a one-row boundary is taken."""
         bs = r_index.shape[0]
-        if self.query.dim() == 2:
-            query = self.query[r_index]
-        else:
-            # (row r_index[b] of block b; as a gather its backward is one scatter, advanced indexing's is a sort plus ~10 launches)
-            query = self.query.gather(1, r_index.view(bs, 1, 1).expand(bs, 1, self.query.shape[-1])).squeeze(1)
+        query = self._query_rows(r_index)
         given = boundary is not None
         if not given:
             index = h_index.unsqueeze(-1).expand_as(query)
@@ -143,7 +139,7 @@ class TransferNBFNet(nn.Module):
         # this instead of the dense tensor in every layer's epilogue); a given boundary has many rows per query: dense only
         graph.boundary_sparse = None if given else (h_index.to(torch.int32), query)
 
-        graph.relation_tables = self._relation_tables(bs)
+        graph.relation_tables = self._layer_tables(graph, bs)
         hiddens, step_graphs = [], []
         layer_input = boundary
         # (only with the grouped relation tables: a layer that projects its own table sends gradient to the relation
@@ -284,14 +280,7 @@ class TransferNBFNet(nn.Module):
         if not (0 <= h < graph.num_node and 0 <= t < graph.num_node and 0 <= r < 2 * graph.num_relation):
             raise IndexError("visualize: h, t must lie in [0, %d) and r in [0, %d): got (%d, %d, %d)"
                              % (graph.num_node, 2 * graph.num_relation, h, t, r))
-        self.query = rel_query_list[0]
-        if len(rel_query_list) > 1:
-            assert len(rel_query_list) == len(self.layers) + 1
-            for i, conv in enumerate(self.layers):
-                conv.relation = rel_query_list[i + 1]
-        else:
-            for conv in self.layers:
-                conv.relation = rel_query_list[0]
+        self._install_relations(rel_query_list)
         graph = self._undirected(graph)
 
         with torch.enable_grad():
@@ -376,19 +365,12 @@ class TransferNBFNet(nn.Module):
             if rel.dim() == 3 and rel.shape[0] != n_query:
                 raise ValueError("edge_gradients_batch: relation representations of %d rows for %d triples" % (rel.shape[0], n_query))
         und = self._undirected(graph)
-        if not self._native_edge_grad_stack(und, rel_query_list[0].dtype):
+        if not self._native_edge_grad_stack(und, self._relation_dtype(rel_query_list)):
             per_triple = [self.edge_gradients(graph, [rel[b:b + 1] if rel.dim() == 3 else rel for rel in rel_query_list],
                                               h_index[b:b + 1], t_index[b:b + 1], r_index[b:b + 1]) for b in range(n_query)]
             edge_grads = [torch.stack([g[i] for g in per_triple]) for i in range(len(self.layers))]
             return (edge_grads, (h, t, r)) if with_ids else edge_grads
-        self.query = rel_query_list[0]
-        if len(rel_query_list) > 1:
-            assert len(rel_query_list) == len(self.layers) + 1
-            for i, conv in enumerate(self.layers):
-                conv.relation = rel_query_list[i + 1]
-        else:
-            for conv in self.layers:
-                conv.relation = rel_query_list[0]
+        self._install_relations(rel_query_list)
         graph = und
 
         with torch.enable_grad():
@@ -513,6 +495,41 @@ class TransferNBFNet(nn.Module):
         weights, paths = zip(*sorted(zip(weights, paths), reverse=True)[:topk])
         return paths, weights
 
+    # ---- where the relation representations enter: the hooks a model with parameters of its own in their place overrides
+    # (nbfnet.NeuralBellmanFordNetwork: a learned embedding of query relations, relation tables that are a linear map of the query)
+    def _install_relations(self, rel_query_list, strict=True):
+        """model.py:149-156: the query table and every layer's relation input from the relation stack's output(s)."""
+        self.query = rel_query_list[0]
+        if len(rel_query_list) > 1:
+            if strict:
+                assert len(rel_query_list) == len(self.layers) + 1
+            for i, conv in enumerate(self.layers):
+                conv.relation = rel_query_list[i + 1]
+        else:
+            for conv in self.layers:
+                conv.relation = rel_query_list[0]
+
+    def _query_table(self):
+        """The tensor the query rows are taken from: ``(2R, D)``, or ``(B, 2R, D)`` with one block per query."""
+        return self.query
+
+    def _query_rows(self, r_index):
+        """``(B, D)``: the row ``r_index[b]`` of the query table (of block ``b`` of a per-query table)."""
+        table = self._query_table()
+        if table.dim() == 2:
+            return table[r_index]
+        bs = r_index.shape[0]
+        # (row r_index[b] of block b; as a gather its backward is one scatter, advanced indexing's is a sort plus ~10 launches)
+        return table.gather(1, r_index.view(bs, 1, 1).expand(bs, 1, table.shape[-1])).squeeze(1)
+
+    def _relation_dtype(self, rel_query_list):
+        return rel_query_list[0].dtype
+
+    def _layer_tables(self, graph, batch_size):
+        """``{id(layer): (R, B * D) table}`` for the layers whose tables one launch makes (``graph.query`` holds the query rows
+        by now), or ``None``: every layer builds its own."""
+        return self._relation_tables(batch_size)
+
     def _relation_tables(self, batch_size):
         """On the GPU with per-query relation representations and the shipped 64 -> 64 -> 64 projections: the
         ``(R, B * D)`` relation tables of ALL layers from one launch (each layer otherwise issues two linear launches
@@ -593,8 +610,11 @@ class TransferNBFNet(nn.Module):
         tables = ops.relation_project(rel_rep, [entry["project"] for entry in stack], repeat=2)
         if not layer._frontier_tables_finite(tables[0]):         # (eager calls only) the first layer's shortcut needs finite tables
             return None
-        boundary = (anchor32, query)
-        n_node = und.num_node
+        return self._fast_layers(ops, csr, stack, tables, (anchor32, query), query, und.num_node, n_query)
+
+    def _fast_layers(self, ops, csr, stack, tables, boundary, query, n_node, n_query):
+        """The launches of the fused inference sequence once the queries and the layers' relation tables exist (``stack``: the
+        ``combine`` entries of :meth:`_fast_stack`; ``boundary``: the sparse form ``(anchor int32, query)``): scores ``(Q, N)``."""
         hidden = None
         listed = None
         for i, entry in enumerate(stack):
@@ -638,9 +658,7 @@ class TransferNBFNet(nn.Module):
         fused score head does not cover this model (the caller then goes through ``forward``)."""
         if not graph.num_relation or not self._fused_head_ok(h_index, None):
             return None
-        self.query = rel_query_list[0]
-        for i, conv in enumerate(self.layers):
-            conv.relation = rel_query_list[i + 1] if len(rel_query_list) > 1 else rel_query_list[0]
+        self._install_relations(rel_query_list, strict=False)
         graph = self._undirected(graph)
         parts = self.bellmanford(graph, h_index, r_index, want_feature=False)
         first, second = self.mlp.layers
@@ -675,15 +693,10 @@ class TransferNBFNet(nn.Module):
     def _project(self, graph, rel_query_list, member, r_index, floor):
         if not graph.num_relation:
             raise ValueError("project needs a relational graph")
-        self.query = rel_query_list[0]
-        for i, conv in enumerate(self.layers):
-            conv.relation = rel_query_list[i + 1] if len(rel_query_list) > 1 else rel_query_list[0]
+        self._install_relations(rel_query_list, strict=False)
         graph = self._undirected(graph)
         n_query = r_index.shape[0]
-        if self.query.dim() == 2:
-            query = self.query[r_index]
-        else:
-            query = self.query.gather(1, r_index.view(n_query, 1, 1).expand(n_query, 1, self.query.shape[-1])).squeeze(1)
+        query = self._query_rows(r_index)
         if tuple(member.shape) != (n_query, graph.num_node):
             raise ValueError("project: member must be (%d, %d), got %s" % (n_query, graph.num_node, tuple(member.shape)))
         ops = backend.get()
@@ -740,16 +753,9 @@ class TransferNBFNet(nn.Module):
                 if not (graph.num_relation and self._removal_by_zero_weight()):
                     graph, keep = graph.edge_mask(keep), None
 
-        self.query = rel_query_list[0]
-        if len(rel_query_list) > 1:
-            assert len(rel_query_list) == len(self.layers) + 1
-            for i, conv in enumerate(self.layers):
-                conv.relation = rel_query_list[i + 1]
-        else:
-            for conv in self.layers:
-                conv.relation = rel_query_list[0]
+        self._install_relations(rel_query_list)
         if metric is not None:
-            q = self.query.detach()
+            q = self._query_table().detach()
             ops = backend.get()
             if ops.accepts(q) and q.dtype == torch.float32:
                 metric["query_norm"], metric["query_mean"], metric["query_std"] = ops.statistics(q).unbind(0)

@@ -403,9 +403,17 @@ class KnowledgeGraphCompletion(nn.Module):
     def _select(self, batch):
         """Multi-graph pre-training batches are ``(triples, graph_id)`` (task.py:722-731): switch to that graph."""
         if isinstance(batch, (tuple, list)):
+            self._needs_relation_models("multi-graph batches")
             batch, graph_id = batch
             self.use(graph_id)
         return batch
+
+    def _needs_relation_models(self, what):
+        """Calls that rest on relation representations computed per graph -- relation prediction, logical queries, batches that
+        name their graph -- are not defined for an entity model with a learned relation vocabulary of its own."""
+        if len(self.rel_models) == 0:
+            raise TypeError("%s: not available for %s, whose relation embeddings are tied to one vocabulary (a task without "
+                            "relation models)" % (what, type(self.model).__name__))
 
     def predict(self, batch, all_loss=None, metric=None):
         batch = self._select(batch)
@@ -774,6 +782,7 @@ class KnowledgeGraphCompletion(nn.Module):
         * C`` columns, not ``P * C``.  (A model without the fused all-entity score head scores a column through ``predict``, which
         computes the triple's other side too.)  The relation cache (:meth:`cache_relation_representations`) is honoured; without
         one the relation stack runs once per distinct base relation of the call (:meth:`relation_tables_of`)."""
+        self._needs_relation_models("relation_scores")
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("relation_scores: batch_size must be positive, got %d" % batch_size)
@@ -795,6 +804,7 @@ class KnowledgeGraphCompletion(nn.Module):
         ``(h, c, t)``, or ``(t, c - R, h)`` for an inverse id ``c >= R`` (``filtered``, default ``self.filtered_ranking``) -- in the
         order ``functional.relation_select`` defines: score descending, equal scores by ascending position in the candidate list,
         NaN last; a pair with fewer than ``k`` such candidates ends in ``-1`` / ``-inf``.  Scores: :meth:`relation_scores`."""
+        self._needs_relation_models("answer_relation")
         k = int(k)
         if not 1 <= k <= TOPK_MAX:
             raise ValueError("answer_relation: 1 to %d relations per pair, got %d" % (TOPK_MAX, k))
@@ -855,6 +865,7 @@ class KnowledgeGraphCompletion(nn.Module):
         ``threshold`` alone); ties at the cut all stay.  The defaults cut nothing: the plain fuzzy definition.  Which cut answers
         best is a question for benchmark data, and none has been run.  DECISION: a set that is empty after the cut has no
         answers -- its row is all zeros, not the scores of a zero boundary."""
+        self._needs_relation_models("project")
         self._check_cut(max_sources)
         member = torch.as_tensor(member, device=self.device)
         relation = torch.as_tensor(relation, device=self.device).reshape(-1)
@@ -873,6 +884,7 @@ class KnowledgeGraphCompletion(nn.Module):
     def query_inputs(self, structure, anchors, relations):
         """The parsed structure and the range-checked ``anchors`` int64 ``(Q, A)`` / ``relations`` int64 ``(Q, P)`` of
         :meth:`answer_query` on the task's device (one host read per call, as :meth:`answer_queries`)."""
+        self._needs_relation_models("logical queries")
         tree, n_anchor, n_relation = parse_query_structure(structure)
         anchors = torch.as_tensor(anchors, device=self.device)
         relations = torch.as_tensor(relations, device=self.device)
@@ -896,6 +908,7 @@ class KnowledgeGraphCompletion(nn.Module):
         through ``TransferNBFNet.project_train`` (:meth:`_project_sets_train`) -- the first hop too, as the one-hot set of
         membership 1.0, which is the boundary of ``score_all_entities`` for that anchor; the sparse first layer of the
         single-source route is given up there."""
+        self._needs_relation_models("logical queries")
         if differentiable:
             return self._query_memberships_train(tree, anchors, relations, threshold, max_sources)
         at = {"e": 0, "r": 0}
@@ -1340,6 +1353,23 @@ class KnowledgeGraphCompletion(nn.Module):
             all_loss = term if first else all_loss + term
             first = False
         return all_loss, metric
+
+
+def build_nbfnet(num_relation, input_dim=64, hidden_dims=(64,) * 6, **kwargs):
+    """The reference's non-transfer model (``models.NBFNet``, ``ultra/model.py:198-392``) under the task: a
+    :class:`~ultra_torchdrug_amd.nbfnet.NeuralBellmanFordNetwork` in the shipped layer configuration (distmult, sum, shortcut,
+    layer norm, ``dependent=True``) and NO relation models.  Keywords the model's constructor knows go to the model
+    (``message_func``, ``aggregate_func``, ``dependent``, ``remove_one_hop`` ...), every other one to the task."""
+    import inspect
+    from .nbfnet import NeuralBellmanFordNetwork
+    known = set(inspect.signature(NeuralBellmanFordNetwork.__init__).parameters) - {"self"}
+    model_kwargs = dict(message_func="distmult", aggregate_func="sum", short_cut=True, layer_norm=True, dependent=True)
+    model_kwargs.update({k: kwargs.pop(k) for k in list(kwargs) if k in known})
+    model = NeuralBellmanFordNetwork(input_dim=input_dim, hidden_dims=list(hidden_dims), num_relation=num_relation, **model_kwargs)
+    defaults = dict(criterion="bce", num_negative=128, strict_negative=True, adversarial_temperature=1.0,
+                    sample_weight=False, full_batch_eval=True)
+    defaults.update(kwargs)
+    return KnowledgeGraphCompletion(model, nn.ModuleList(), **defaults)
 
 
 def build_ultra(num_relation, input_dim=64, hidden_dims=(64,) * 6, rel_hidden=64, rel_layers=6, remove_one_hop=False,
